@@ -9,10 +9,22 @@ already resident in HBM.  The default workload is BASELINE.json's configs[2] —
 ("scans/s END-TO-END odometry", SURVEY.md §8d: SR -> LO -> laserMapping) is quoted on: before the W warm-up
 steps the sequence's first ``--map-warmup`` (200) sweeps are streamed through the same handle, untimed, so
 that the voxel-hash local map is at its steady-state size ("~200 scans") when the K timed sweeps run.
-``--workload lo`` is configs[1] (no mapping); the default run reports it as the extra leg ``configs1``.
+``--workload lo`` is configs[1] (no mapping); a ``--full`` run reports it as the extra leg ``configs1``.
 Rank r drives its own independent sequence (different scene / trajectory / noise seeds): the path
 shards one-sequence-per-GPU with no data-path collective; the only collective is an
 all-gather of the trajectories after the timed region.  Rank 0 prints ONE JSON line.
+
+A plain run does only what the headline needs: it synthesises the sweeps, warms up, times the K steps,
+writes the outputs if ``--dump-outputs DIR`` is given and prints the line.  Everything else — the
+per-kernel replay and the roofline, the extra legs (configs[1], batched sessions, latency, sustained
+streaming, host input, the VO / image stages), the CPU baseline and the parity check against the
+oracle — runs only with ``--full`` (``--no-kernel-timer``, ``--no-extras``, ``--no-cpu-baseline``
+switch single parts of it off again).
+
+``--dump-outputs DIR`` writes, after the timed region, what a caller of the timed path holds after its
+last step (rank 0): the trajectory rows of the K timed sweeps (float64), the last sweep's scan-registration
+clouds, its registered full-resolution cloud and the published map (float32 x, y, z, intensity), as
+DIR/<name>.npy.  The inputs are synthesised from fixed seeds, so the same arguments give the same inputs.
 
 PyTorch is plumbing only here (device buffers for the inputs, torch.distributed barrier / gather).
 The CPU oracle (oracle/) is used only for the ``cpu_baseline`` leg and the parity numbers — never
@@ -210,6 +222,35 @@ def sweep_bytes(c, with_mapping):
     return b_sr, b_lo, b_map
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+SCAN_CLOUDS = ((0, "laserCloud"), (1, "cornerPointsSharp"), (2, "cornerPointsLessSharp"), (3, "surfPointsFlat"), (4, "surfPointsLessFlat"))
+
+
+def timed_outputs(h, traj, first, with_mapping):
+    """What a caller of the timed path holds after its last step (c_api.h): the trajectory rows of the timed sweeps (f64: laser-odometry
+    world pose + mapping pose), the last sweep's scan-registration clouds and, with mapping, its full-resolution cloud registered in the
+    map frame and the published map (f32 x, y, z, intensity)."""
+    out = {"trajectory": traj[first:]}
+    for which, name in SCAN_CLOUDS:
+        out[name] = h.features(which)
+    if with_mapping:
+        out["laserCloudRegistered"] = h.features(11)
+        out["laserCloudMap"] = h.get_map()
+    return out
+
+
+def dump_outputs(path, arrays):
+    """DIR/<name>.npy per array in its own dtype; an array larger than its share of DUMP_LIMIT_BYTES is replaced by a fixed, seeded sample
+    of its rows, kept in order."""
+    os.makedirs(path, exist_ok=True)
+    share = DUMP_LIMIT_BYTES // len(arrays)
+    for name, a in arrays.items():
+        if a.nbytes > share:
+            keep = np.random.default_rng(0).choice(a.shape[0], share // (a.nbytes // a.shape[0]), replace=False)
+            a = a[np.sort(keep)]
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a))
+
+
 # ---------------------------------------------------------------------------------------------------- host-side helpers
 _SEQS = []
 _SYNTH = None
@@ -289,7 +330,12 @@ def main():
                     help="extra leg: stream the headline workload for about this long (sweeps replayed back and forth; 0 = skip)")
     ap.add_argument("--no-host-input", action="store_true", help="skip the host-input leg (vloam_process_scan from pinned / pageable memory)")
     ap.add_argument("--synth-procs", type=int, default=0, help="worker processes for the synthetic ray casting (0 = min(cores, 16))")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every leg beside the headline: per-kernel replay + roofline, the extra legs, CPU baseline + parity vs the oracle")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="", help="write what the timed path computed in its last step as DIR/<name>.npy")
     args = ap.parse_args()
+    if not args.full:   # a plain run: set-up, warm-up, the timed steps, the outputs and the line
+        args.no_cpu_baseline = args.no_kernel_timer = args.no_extras = True
 
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -410,6 +456,8 @@ def main():
         elapsed = multi.max_over_ranks(dist, elapsed, device=coll_dev)
     counts = h.counts()
     traj = h.trajectory()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, timed_outputs(h, traj, M0 + W, with_mapping))
     h.close()
 
     # ---- per-kernel leg: every kernel's launch duration, HIP events on the kernel's own stream.  A separate replay of the same
@@ -734,24 +782,6 @@ def main():
     if rank == 0:
         value = multi.aggregate_throughput(K, world, elapsed)
         assert len(trajectories) == world and all(t.shape == (T, 14) for t in trajectories)
-        b_sr, b_lo, b_map = sweep_bytes(counts, with_mapping)
-        # per-kernel table of the replay; the roofline object is the kernel with the largest share of GPU time
-        tot_ms = sum(v[0] for v in ktable.values()) or 1.0
-        kernels = {}
-        for name, (ms, n) in sorted(ktable.items(), key=lambda kv: -kv[1][0]):
-            kb = algorithmic_bytes(name, counts)
-            avg_us = 1e3 * ms / n
-            kernels[name] = {"launches_per_sweep": round(n / K, 2), "avg_us": round(avg_us, 2), "share_of_gpu_time": round(ms / tot_ms, 4),
-                             "algorithmic_bytes": int(kb), "achieved_GBs": round(kb / (avg_us * 1e-6) / 1e9, 2) if avg_us > 0 else 0.0}
-        kernel = args.kernel or (next(iter(kernels)) if kernels else ("k_lm_solve" if with_mapping else "k_sr_ring"))
-        kb = algorithmic_bytes(kernel, counts)
-        k_ms, k_launches = ktable.get(kernel, (0.0, 0))
-        avg_ms = k_ms / max(k_launches, 1)
-        traffic, traffic_src = pmc_traffic(args.workload, kernel)
-        achieved = kb / (avg_ms * 1e-3) / 1e9 if avg_ms > 0 else 0.0
-        # the same figures from the committed profiles of the same command, quoted only when they were measured on the kernel sources being timed
-        rp_us, rp_src = rocprof_avg_us(args.workload, kernel)
-        wait_pct, wait_src = sq_wait_pct(kernel)
         out = {
             "metric": "scans/sec end-to-end odometry on 64x2048 cloud", "value": value, "unit": "scans/s", "n_gpus": world, "steps": K,
             "warmup": W, "ms_per_step": 1e3 * elapsed / K, "per_rank_ms_per_step": [1e3 * s_ / K for s_ in per_rank_s],
@@ -766,26 +796,44 @@ def main():
                        "collective": None if dist is None else {"backend": dist.get_backend(), "world_size": dist.get_world_size(),
                                                                 "rccl_version": list(torch.cuda.nccl.version()) if dist.get_backend() == "nccl" else None},
                        "pipelining": "SR / LO / mapping of consecutive sweeps overlap on their own HIP streams (one sequence, one GPU)"},
-            "roofline": {"bound": "hbm", "kernel": kernel, "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": traffic_src,
-                         "algorithmic_bytes_per_launch": kb,
-                         "algorithmic_bytes_per_unit": ALGORITHMIC_UNIT.get(kernel),
-                         "avg_launch_us": 1e3 * avg_ms, "launches_timed": k_launches,
-                         "avg_launch_us_source": "HIP events around every launch of the kernel on its own stream, untraced replay of the timed sweeps (the bracket adds a few us to a ~30 us kernel; rocprof_* below is the kernel's own duration)",
-                         "rocprof_avg_launch_us": rp_us, "rocprof_source": rp_src,
-                         "frac_rocprof": (kb / (rp_us * 1e-6) / 1e9 / HBM_PEAK_GBS) if rp_us else None,
-                         # what the counters say the kernel draws from HBM: PMC bytes per launch / its duration / peak
-                         "counter_frac": (traffic / ((rp_us or 1e3 * avg_ms) * 1e-6) / 1e9 / HBM_PEAK_GBS) if traffic else None,
-                         "sq_wait_pct": wait_pct, "sq_wait_source": wait_src,
-                         "timed_region_s": elapsed,
-                         "sweep_algorithmic_bytes": {"B_SR": b_sr, "B_LO": b_lo, "B_MAP": b_map},
-                         "end_to_end_frac": (b_sr + b_lo + b_map) * value / world / 1e9 / HBM_PEAK_GBS},
             "counts_last_sweep": counts,
-            "kernels": kernels,
-            "reference_timers": {name: round(sum(1e3 * ktable[k][0] for k in ks if k in ktable) / K, 2) for name, ks in REFERENCE_TIMERS.items()
-                                 if any(k in ktable for k in ks)},
             "host": {"cpu": cpu_model(), "cores": cores, "synth_seconds": round(synth_s, 2), "synth_processes": procs},
         }
+        if args.full:   # per-kernel table of the replay and the roofline of the kernel with the largest share of GPU time
+            b_sr, b_lo, b_map = sweep_bytes(counts, with_mapping)
+            tot_ms = sum(v[0] for v in ktable.values()) or 1.0
+            kernels = {}
+            for name, (ms, n) in sorted(ktable.items(), key=lambda kv: -kv[1][0]):
+                kb = algorithmic_bytes(name, counts)
+                avg_us = 1e3 * ms / n
+                kernels[name] = {"launches_per_sweep": round(n / K, 2), "avg_us": round(avg_us, 2), "share_of_gpu_time": round(ms / tot_ms, 4),
+                                 "algorithmic_bytes": int(kb), "achieved_GBs": round(kb / (avg_us * 1e-6) / 1e9, 2) if avg_us > 0 else 0.0}
+            kernel = args.kernel or (next(iter(kernels)) if kernels else ("k_lm_solve" if with_mapping else "k_sr_ring"))
+            kb = algorithmic_bytes(kernel, counts)
+            k_ms, k_launches = ktable.get(kernel, (0.0, 0))
+            avg_ms = k_ms / max(k_launches, 1)
+            traffic, traffic_src = pmc_traffic(args.workload, kernel)
+            achieved = kb / (avg_ms * 1e-3) / 1e9 if avg_ms > 0 else 0.0
+            # the same figures from the committed profiles of the same command, quoted only when they were measured on the kernel sources being timed
+            rp_us, rp_src = rocprof_avg_us(args.workload, kernel)
+            wait_pct, wait_src = sq_wait_pct(kernel)
+            out["roofline"] = {"bound": "hbm", "kernel": kernel, "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                               "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": traffic_src,
+                               "algorithmic_bytes_per_launch": kb,
+                               "algorithmic_bytes_per_unit": ALGORITHMIC_UNIT.get(kernel),
+                               "avg_launch_us": 1e3 * avg_ms, "launches_timed": k_launches,
+                               "avg_launch_us_source": "HIP events around every launch of the kernel on its own stream, untraced replay of the timed sweeps (the bracket adds a few us to a ~30 us kernel; rocprof_* below is the kernel's own duration)",
+                               "rocprof_avg_launch_us": rp_us, "rocprof_source": rp_src,
+                               "frac_rocprof": (kb / (rp_us * 1e-6) / 1e9 / HBM_PEAK_GBS) if rp_us else None,
+                               # what the counters say the kernel draws from HBM: PMC bytes per launch / its duration / peak
+                               "counter_frac": (traffic / ((rp_us or 1e3 * avg_ms) * 1e-6) / 1e9 / HBM_PEAK_GBS) if traffic else None,
+                               "sq_wait_pct": wait_pct, "sq_wait_source": wait_src,
+                               "timed_region_s": elapsed,
+                               "sweep_algorithmic_bytes": {"B_SR": b_sr, "B_LO": b_lo, "B_MAP": b_map},
+                               "end_to_end_frac": (b_sr + b_lo + b_map) * value / world / 1e9 / HBM_PEAK_GBS}
+            out["kernels"] = kernels
+            out["reference_timers"] = {name: round(sum(1e3 * ktable[k][0] for k in ks if k in ktable) / K, 2) for name, ks in REFERENCE_TIMERS.items()
+                                       if any(k in ktable for k in ks)}
         if latency:
             out["latency"] = latency
         if sustained:

@@ -25,7 +25,7 @@ def test_bench_two_ranks_share_one_gpu_over_gloo():
     env = dict(os.environ, VLOAM_BENCH_BACKEND="gloo", MASTER_ADDR="127.0.0.1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "6", "--warmup", "2",
-           "--map-warmup", "8", "--no-extras", "--no-cpu-baseline", "--synth-procs", "2"]
+           "--map-warmup", "8", "--full", "--no-extras", "--no-cpu-baseline", "--synth-procs", "2"]
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{") and '"metric"' in ln]

@@ -10,8 +10,8 @@ cd $GRAFT_REPO_ROOT
 if [ -z "$NOTEST" ]; then
   timeout 1500 python -m pytest tests -m gpu -x -q > $OUT/pytest.log 2>&1; echo "pytest rc=$?" | tee -a $OUT/pytest.log; tail -3 $OUT/pytest.log
 fi
-timeout 900 python bench.py --steps 20 --warmup 5 > $OUT/bench_driver.json 2> $OUT/bench_driver.err; cut -c1-300 $OUT/bench_driver.json
-timeout 900 python bench.py > $OUT/bench_map.json 2> $OUT/bench_map.err; cut -c1-300 $OUT/bench_map.json
+timeout 900 python bench.py --full --steps 20 --warmup 5 > $OUT/bench_driver.json 2> $OUT/bench_driver.err; cut -c1-300 $OUT/bench_driver.json
+timeout 900 python bench.py --full > $OUT/bench_map.json 2> $OUT/bench_map.err; cut -c1-300 $OUT/bench_map.json
 export TMPDIR=/tmp
 for W in map lo; do
   (cd /tmp && timeout 600 rocprofv3 --kernel-trace --stats -d $OUT/prof_$W -- python $GRAFT_REPO_ROOT/bench.py --workload $W --synth-procs 1 --no-cpu-baseline --no-kernel-timer --no-extras > $OUT/prof_$W.log 2>&1)
