@@ -31,7 +31,8 @@ enum {
   VLOAM_OK = 0,
   VLOAM_ERR_INVALID = -1,     /* bad argument / unsupported scan_line (the reference ROS_BREAK()s) */
   VLOAM_ERR_HIP = -2,         /* a HIP runtime call failed; vloam_last_error() has the text */
-  VLOAM_ERR_CAPACITY = -3,    /* more points / ring length / map entries than the handle was sized for */
+  VLOAM_ERR_CAPACITY = -3,    /* more points / ring length / map entries than the handle was sized for (a scan line of more than
+                                 vloam_config::max_ring_points points: raise it, up to 16384) */
   VLOAM_ERR_EMPTY = -4,       /* no point survived NaN / minimum_range removal (reference: UB, scan_registration.cpp:166) */
   VLOAM_ERR_NO_DEVICE = -5,   /* no usable gfx950 device: there is NO CPU fallback */
   VLOAM_ERR_ORDER = -6        /* stage called out of the façade's order */
@@ -57,6 +58,7 @@ typedef struct vloam_config {
   int image_width;                 /* capacity of the image front-end (KITTI: 1242 x 375); 0 = none (0) */
   int image_height;
   int CLAHE;                       /* 1: cv::createCLAHE(2.0)->apply on every image first (vloam_main.launch:8)  (0) */
+  int max_ring_points;             /* capacity of one scan line: 4096 (0 = 4096); 4097 .. 16384 add the long ring tier  (4096) */
 } vloam_config;
 
 typedef struct vloam_calib {  /* row-major f32, as PointCloudUtil holds them (point_cloud_util.h:43-46) */

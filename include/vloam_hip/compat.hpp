@@ -105,6 +105,9 @@ inline Cloud from_cloud_ptr(const P& in) {
   return c;
 }
 
+// A Session / LidarOdometryMapping created with a vloam_config* takes the handle's capacities from it: max_points (points of a sweep),
+// map_capacity_log2, and max_ring_points (points of one scan line: 4096 by default; 4097 .. 16384 for sensors whose scan lines are longer —
+// an HDL-32E at 5 Hz, an HDL-64E with two lasers in one scan line, 4 096-column heads).
 class Session {  // one vloam_handle == one sequence on one GPU; shared by the three stage objects
  public:
   explicit Session(int device = 0, const vloam_config* cfg = nullptr) {

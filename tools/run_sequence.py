@@ -70,7 +70,10 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--velodyne", help="directory of KITTI raw velodyne .bin sweeps")
     ap.add_argument("--synthetic", type=int, default=0, help="number of synthetic 64 x --azimuth sweeps instead")
-    ap.add_argument("--azimuth", type=int, default=2048)
+    ap.add_argument("--azimuth", type=int, default=None, help="columns of a synthetic sweep (default: 2048, hdl64e: 2083)")
+    ap.add_argument("--sensor", choices=("default", "hdl64e"), default="default",
+                    help="synthetic sensor model (hdl64e: two lasers share a scan line now and then: lines of more than 4096 points)")
+    ap.add_argument("--max-ring-points", type=int, default=0, help="vloam_config::max_ring_points (0: the default, 4096; up to 16384)")
     ap.add_argument("--out", required=True)
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--mapping-skip-frame", type=int, default=2)
@@ -94,7 +97,7 @@ def main():
         n = len(files)
     else:
         synth = importlib.import_module("vloam_amd.synth")
-        seq = synth.SynthSequence(n_rings=64, n_azimuth=a.azimuth, n_sweeps=max(a.synthetic, 2) + 1)
+        seq = synth.SynthSequence(n_rings=64, n_azimuth=a.azimuth, n_sweeps=max(a.synthetic, 2) + 1, sensor=a.sensor)
         clouds = (seq.sweep(k) for k in range(a.synthetic))
         n = a.synthetic
     if n == 0:
@@ -122,7 +125,8 @@ def main():
         ih, iw = (kio.load_png_gray(real_images[0]).shape if real_images else (375, 1242))
         img_cfg = dict(image_width=int(iw), image_height=int(ih), CLAHE=int(a.clahe))
     loam = vl.LidarOdometryMapping(device=a.device, mapping_skip_frame=a.mapping_skip_frame, detach_VO_LO=0 if a.vloam else 1,
-                                   timing=1 if (a.metrics and not a.vloam) else 0, **img_cfg)
+                                   timing=1 if (a.metrics and not a.vloam) else 0, **img_cfg,
+                                   **({"max_ring_points": a.max_ring_points} if a.max_ring_points else {}))
     hd = loam.hd
     if a.vloam:
         if real_images:   # PointCloudUtil::loadTransformations (point_cloud_util.cpp:5-116)

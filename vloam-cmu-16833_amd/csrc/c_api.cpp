@@ -74,7 +74,7 @@ struct vloam_handle {
   int sel = 0;          // session the getters read (vloam_select_session)
   double* sync_pool = nullptr;
   bool counted_single = false; // this handle is in g_single_handles
-  int* ring_watch = nullptr;   // host-mapped [kMaxBatch]: a ring of that session came near the small ring tier's capacity (k_sr_ring)
+  int* ring_watch = nullptr;   // host-mapped [2][kMaxBatch]: a ring of that session came near the small ring tier's capacity / near kMaxRingLen (k_sr_ring)
   int* coop_flag = nullptr;    // host-mapped [1]: a cooperative solve of this handle degraded to one workgroup (k_lm_solve) — polled before every enqueue
   long long fallback_solves = 0;   // cooperative solves that degraded to one workgroup, as of the last vloam_sync
   int frame = 0;        // sweeps accepted (scan registration enqueued)
@@ -185,6 +185,15 @@ static vloam_status handle_layout(vloam_handle* h, Arena& A) {
   TAKE(a.dbg_label, (size_t)P);
   TAKE(a.dbg_cyc, (size_t)kMaxRings * 8);
   TAKE(a.dbg_feat_idx, 3 * kMaxLessSharp);
+  if (cfg->max_ring_points > kMaxRingLen) {   // the long ring tier's working arrays (k_sr_ring_long); nothing on a default handle
+    a.long_cap = cfg->max_ring_points;
+    a.long_kcap = 1;
+    while (a.long_kcap < a.long_cap) a.long_kcap <<= 1;
+    TAKE(a.long_keys, (size_t)kMaxRings * a.long_kcap);
+    TAKE(a.long_iscr, (size_t)kMaxRings * a.long_kcap);
+    TAKE(a.long_bytes, (size_t)kMaxRings * 4 * a.long_cap);
+    TAKE(a.long_ds, (size_t)kMaxRings * a.long_cap);
+  }
   for (int k = 1; k < vloam_handle::kSets; k++) h->sr[k] = a;
   for (int k = 0; k < vloam_handle::kSets; k++) {
     TAKE(h->sr[k].S, 1);
@@ -256,6 +265,7 @@ void vloam_default_config(vloam_config* c) {
   c->image_width = 0;
   c->image_height = 0;
   c->CLAHE = 0;
+  c->max_ring_points = kMaxRingLen;
 }
 
 const char* vloam_last_error(void) { return g_err.c_str(); }
@@ -270,6 +280,9 @@ vloam_status vloam_create_batch(const vloam_config* cfg, int device, int n_sessi
   }
   if (cfg->max_points < 64 || cfg->max_points > (1 << 24) || cfg->max_frames < 1 || cfg->mapping_skip_frame < 1) {  // 24-bit point tags
     set_err("bad capacity"); return VLOAM_ERR_INVALID;
+  }
+  if (cfg->max_ring_points != 0 && (cfg->max_ring_points < kMaxRingLen || cfg->max_ring_points > kMaxRingLenLong)) {
+    set_err("max_ring_points must be 0 or %d (default) .. %d", kMaxRingLen, kMaxRingLenLong); return VLOAM_ERR_INVALID;
   }
   // laser_mapping.cpp:95-101 takes any leaf; the reference's launch files use 0.2 / 0.4 (VLP-16, HDL-32) and 0.4 / 0.8 (KITTI).  Here the
   // position of a voxel in the gathered map cloud (the 5-NN tie rank) is a 32-bit mixed-radix number: 75 cubes x radix^3 voxels.
@@ -315,6 +328,7 @@ vloam_status vloam_create_batch(const vloam_config* cfg, int device, int n_sessi
   }
   vloam_handle* h = new vloam_handle;
   h->cfg = *cfg;
+  if (h->cfg.max_ring_points == 0) h->cfg.max_ring_points = kMaxRingLen;   // zero-initialised configs: the default
   h->device = device;
   *out = nullptr;
   vloam_status st = VLOAM_OK;
@@ -409,8 +423,8 @@ vloam_status vloam_create_batch(const vloam_config* cfg, int device, int n_sessi
       tf_identity(&init.tf.base_T_cam0); tf_identity(&init.tf.velo_T_cam0); tf_identity(&init.tf.cam0_curr_T_cam0_last);  // visual_odometry.cpp:73-74
       tf_identity(&init.tf.cam0_curr_LOT_cam0_prev); tf_identity(&init.tf.world_VOT_base_last);                            // vloam_tf.cpp:10-11
       HIPCHK(hipMemcpyAsync(h->lo, &init, sizeof(init), hipMemcpyHostToDevice, h->stream));
-      if (hipHostMalloc((void**)&h->ring_watch, sizeof(int) * kMaxBatch, hipHostMallocMapped) != hipSuccess) { h->ring_watch = nullptr; set_err("hipHostMalloc failed"); return VLOAM_ERR_HIP; }
-      for (int b = 0; b < kMaxBatch; b++) h->ring_watch[b] = 0;
+      if (hipHostMalloc((void**)&h->ring_watch, sizeof(int) * 2 * kMaxBatch, hipHostMallocMapped) != hipSuccess) { h->ring_watch = nullptr; set_err("hipHostMalloc failed"); return VLOAM_ERR_HIP; }
+      for (int b = 0; b < 2 * kMaxBatch; b++) h->ring_watch[b] = 0;
       if (hipHostMalloc((void**)&h->coop_flag, sizeof(int), hipHostMallocMapped) != hipSuccess) { h->coop_flag = nullptr; set_err("hipHostMalloc failed"); return VLOAM_ERR_HIP; }
       *h->coop_flag = 0;
       h->lo_F.host_degraded = h->coop_flag; h->map.F[0].host_degraded = h->coop_flag; h->map.F[1].host_degraded = h->coop_flag;
@@ -545,11 +559,13 @@ static vloam_status enqueue_sr(vloam_handle* h, const BatchIn& bi) {
   if (h->cfg.timing) HIPCHK(hipEventRecord(h->ev[0], h->stream));
   // the full grid of the big ring tier only while long rings are around (watch word of an earlier sweep: plain read of host-mapped memory);
   // whatever the host knows or does not know, ONE catch-all workgroup of the big tier follows the small tier on every sweep, so any ring of up
-  // to kMaxRingLen points is processed (sr_launch)
-  bool big_tier = false;
+  // to kMaxRingLen points is processed (sr_launch); the same for the long tier and rings of up to max_ring_points on handles that have it
+  bool big_tier = false, long_tier = false;
   for (int b = 0; b < h->se.B; b++) big_tier = big_tier || __atomic_load_n(&h->ring_watch[b], __ATOMIC_RELAXED) != 0;
+  if (h->cfg.max_ring_points > kMaxRingLen)
+    for (int b = 0; b < h->se.B; b++) long_tier = long_tier || __atomic_load_n(&h->ring_watch[kMaxBatch + b], __ATOMIC_RELAXED) != 0;
   HIPCHK(sr_launch(h->stream, h->sr[cur], bi, h->se, h->cfg.scan_line, (float)h->cfg.minimum_range, h->cfg.debug, &h->prof,
-                   h->ev_sr[cur], h->ring_watch, big_tier));  // the odometry of THIS sweep needs the feature clouds only (its NN grids were built with the previous sweep)
+                   h->ev_sr[cur], h->ring_watch, big_tier, long_tier));  // the odometry of THIS sweep needs the feature clouds only (its NN grids were built with the previous sweep)
   // == kdtreeCornerLast / kdtreeSurfLast->setInputCloud (laser_odometry.cpp:525-526): index this sweep's clouds for the next one
   // (the next sweep's ev_sr is recorded behind this on the same stream, so its odometry sees the finished grids)
   lo_grid_build_launch(h->stream, h->se, h->sr[cur].less_sharp, h->sr[cur].less_flat, h->sr[cur].S, h->grid[cur], &h->prof);
@@ -755,7 +771,7 @@ static vloam_status read_sr_error(vloam_handle* h, int cur) {
   { vloam_status s_ = sync_all(h); if (s_ != VLOAM_OK) return s_; }
   HIPCHK(hipMemcpy(&err, &SEL(h, h->sr[cur].S)->error, sizeof(int), hipMemcpyDeviceToHost));
   if (err & kErrEmpty) { set_err("no point survived NaN / minimum_range removal"); return VLOAM_ERR_EMPTY; }
-  if (err & kErrRingTooLong) { set_err("a ring holds more than %d points", kMaxRingLen); return VLOAM_ERR_CAPACITY; }
+  if (err & kErrRingTooLong) { set_err("a ring holds more than %d points", h->cfg.max_ring_points); return VLOAM_ERR_CAPACITY; }
   return VLOAM_OK;
 }
 
@@ -1441,7 +1457,7 @@ vloam_status vloam_sync(vloam_handle* h) {
     }
     h->fallback_solves = fb;
     if (merr & kErrEmpty) { set_err("no point survived NaN / minimum_range removal in at least one sweep since the last vloam_sync"); return VLOAM_ERR_EMPTY; }
-    if (merr & kErrRingTooLong) { set_err("a ring held more than %d points (dropped) in at least one sweep since the last vloam_sync", kMaxRingLen); return VLOAM_ERR_CAPACITY; }
+    if (merr & kErrRingTooLong) { set_err("a ring held more than %d points (dropped) in at least one sweep since the last vloam_sync", h->cfg.max_ring_points); return VLOAM_ERR_CAPACITY; }
     if (merr & kErrMapFull) { set_err("voxel hash full (map_capacity_log2=%d)", h->cfg.map_capacity_log2); return VLOAM_ERR_CAPACITY; }
     if (merr & kErrStackFull) { set_err("mapping factor table full"); return VLOAM_ERR_CAPACITY; }
     if (merr & kErrMapDeferred) { set_err("raw-point capacity of the map exceeded (more than 255 un-merged points in a voxel of a cube outside the valid block, or more than 64 raw voxels around one query)"); return VLOAM_ERR_CAPACITY; }

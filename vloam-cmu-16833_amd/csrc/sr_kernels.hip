@@ -13,6 +13,8 @@
 //                                at once + boundary fixed point), lessFlat + VoxelGrid(0.2) over voxel runs  SR:288-439
 //                                (two capacity tiers: 2 176 points in 78.75 KB of LDS = two rings per CU; the 4 096-point tier follows on every
 //                                sweep — its full grid while long rings are around, one catch-all workgroup otherwise)
+//   k_sr_ring_long   1 WG/ring   opt-in third tier (vloam_config::max_ring_points > 4 096): rings of 4 097 .. max_ring_points points,
+//                                working arrays in HBM, sectors walked in order; launched like the big tier, behind it
 //   k_sr_compact     1 WG/ring   ring/sector-ordered feature clouds (+ per-ring bounding boxes of the less-clouds for the mapping
 //                                stage's VoxelGrid)                                                 SR:338-344,388,439
 #include <hip/hip_runtime.h>
@@ -433,6 +435,7 @@ __device__ void sr_spread(int ind, const float* px, const float* py, const float
 // the kMaxRingLen tier (146 KB, one workgroup per CU) is launched right behind it and only works on rings the small tier had to
 // leave alone (len > kRingCapSmall).
 constexpr int kRingCapSmall = 2176, kSectCapSmall = 512, kRingWatch = 2144;   // an HDL-64E revolution at 10 Hz has <= 2 083 firings per laser
+constexpr int kLongWatch = kMaxRingLen - 32;   // the big tier's warning to the long tier (the same margin)
 template <int CAP, int SECT>
 constexpr size_t sr_ring_keys_bytes() { return sizeof(u64) * kSectors * SECT > (size_t)12 * CAP ? sizeof(u64) * kSectors * SECT : (size_t)12 * CAP; }
 
@@ -442,7 +445,7 @@ __global__ __launch_bounds__(kRingThreads) void k_sr_ring(const float4* __restri
                                                           float4* __restrict__ ring_ds, float* __restrict__ dbg_curv,
                                                           int* __restrict__ dbg_sort, int* __restrict__ dbg_picked,
                                                           int* __restrict__ dbg_label, long long* __restrict__ dbg_cyc /* [rings][8] */,
-                                                          int* ring_watch /* host-mapped [sessions] */, int big_follows, size_t ss) {
+                                                          int* ring_watch /* host-mapped [2][kMaxBatch] */, int tier_follows, size_t ss) {
   VL_SESSION(ss); RB(cloud); RB(S); RB(sharp_idx); RB(less_sharp_idx); RB(flat_idx); RB(ring_ds); RB(dbg_curv); RB(dbg_sort); RB(dbg_picked);
   RB(dbg_label); RB(dbg_cyc);
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -484,8 +487,12 @@ __global__ __launch_bounds__(kRingThreads) void k_sr_ring(const float4* __restri
   // host-mapped word it polls without synchronising) or during the first sweeps; otherwise a single catch-all workgroup per session
   // follows the small tier, so that a ring which outgrows the small tier without that warning is still processed (slowly: the rings
   // one after the other, until the host has seen the watch word).
+  // The same between the big tier and the long tier (k_sr_ring_long, long-tier handles only): the big tier raises the second watch word
+  // (ring_watch[kMaxBatch + session]) for rings near kMaxRingLen, which the host only reads on handles that have a long tier.
   if (!BIG_TIER && tid == 0 && len > kRingWatch && ring_watch) __hip_atomic_store(&ring_watch[blockIdx.z], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-  if (len > CAP) { if ((BIG_TIER || !big_follows) && tid == 0) atomicOr(&S->error, kErrRingTooLong); return; }   // small tier: left to the big tier
+  if (BIG_TIER && tid == 0 && len > kLongWatch && ring_watch) __hip_atomic_store(&ring_watch[kMaxBatch + blockIdx.z], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+  // tier_follows: the next tier is launched behind this one (small tier: the big tier; big tier: the long tier) and takes what does not fit
+  if (len > CAP) { if (!tier_follows && tid == 0) atomicOr(&S->error, kErrRingTooLong); return; }
   if (end - start < 6) return;  // SR:314
 
   for (int l = tid; l < len; l += kRingThreads) {
@@ -1041,14 +1048,279 @@ __global__ __launch_bounds__(kRingThreads) void k_sr_ring(const float4* __restri
 }
 
 // ------------------------------------------------------------------------------------------------
+// The long ring tier (opt-in, vloam_config::max_ring_points > kMaxRingLen): rings of kMaxRingLen + 1 .. max_ring_points points, on handles that
+// asked for them.  Such a ring does not fit the LDS of a CU (~36 B per point in the tiers above, 590 KB at 16 384 points), so this tier keeps
+// its per-point arrays in HBM (SRBuffers::long_*, one region per ring and session; the points themselves are read from the ring-major cloud)
+// and only the reduction slots in LDS.  It is written for global memory rather than as a third instantiation of the LDS body: that body's
+// sector walks keep a sector in registers (211 VGPRs at the big tier's 682-point sectors; a 16 384-point ring has 2 729-point sectors) and its
+// run keys carry 12-bit point indices.  Here, as in the reference:
+//  - the six sectors are walked one after the other by wavefront 0, so a pick's neighbour suppression reaches into the next sector exactly as
+//    cloudNeighborPicked does (SR:353-376) and no boundary fixed point is needed.  A pick is the arg-max (sharp walk) / arg-min (flat walk)
+//    of (curvature, index) over the sector's eligible points, i.e. the first eligible entry of the sector sorted by (curvature, index),
+//    walked from the top or the bottom (the canonical order of the LDS tiers and of the oracle);
+//  - lessFlat's VoxelGrid(0.2) sorts one key per point (voxel : index, non-candidates last), so it takes any number of voxels, and sums every
+//    voxel's points in input order (CentroidPoint, f32).
+// Memory ordering: everything exchanged through these arrays stays inside the workgroup, i.e. on one CU behind one L1: between wavefronts
+// behind __syncthreads() (workgroup-scope release / acquire), between the lanes of wavefront 0 behind lds_fence_wave() — a workgroup-scope
+// fence over every address space (it waits for the wavefront's stores) and a wave barrier.  No other workgroup reads them during the launch;
+// the next launch that does (k_sr_compact: long_ds) is ordered behind this one on the stream.
+constexpr int kLongSlots = ((kMaxRingLenLong - 11 + kSectors - 1) / kSectors + 63) / 64;   // register slots per lane of a sector walk (2 729 points at 16 384)
+
+__global__ __launch_bounds__(kRingThreads) void k_sr_ring_long(const float4* __restrict__ cloud, FrameScalars* S, int* __restrict__ sharp_idx,
+                                                               int* __restrict__ less_sharp_idx, int* __restrict__ flat_idx, int cap, int kcap,
+                                                               u64* keys_all, int* iscr_all, unsigned char* bytes_all, float4* ds_all,
+                                                               float* __restrict__ dbg_curv, int* __restrict__ dbg_sort, int* __restrict__ dbg_picked,
+                                                               int* __restrict__ dbg_label, size_t ss) {
+  VL_SESSION(ss); RB(cloud); RB(S); RB(sharp_idx); RB(less_sharp_idx); RB(flat_idx); RB(keys_all); RB(iscr_all); RB(bytes_all); RB(ds_all);
+  RB(dbg_curv); RB(dbg_sort); RB(dbg_picked); RB(dbg_label);
+  __shared__ int scan_tmp[kRingThreads];
+  __shared__ float wred[kRingThreads / 64 * 8];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  auto one_ring = [&](const int r) {
+    const int len = S->ring_count[r], off = S->ring_off[r];
+    const int start = off + 5, end = off + len - 6;  // SR:278-280
+    if (len <= kMaxRingLen) return;                  // an LDS tier has done this ring
+    if (tid < kSectors * 3) (&S->sect_cnt[r][0][0])[tid] = 0;
+    if (tid == 0) S->ring_ds_cnt[r] = 0;
+    if (len > cap) { if (tid == 0) atomicOr(&S->error, kErrRingTooLong); return; }
+    if (end - start < 6) return;  // SR:314
+    const float4* p = cloud + off;
+    u64* keys = keys_all + (size_t)r * kcap;
+    int* iscr = iscr_all + (size_t)r * kcap;
+    float* curv = (float*)iscr;
+    unsigned char* picked = bytes_all + (size_t)r * 4 * cap;
+    signed char* label = (signed char*)(picked + cap);
+    unsigned char* gap = picked + 2 * cap;
+    unsigned char* reach = picked + 3 * cap;
+    float4* out = ds_all + (size_t)r * cap;
+
+    // gap[l] = 1 when dist2(p[l + 1], p[l]) > 0.05 (SR:353-376 stops there)
+    for (int l = tid; l < len; l += kRingThreads) {
+      picked[l] = 0; label[l] = 0;  // SR:305-306
+      bool g = true;
+      if (l + 1 < len) {
+        const float4 a = p[l], b = p[l + 1];
+        const float dx = b.x - a.x, dy = b.y - a.y, dz = b.z - a.z;
+        g = (double)(dx * dx + dy * dy + dz * dz) > 0.05;
+      }
+      gap[l] = g ? 1 : 0;
+    }
+    __syncthreads();
+    // curvature (SR:288-303) of every sector point and its suppression reach: how many of l-1 .. l-5 (low nibble) and of l+1 .. l+5 (high
+    // nibble) a pick at l marks
+    for (int l = 5 + tid; l <= len - 7; l += kRingThreads) {
+      float4 q[11];
+#pragma unroll
+      for (int k = 0; k < 11; k++) q[k] = p[l - 5 + k];
+      const float dX = q[0].x + q[1].x + q[2].x + q[3].x + q[4].x - 10 * q[5].x + q[6].x + q[7].x + q[8].x + q[9].x + q[10].x;
+      const float dY = q[0].y + q[1].y + q[2].y + q[3].y + q[4].y - 10 * q[5].y + q[6].y + q[7].y + q[8].y + q[9].y + q[10].y;
+      const float dZ = q[0].z + q[1].z + q[2].z + q[3].z + q[4].z - 10 * q[5].z + q[6].z + q[7].z + q[8].z + q[9].z + q[10].z;
+      const float c = dX * dX + dY * dY + dZ * dZ;
+      curv[l] = c;
+      if (dbg_curv) dbg_curv[off + l] = c;
+      int f = 0, k = 0;
+      while (f < 5 && !gap[l + f]) f++;
+      while (k < 5 && !gap[l - 1 - k]) k++;
+      reach[l] = (unsigned char)(k | (f << 4));
+    }
+    __syncthreads();
+    auto sect_lo = [&](int s) { return start + (end - start) * s / 6 - off; };            // SR:319, local
+    auto sect_hi = [&](int s) { return start + (end - start) * (s + 1) / 6 - 1 - off; };  // SR:320, local
+
+    // ---- debug only: the reference's std::sort of every sector (SR:323, ties by index), one sector after the other
+    if (dbg_sort) {
+      for (int s = 0; s < kSectors; s++) {
+        const int sp_l = sect_lo(s), seclen = sect_hi(s) - sp_l + 1;
+        int P = 256;
+        while (P < seclen) P <<= 1;
+        for (int t = tid; t < P; t += kRingThreads)
+          keys[t] = t < seclen ? ((u64)__float_as_uint(curv[sp_l + t]) << 32) | (unsigned)(sp_l + t) : ~0ull;   // c >= 0: bits order like the value
+        __syncthreads();
+        block_bitonic_sort_u64(keys, P, tid, kRingThreads);
+        for (int t = tid; t < seclen; t += kRingThreads) dbg_sort[off + sp_l + t] = off + (int)(keys[t] & 0xffffffffu);
+        __syncthreads();
+      }
+    }
+
+    // ---- greedy picks (SR:325-422), wavefront 0, sector after sector
+    if (wave == 0) {
+      for (int s = 0; s < kSectors; s++) {
+        const int sp_l = sect_lo(s), ep_l = sect_hi(s);
+        int* o_sharp = sharp_idx + (r * kSectors + s) * kMaxSharpPerSect;
+        int* o_less = less_sharp_idx + (r * kSectors + s) * kMaxLessSharpPerSect;
+        int* o_flat = flat_idx + (r * kSectors + s) * kMaxFlatPerSect;
+        unsigned v[kLongSlots];   // point sp_l + q * 64 + lane: its curvature bits while it is a candidate of the running walk, else the walk's neutral value
+        // the candidates of a walk: points no earlier pick has marked — of this sector or, over the seam, of the previous one
+        auto load = [&](bool sharp_walk) {
+          lds_fence_wave();   // this wavefront's marks are stored before they are read back
+#pragma unroll
+          for (int q = 0; q < kLongSlots; q++) {
+            const int i = sp_l + q * 64 + lane;
+            v[q] = sharp_walk ? 0u : 0xffffffffu;
+            if (i <= ep_l && !picked[i]) {
+              // SR:330 / SR:383: (double)c > 0.1 <=> c >= 0.1f, (double)c < 0.1 <=> c < 0.1f (0.1 lies between two neighbouring floats)
+              const float c = curv[i];
+              if (sharp_walk ? c >= 0.1f : c < 0.1f) v[q] = __float_as_uint(c);   // c >= 0: the bits order like the value
+            }
+          }
+        };
+        // SR:345-376 around the winner: cloudNeighborPicked in memory (one lane per marked point), and the marked points leave the walk
+        auto mark = [&](int w, unsigned neutral) {
+          const unsigned rb = reach[w];
+          const int lo_m = w - (int)(rb & 15u), hi_m = w + (int)(rb >> 4);
+          if (lane <= hi_m - lo_m) picked[lo_m + lane] = 1;
+#pragma unroll
+          for (int q = 0; q < kLongSlots; q++) {
+            const int i = sp_l + q * 64 + lane;
+            if (i >= lo_m && i <= hi_m) v[q] = neutral;
+          }
+        };
+        // SR:327-378, descending (curvature, index)
+        load(true);
+        int n_less = 0;
+        while (n_less < kMaxLessSharpPerSect) {
+          unsigned lb = v[0];
+          int qb = 0;
+#pragma unroll
+          for (int q = 1; q < kLongSlots; q++) if (v[q] >= lb) { lb = v[q]; qb = q; }   // ties: the higher index
+          const unsigned hi = wave_max_u32(lb);
+          if (hi == 0) break;   // (candidates have c >= 0.1f: non-zero bits)
+          const int w = (int)wave_max_u32(lb == hi ? (unsigned)(sp_l + qb * 64 + lane) : 0u);
+          if (lane == 0) {
+            label[w] = n_less < kMaxSharpPerSect ? 2 : 1;
+            o_less[n_less] = off + w;
+            if (n_less < kMaxSharpPerSect) o_sharp[n_less] = off + w;
+          }
+          n_less++;
+          mark(w, 0u);
+        }
+        // SR:380-422, ascending (curvature, index)
+        load(false);
+        int n_flat = 0;
+        while (n_flat < kMaxFlatPerSect) {
+          unsigned lb = v[0];
+          int qb = 0;
+#pragma unroll
+          for (int q = 1; q < kLongSlots; q++) if (v[q] < lb) { lb = v[q]; qb = q; }   // ties: the lower index
+          const unsigned hi = wave_min_u32(lb);
+          if (hi == 0xffffffffu) break;   // (c < 0.1f: never all ones)
+          const int w = (int)wave_min_u32(lb == hi ? (unsigned)(sp_l + qb * 64 + lane) : 0xffffffffu);
+          if (lane == 0) { label[w] = -1; o_flat[n_flat] = off + w; }
+          n_flat++;
+          if (n_flat >= kMaxFlatPerSect) break;  // the 4th flat point is emitted but not suppressed (SR:390-394)
+          mark(w, 0xffffffffu);
+        }
+        if (lane == 0) { S->sect_cnt[r][s][0] = min(n_less, kMaxSharpPerSect); S->sect_cnt[r][s][1] = n_less; S->sect_cnt[r][s][2] = n_flat; }
+      }
+    }
+    __syncthreads();
+    if (dbg_picked) for (int l = tid; l < len; l += kRingThreads) { dbg_picked[off + l] = picked[l]; dbg_label[off + l] = label[l]; }
+
+    // ---- lessFlat (SR:424-430) + per-ring pcl::VoxelGrid leaf 0.2 (SR:433-437), as in k_sr_ring
+    const int c_lo = 5, c_hi = len - 7;  // local range covered by the six sectors: [start, end-1]
+    float mn[3] = {3.4e38f, 3.4e38f, 3.4e38f}, mx[3] = {-3.4e38f, -3.4e38f, -3.4e38f};
+    int mycnt = 0;
+    for (int l = c_lo + tid; l <= c_hi; l += kRingThreads)
+      if (label[l] <= 0) {
+        const float4 q = p[l];
+        mn[0] = fminf(mn[0], q.x); mx[0] = fmaxf(mx[0], q.x);
+        mn[1] = fminf(mn[1], q.y); mx[1] = fmaxf(mx[1], q.y);
+        mn[2] = fminf(mn[2], q.z); mx[2] = fmaxf(mx[2], q.z);
+        mycnt++;
+      }
+    for (int a = 0; a < 3; a++) { mn[a] = wave_fminmax<false>(mn[a]); mx[a] = wave_fminmax<true>(mx[a]); }
+    mycnt = wave_sum_i32(mycnt);
+    if (lane == 0) {
+      for (int a = 0; a < 3; a++) { wred[wave * 8 + a] = mn[a]; wred[wave * 8 + 3 + a] = mx[a]; }
+      ((int*)wred)[wave * 8 + 6] = mycnt;
+    }
+    __syncthreads();
+    int ncand = 0;
+    for (int a = 0; a < 3; a++) { mn[a] = wred[a]; mx[a] = wred[3 + a]; }
+    for (int w = 0; w < kRingThreads / 64; w++) {
+      for (int a = 0; a < 3; a++) { mn[a] = fminf(mn[a], wred[w * 8 + a]); mx[a] = fmaxf(mx[a], wred[w * 8 + 3 + a]); }
+      ncand += ((int*)wred)[w * 8 + 6];
+    }
+    if (ncand == 0) return;
+    const float inv = 1.0f / 0.2f;  // inverse_leaf_size_
+    const long long dx = (long long)((mx[0] - mn[0]) * inv) + 1, dy = (long long)((mx[1] - mn[1]) * inv) + 1, dz = (long long)((mx[2] - mn[2]) * inv) + 1;
+    if (dx * dy * dz > (long long)INT_MAX) {
+      // PCL: "Leaf size is too small for the input dataset" -> output = input.  Keep input order.
+      for (int l = tid; l < len; l += kRingThreads) iscr[l] = (l >= c_lo && l <= c_hi && label[l] <= 0) ? 1 : 0;
+      __syncthreads();
+      block_exclusive_scan(iscr, len, scan_tmp);
+      for (int l = c_lo + tid; l <= c_hi; l += kRingThreads)
+        if (label[l] <= 0) out[iscr[l]] = p[l];
+      if (tid == 0) S->ring_ds_cnt[r] = ncand;
+      return;
+    }
+    int min_b[3], div_b[3];
+    for (int a = 0; a < 3; a++) {
+      min_b[a] = (int)floorf(mn[a] * inv);
+      div_b[a] = (int)floorf(mx[a] * inv) - min_b[a] + 1;
+    }
+    // key = voxel index : point, ~0 for a point that is no candidate (sorted behind the ncand candidates)
+    int P2 = 256;
+    while (P2 < len) P2 <<= 1;   // <= kcap
+    for (int l = tid; l < P2; l += kRingThreads) {
+      u64 key = ~0ull;
+      if (l >= c_lo && l <= c_hi && label[l] <= 0) {
+        const float4 q = p[l];
+        const int ijk0 = (int)(floorf(q.x * inv) - (float)min_b[0]);
+        const int ijk1 = (int)(floorf(q.y * inv) - (float)min_b[1]);
+        const int ijk2 = (int)(floorf(q.z * inv) - (float)min_b[2]);
+        key = ((u64)(unsigned)(ijk0 + ijk1 * div_b[0] + ijk2 * div_b[0] * div_b[1]) << 32) | (unsigned)l;
+      }
+      keys[l] = key;
+    }
+    __syncthreads();
+    block_bitonic_sort_u64(keys, P2, tid, kRingThreads);
+    // voxel heads -> output rank, then one lane per voxel sums its points in input order
+    for (int t = tid; t < ncand; t += kRingThreads) iscr[t] = (t == 0 || (keys[t] >> 32) != (keys[t - 1] >> 32)) ? 1 : 0;
+    __syncthreads();
+    const int nvox = block_exclusive_scan(iscr, ncand, scan_tmp);
+    for (int t = tid; t < ncand; t += kRingThreads) {
+      const unsigned vid = (unsigned)(keys[t] >> 32);
+      if (t > 0 && (unsigned)(keys[t - 1] >> 32) == vid) continue;
+      float sx = 0.f, sy = 0.f, sz = 0.f, si = 0.f;  // CentroidPoint<PointXYZI>: f32 sums in input order
+      int npt = 0;
+      for (int u = t; u < ncand; u++) {
+        const u64 k = keys[u];
+        if ((unsigned)(k >> 32) != vid) break;
+        const float4 q = p[(int)(k & 0xffffffffu)];
+        sx += q.x; sy += q.y; sz += q.z; si += q.w;
+        npt++;
+      }
+      const float cnt = (float)npt;
+      out[iscr[t]] = make_float4(sx / cnt, sy / cnt, sz / cnt, si / cnt);
+    }
+    if (tid == 0) S->ring_ds_cnt[r] = nvox;
+  };
+  // one workgroup per ring — or the catch-all: ONE workgroup per session walks the long rings (normally none: the launch ends here)
+  static_assert(kMaxRings == 64, "one ring per lane");
+  if (gridDim.x == kMaxRings) {
+    one_ring((int)blockIdx.x);
+  } else {
+    unsigned long long todo = __ballot(S->ring_count[lane] > kMaxRingLen);
+    while (todo != 0ull) {
+      const int r = __ffsll((long long)todo) - 1;
+      todo &= todo - 1ull;
+      one_ring(r);
+      __syncthreads();   // the reduction slots are no longer read
+    }
+  }
+}
+
+// ------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void k_sr_compact(const float4* __restrict__ cloud, FrameScalars* S, const int* __restrict__ sharp_idx,
                                                     const int* __restrict__ less_sharp_idx, const int* __restrict__ flat_idx,
                                                     const float4* __restrict__ ring_ds, float4* __restrict__ sharp,
                                                     float4* __restrict__ less_sharp, float4* __restrict__ flat,
                                                     float4* __restrict__ less_flat, int* __restrict__ dbg_feat_idx /* [3][kMaxLessSharp] */,
-                                                    int* sticky_err, size_t ss) {
+                                                    int* sticky_err, const float4* __restrict__ long_ds /* [kMaxRings][long_cap] or null */,
+                                                    int long_cap, size_t ss) {
   VL_SESSION(ss); RB(cloud); RB(S); RB(sharp_idx); RB(less_sharp_idx); RB(flat_idx); RB(ring_ds); RB(sharp); RB(less_sharp); RB(flat); RB(less_flat);
-  RB(dbg_feat_idx); RB(sticky_err);
+  RB(dbg_feat_idx); RB(sticky_err); RB(long_ds);
   __shared__ int base[4];
   __shared__ int soff[kSectors][3];
   __shared__ float s_box[4][12];
@@ -1110,7 +1382,8 @@ __global__ __launch_bounds__(256) void k_sr_compact(const float4* __restrict__ c
     }
   }
   const int nds = S->ring_ds_cnt[r];
-  const float4* src = ring_ds + (size_t)r * kMaxRingLen;
+  // a ring of more than kMaxRingLen points was downsampled by the long tier (long-tier handles only)
+  const float4* src = long_ds && S->ring_count[r] > kMaxRingLen ? long_ds + (size_t)r * long_cap : ring_ds + (size_t)r * kMaxRingLen;
   for (int k = tid; k < nds; k += 256) {
     const float4 p = src[k];
     less_flat[base[3] + k] = p;
@@ -1187,11 +1460,11 @@ hipError_t sr_init() {
                                      (int)sr_ring_smem_bytes<kRingCapSmall, kSectCapSmall>());
   if (e != hipSuccess) return e;
   return hipFuncSetAttribute((const void*)k_sr_ring<kMaxRingLen, kSectCap, true>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                             (int)sr_ring_smem_bytes<kMaxRingLen, kSectCap>());
+                             (int)sr_ring_smem_bytes<kMaxRingLen, kSectCap>());   // (k_sr_ring_long: static LDS only)
 }
 
 hipError_t sr_launch(hipStream_t st, const SRBuffers& b, const BatchIn& bi, Sess se, int N_SCANS, float min_range, int debug_level, ProfHook* ph, hipEvent_t done,
-                     int* ring_watch, bool big_tier) {
+                     int* ring_watch, bool big_tier, bool long_tier) {
   const bool debug = debug_level == 1, stamps = debug_level != 0;   // debug = 2: only the ring kernel's phase stamps (no reference-order debug sort)
   int n = 0;
   for (int k = 0; k < se.B; k++) n = bi.n[k] > n ? bi.n[k] : n;   // launch geometry for the largest sweep of the batch (blocks beyond a session's n idle)
@@ -1220,8 +1493,14 @@ hipError_t sr_launch(hipStream_t st, const SRBuffers& b, const BatchIn& bi, Sess
   // VLOAM_SR_CATCHALL=0: a host that KNOWS its rings stay below kRingCapSmall points (any 10 Hz sensor of the reference's three scan_line
   // settings) may drop the catch-all launch: a ring that outgrows the small tier without the watch word's warning is then REPORTED
   // (kErrRingTooLong -> VLOAM_ERR_CAPACITY) instead of processed; with the warning the full big tier runs as always.
+  // The long tier (handles with max_ring_points > kMaxRingLen only) follows the big tier the same way: its full grid while the big tier has
+  // seen rings near kMaxRingLen (second watch word), else its one-workgroup catch-all; VLOAM_SR_CATCHALL=0 drops that catch-all as well.
+  // Default handles launch neither.
   static const int catchall = getenv("VLOAM_SR_CATCHALL") ? atoi(getenv("VLOAM_SR_CATCHALL")) : 1;
-  const bool big_launch = big_tier || catchall != 0;
+  const bool has_long = b.long_cap > kMaxRingLen;
+  long_tier = long_tier && has_long;
+  const bool big_launch = big_tier || long_tier || catchall != 0;
+  const bool long_launch = has_long && (long_tier || catchall != 0);
   VLOAM_LAUNCH(ph, kKSrRing, st, (k_sr_ring<kRingCapSmall, kSectCapSmall, false>), dim3(kMaxRings, 1, Z), dim3(kRingThreads),
                (sr_ring_smem_bytes<kRingCapSmall, kSectCapSmall>()), st, b.cloud, b.S, b.sharp_idx, b.less_sharp_idx,
                b.flat_idx, b.ring_ds, debug ? b.dbg_curv : nullptr, debug ? b.dbg_sort : nullptr, debug ? b.dbg_picked : nullptr,
@@ -1231,9 +1510,14 @@ hipError_t sr_launch(hipStream_t st, const SRBuffers& b, const BatchIn& bi, Sess
     VLOAM_LAUNCH(ph, kKSrRingBig, st, (k_sr_ring<kMaxRingLen, kSectCap, true>), dim3(big_tier ? kMaxRings : 1, 1, Z), dim3(kRingThreads),
                  (sr_ring_smem_bytes<kMaxRingLen, kSectCap>()), st, b.cloud, b.S, b.sharp_idx, b.less_sharp_idx,
                  b.flat_idx, b.ring_ds, debug ? b.dbg_curv : nullptr, debug ? b.dbg_sort : nullptr, debug ? b.dbg_picked : nullptr,
-                 debug ? b.dbg_label : nullptr, stamps ? b.dbg_cyc : nullptr, ring_watch, 1, se.ss);
+                 debug ? b.dbg_label : nullptr, stamps ? b.dbg_cyc : nullptr, ring_watch, long_launch ? 1 : 0, se.ss);
+  if (long_launch)
+    VLOAM_LAUNCH(ph, kKSrRingLong, st, k_sr_ring_long, dim3(long_tier ? kMaxRings : 1, 1, Z), dim3(kRingThreads), 0, st, b.cloud, b.S, b.sharp_idx,
+                 b.less_sharp_idx, b.flat_idx, b.long_cap, b.long_kcap, b.long_keys, b.long_iscr, b.long_bytes, b.long_ds,
+                 debug ? b.dbg_curv : nullptr, debug ? b.dbg_sort : nullptr, debug ? b.dbg_picked : nullptr, debug ? b.dbg_label : nullptr, se.ss);
   VLOAM_LAUNCH_EV(ph, kKSrCompact, st, done, k_sr_compact, dim3(kMaxRings, 1, Z), dim3(256), 0, st, b.cloud, b.S, b.sharp_idx, b.less_sharp_idx, b.flat_idx, b.ring_ds,
-                     b.sharp, b.less_sharp, b.flat, b.less_flat, debug ? b.dbg_feat_idx : nullptr, b.sticky_err, se.ss);
+                     b.sharp, b.less_sharp, b.flat, b.less_flat, debug ? b.dbg_feat_idx : nullptr, b.sticky_err, has_long ? b.long_ds : nullptr,
+                     b.long_cap, se.ss);
   return hipGetLastError();
 }
 

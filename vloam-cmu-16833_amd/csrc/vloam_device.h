@@ -47,7 +47,8 @@ struct Arena {
 
 constexpr int kMaxRings = 64;        // N_SCANS upper bound (scan_registration.cpp:195-226)
 constexpr int kSectors = 6;          // scan_registration.cpp:317
-constexpr int kMaxRingLen = 4096;    // points of one ring kept in LDS by k_sr_ring (HDL-64E: <= ~2100)
+constexpr int kMaxRingLen = 4096;    // points of one ring kept in LDS by k_sr_ring (HDL-64E: <= ~2100); the ring capacity of a default handle
+constexpr int kMaxRingLenLong = 16384;  // upper bound of vloam_config::max_ring_points: rings beyond kMaxRingLen go to k_sr_ring_long (HBM-resident)
 constexpr int kSectCap = 1024;       // padded sector length for the LDS bitonic sort
 constexpr int kLabelBlock = 1024;    // points per workgroup in the label / scatter kernels
 constexpr int kMaxSharpPerSect = 2, kMaxLessSharpPerSect = 20, kMaxFlatPerSect = 4;  // scan_registration.cpp:335-345,391
@@ -61,13 +62,14 @@ enum KernelId : int {
   kKNone = 0, kKSrFirstLast, kKSrLabel, kKSrScan, kKSrScatter, kKSrRing, kKSrCompact, kKLoAssoc, kKLmSolve, kKLoFinish,
   kKMapPrepare, kKMapStack, kKMapAssoc, kKMapInsert, kKMapFinalize, kKVoProject, kKVoMatch,
   kKLoGridCount, kKLoGridScan, kKLoGridScatter, kKMapDsReduce, kKMapFit, kKLmCompact, kKVoFold, kKSrRingBig,
-  kKImgSobel, kKImgEig, kKImgLocalMax, kKImgNeighbours, kKImgSelect, kKImgPyrDown, kKImgScharr, kKImgLk, kKLoAssocFast, kKCount
+  kKImgSobel, kKImgEig, kKImgLocalMax, kKImgNeighbours, kKImgSelect, kKImgPyrDown, kKImgScharr, kKImgLk, kKLoAssocFast, kKSrRingLong, kKCount
 };
 static const char* const kKernelNames[kKCount] = {"", "k_sr_first_last", "k_sr_label", "k_sr_scan", "k_sr_scatter", "k_sr_ring",
   "k_sr_compact", "k_lo_assoc", "k_lm_solve", "k_lo_finish", "k_map_prepare", "k_map_ds_bin", "k_map_assoc", "k_map_insert",
   "k_map_finalize", "k_vo_project", "k_vo_match", "k_lo_grid_count", "k_lo_grid_scan", "k_lo_grid_scatter",
   "k_map_ds_reduce", "k_map_fit", "k_lm_compact", "k_vo_fold", "k_sr_ring_big_tier",
-  "k_img_sobel", "k_img_eig", "k_img_localmax", "k_img_neighbours", "k_img_select", "k_img_pyrdown", "k_img_scharr", "k_img_lk", "k_lo_assoc_fast"};
+  "k_img_sobel", "k_img_eig", "k_img_localmax", "k_img_neighbours", "k_img_select", "k_img_pyrdown", "k_img_scharr", "k_img_lk", "k_lo_assoc_fast",
+  "k_sr_ring_long"};
 constexpr int kKAll = -1;  // ProfHook::id: bracket every launch, whichever kernel
 
 // Records a HIP-event pair around every launch of one selected kernel (or of all kernels), on the stream it is launched on.
@@ -126,7 +128,7 @@ extern int g_vl_plain_events;   // VLOAM_PLAIN_EVENTS=1 (A/B switch): a marker p
 
 enum ErrorBits : int {
   kErrEmpty = 1,       // no point survived S1
-  kErrRingTooLong = 2, // a ring exceeded kMaxRingLen
+  kErrRingTooLong = 2, // a ring exceeded the handle's ring capacity (kMaxRingLen, or vloam_config::max_ring_points on a long-tier handle)
   kErrMapFull = 4,     // voxel hash out of slots
   kErrMapDeferred = 8, // raw-point capacity: more than 255 un-merged points in one voxel of a cube outside the valid block, or more than 64 raw voxels around one query
   kErrStackFull = 16,

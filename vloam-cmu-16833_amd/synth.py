@@ -9,6 +9,11 @@ kept (exercises ``removeClosedPointCloud``, scan_registration.cpp:100-129).
 Beam table: ring r -> elevation 1.9 - r/3 deg (r <= 31), -8.93 - (r-32)/2 deg (r >= 32), i.e. the
 HDL-64E table shifted 0.1 deg down so the reference's ``int((2-angle)*3+0.5)`` /
 ``32+int((-8.83-angle)*2+0.5)`` mapping (scan_registration.cpp:213-226) lands mid-bin.
+
+``sensor="hdl64e"`` (opt-in): an HDL-64E S2-like head instead — two blocks of 32 lasers whose rays start 0.1 m above / below the
+sensor origin, elevations drawn around the data-sheet table (hdl64e_beams), 2 083 firings per revolution.  The reference bins returns
+by atan(z / r) of the POINT, so the block offsets and the per-laser calibration put two lasers into one scan line now and then: scan
+lines of more than 4 096 points (vloam_config::max_ring_points).
 """
 import numpy as np
 
@@ -25,6 +30,20 @@ def beam_elevations_deg(n_rings):
     if n_rings == 32:  # HDL-32: scanID = int((angle + 92/3) * 3/4)      (scan_registration.cpp:204-212)
         return -92.0 / 3.0 + (r + 0.5) * 4.0 / 3.0
     raise ValueError("n_rings must be 16, 32 or 64")
+
+
+HDL64E_FIRINGS = 2083       # firings per laser and revolution at 10 Hz
+HDL64E_SEED = 1              # calibration draw of the default hdl64e head: scan lines 27 and 38 receive two lasers each (4 166 points)
+
+
+def hdl64e_beams(seed=HDL64E_SEED):
+    """(elevation [deg], ray origin z offset [m]) of the 64 lasers of an HDL-64E S2-like head: upper block 2.0 deg downwards in 1/3 deg
+    steps, lower block -8.83 deg downwards in 1/2 deg steps, every elevation drawn within +-0.15 deg of its nominal value; the upper block's
+    rays start 0.1 m above the sensor origin, the lower block's 0.1 m below."""
+    i = np.arange(32, dtype=np.float64)
+    nominal = np.concatenate([2.0 - i / 3.0, -8.83 - i / 2.0])
+    el = nominal + np.random.default_rng(seed).uniform(-0.15, 0.15, 64)
+    return el, np.where(np.arange(64) < 32, 0.1, -0.1)
 
 
 def _rot_zyx(yaw, pitch, roll):
@@ -63,11 +82,25 @@ def quat_to_rot(q):
 
 
 class SynthSequence:
-    def __init__(self, n_rings=64, n_azimuth=2048, n_sweeps=200, seed_scene=1234, seed_traj=42, seed_noise=5678,
-                 noise_sigma=0.02, speed=10.0, dt=0.1, pitch_amp=0.01, roll_amp=0.01, heave_amp=0.05):
+    def __init__(self, n_rings=64, n_azimuth=None, n_sweeps=200, seed_scene=1234, seed_traj=42, seed_noise=5678,
+                 noise_sigma=0.02, speed=10.0, dt=0.1, pitch_amp=0.01, roll_amp=0.01, heave_amp=0.05, sensor="default", sensor_seed=HDL64E_SEED):
+        """sensor: "default" (beam_elevations_deg, one origin, n_azimuth 2048 unless given) or "hdl64e" (hdl64e_beams(sensor_seed), 64 lasers,
+        n_azimuth HDL64E_FIRINGS unless given)."""
+        if sensor not in ("default", "hdl64e"):
+            raise ValueError("sensor must be 'default' or 'hdl64e'")
+        if sensor == "hdl64e" and n_rings != 64:
+            raise ValueError("the hdl64e sensor has 64 lasers")
+        if n_azimuth is None:
+            n_azimuth = HDL64E_FIRINGS if sensor == "hdl64e" else 2048
         self.n_rings, self.n_azimuth, self.n_sweeps = n_rings, n_azimuth, n_sweeps
         self.seed_noise, self.noise_sigma = seed_noise, noise_sigma
-        el = np.deg2rad(beam_elevations_deg(n_rings))
+        self.sensor = sensor
+        self.beam_dz = None   # per-laser ray origin offset along the sensor z axis [m] (hdl64e only)
+        if sensor == "hdl64e":
+            el_deg, self.beam_dz = hdl64e_beams(sensor_seed)
+            el = np.deg2rad(el_deg)
+        else:
+            el = np.deg2rad(beam_elevations_deg(n_rings))
         # clockwise so ori = -atan2(y, x) increases.  A fixed per-column jitter keeps the firing azimuths off a perfect grid: on a
         # perfect grid whole columns sit EXACTLY on the reference's +-pi/2 unwrap thresholds (scan_registration.cpp:237-261),
         # where a 1-ulp difference between two atan2f implementations flips relTime — and with it int(intensity) — by a turn.
@@ -174,10 +207,12 @@ class SynthSequence:
         R, o = self.pose(k)
         nr, na = self.n_rings, self.n_azimuth
         d = (self.dirs @ R.T).reshape(nr, na, 3)  # world directions, [ring][column]
+        # ray origins: the sensor origin, or per laser (hdl64e) — [1 | ring][1][3]
+        O = o[None, None, :] if self.beam_dz is None else o[None, None, :] + (self.beam_dz[:, None] * R[:, 2][None, :])[:, None, :]
         best = np.full((nr, na), np.inf)
         # ground
         with np.errstate(divide="ignore", invalid="ignore"):
-            tg = (GROUND_Z - o[2]) / d[:, :, 2]
+            tg = (GROUND_Z - O[:, :, 2]) / d[:, :, 2]
         tg = np.where((d[:, :, 2] < 0) & (tg > 0), tg, np.inf)
         best = np.minimum(best, tg)
         with np.errstate(divide="ignore", invalid="ignore"):
@@ -197,8 +232,8 @@ class SynthSequence:
             corners = np.array([[b[i], b[j], b[kk]] for i in (0, 3) for j in (1, 4) for kk in (2, 5)])
             j0, j1 = self._az_window(corners, R, o)
             for sl in cols(j0, j1):
-                t1 = (b[None, None, 0:3] - o[None, None, :]) * inv[:, sl]
-                t2 = (b[None, None, 3:6] - o[None, None, :]) * inv[:, sl]
+                t1 = (b[None, None, 0:3] - O) * inv[:, sl]
+                t2 = (b[None, None, 3:6] - O) * inv[:, sl]
                 tmin = np.nanmax(np.minimum(t1, t2), axis=2)
                 tmax = np.nanmin(np.maximum(t1, t2), axis=2)
                 hit = (tmax >= tmin) & (tmin > 0)
@@ -210,7 +245,7 @@ class SynthSequence:
         for c in cy[near]:
             corners = np.array([[c[0] + sx * c[2], c[1] + sy * c[2], z] for sx in (-1, 1) for sy in (-1, 1) for z in (c[3], c[4])])
             j0, j1 = self._az_window(corners, R, o)
-            ox, oy = o[0] - c[0], o[1] - c[1]
+            ox, oy = O[:, :, 0] - c[0], O[:, :, 1] - c[1]
             for sl in cols(j0, j1):
                 dd = d[:, sl]
                 a = dd[:, :, 0] ** 2 + dd[:, :, 1] ** 2
@@ -219,7 +254,7 @@ class SynthSequence:
                 disc = bq * bq - 4 * a * cq
                 with np.errstate(invalid="ignore", divide="ignore"):
                     tc = (-bq - np.sqrt(disc)) / (2 * a)
-                zc = o[2] + tc * dd[:, :, 2]
+                zc = O[:, :, 2] + tc * dd[:, :, 2]
                 hit = (disc > 0) & (tc > 0) & (zc >= c[3]) & (zc <= c[4])
                 bs = best[:, sl]
                 best[:, sl] = np.where(hit & (tc < bs), tc, bs)
@@ -233,6 +268,8 @@ class SynthSequence:
         miss = ~np.isfinite(r) | (r > MAX_RANGE) | (r <= 0.05)
         with np.errstate(invalid="ignore"):
             pts = self.dirs * r[:, None]
+            if self.beam_dz is not None:   # offset + dir x range
+                pts[:, 2] += np.repeat(self.beam_dz, self.n_azimuth)
         out = np.zeros((pts.shape[0], 4), dtype=np.float32)
         out[:, :3] = pts.astype(np.float32)
         out[miss, :3] = np.nan
