@@ -142,8 +142,16 @@ vloam_status vloam_laser_odometry(vloam_handle* h, double q_w[4], double t_w[3],
  * SCAN_PERIOD * relTime as scan registration writes it (scan_registration.cpp:262-264); a NULL cloud keeps the device's.  The clouds replace
  * the sweep's own: this sweep's odometry, the next sweep's CornerLast / SurfLast (laser_odometry.cpp:506-526) and the mapping stage's input
  * all see them.  Capacity: 768 / 7 680 / 1 536 points for cornerPointsSharp / LessSharp / surfPointsFlat, max_points for the other two.
- * Stated limit: the two less-clouds must keep scan registration's ordering (scan lines ascending up to the r / r - 1 jitter of
- * int(intensity)); the adjacent-line walks of laser_odometry.cpp:294-324,371-428 are evaluated from per-line first / last indices.
+ * Enforced rule, checked on the host arrays before anything is uploaded (VLOAM_ERR_INVALID otherwise; vloam_last_error() names the cloud, the
+ * point index and the rule; the handle stays as it was, so vloam_laser_odometry then runs on scan registration's own clouds):
+ *   (i)   every float of all five clouds is finite;
+ *   (ii)  in cornerPointsLessSharp and surfPointsLessFlat, every L = int(intensity) lies in [0, 64);
+ *   (iii) in those two clouds, max_{i<j} L[i] - L[j] <= 2: no point comes after one whose line is 3 or more above its own.
+ * Why (iii): the adjacent-line walks of laser_odometry.cpp:294-324,371-428 start at the closest point's index and break at the first line
+ * outside r +- 2.5; the device bounds them by the first index of the cloud with a line >= r + 3 and the last with a line <= r - 3.  The two
+ * agree at every index exactly under (iii).  Scan registration's clouds keep it (lines ascending up to the r / r - 1 jitter of
+ * int(intensity)), and so does any filter that drops points, a shuffle inside a line, or a reorder of lines within windows of three.  The
+ * rule is conservative: some orders that break (iii) still walk the same way in the reference, and they are refused too.
  * Both stage-input calls are for single-sequence handles driven stage by stage (VLOAM_ERR_INVALID on n_sessions > 1: a batch is enqueued whole). */
 vloam_status vloam_set_odometry_input(vloam_handle* h, const float* laserCloud, int n_full, const float* cornerPointsSharp, int n_sharp,
                                       const float* cornerPointsLessSharp, int n_less_sharp, const float* surfPointsFlat, int n_flat,
@@ -156,7 +164,8 @@ vloam_status vloam_get_odometry_pose(vloam_handle* h, double q_w[4], double t_w[
 /* LaserMapping::input with clouds / an odometry pose that are NOT LaserOdometry::output's (laser_mapping.cpp:167-196 copies what it is handed; on a
  * sweep skipped by mapping_skip_frame only the pose).  Call between vloam_laser_odometry and vloam_laser_mapping; NULL keeps the device's.  Only
  * this sweep's mapping (and the /velodyne_cloud_registered product, vloam_get_features(11)) sees them — the odometry keeps its own
- * CornerLast / SurfLast, like the reference's separate copies.  Stated limit: q_wodom_curr must be a unit quaternion (as any
+ * CornerLast / SurfLast, like the reference's separate copies.  Enforced: every float of the three clouds is finite (VLOAM_ERR_INVALID
+ * otherwise, before anything is uploaded; mapping does not walk by scan line, so no line rule applies).  Stated limit: q_wodom_curr must be a unit quaternion (as any
  * Eigen::Quaterniond an odometry produces): the solver's closed-form Jacobians are those of a rotation, the reference's autodiff
  * differentiates Eigen's un-normalised q * v — with |q|^2 = 1 + 5e-6 the map poses part by 1e-9 (measured, tests/test_gpu_stage_inputs.py). */
 vloam_status vloam_set_mapping_input(vloam_handle* h, const float* laserCloudCornerLast, int n_corner, const float* laserCloudSurfLast, int n_surf,

@@ -24,12 +24,15 @@
 // What stays in HBM: the reference hands clouds from stage to stage by value (LaserOdometry::input deep-copies the five
 // scan-registration clouds, laser_odometry.cpp:141-145; LaserMapping::input copies three more, laser_mapping.cpp:167-181).
 // Here the stages read each other's results on the device, so input(...) does not upload anything when it is handed what the previous
-// stage produced (size + first / last point are compared).  A caller that edits or substitutes clouds between the stages gets the
-// reference's semantics all the same: the foreign clouds are uploaded with vloam_set_stage_clouds and the stage works on them.
+// stage produced (every point compared bit for bit).  A caller that edits or substitutes clouds between the stages gets the reference's
+// semantics all the same: the foreign clouds are uploaded with vloam_set_odometry_input / vloam_set_mapping_input and the stage works on
+// them, within the rule those calls enforce (c_api.h: finite values; the two less-clouds keep their scan lines in [0, 64), no line more
+// than 2 below an earlier one) — a cloud that breaks it throws std::runtime_error and the stage keeps the previous stage's clouds.
 // init(std::shared_ptr<TF>&) accepts (and ignores) the reference's vloam_tf blackboard: the pose hand-overs it carries are
 // device-resident (vloam_set_lo_prior / vloam_process_frame are the VO coupling points).
 #pragma once
 #include <array>
+#include <cstring>
 #include <memory>
 #include <mutex>
 #include <stdexcept>
@@ -82,11 +85,12 @@ inline void check(vloam_status s) {
   if (s != VLOAM_OK) throw std::runtime_error(std::string("vloam_hip: ") + vloam_last_error());
 }
 
-inline bool same_cloud(const Cloud& a, const Cloud& b) {  // cheap identity check: size, first and last point bit for bit
+// identity check of a handed-in cloud against the device's (already downloaded whole): all four floats of every point, bit for bit.  A
+// nudged interior point or an intensity-only edit (intensity = scan line + 0.1 relTime: the line walks and the map's centroids read it) is an edit.
+inline bool same_cloud(const Cloud& a, const Cloud& b) {
+  static_assert(sizeof(PointXYZI) == 16, "packed x, y, z, intensity");
   if (a.size() != b.size()) return false;
-  if (a.empty()) return true;
-  auto eq = [](const PointXYZI& p, const PointXYZI& q) { return p.x == q.x && p.y == q.y && p.z == q.z; };
-  return eq(a.front(), b.front()) && eq(a.back(), b.back());
+  return a.empty() || std::memcmp(a.data(), b.data(), a.size() * sizeof(PointXYZI)) == 0;
 }
 
 // cloud pointer <-> Cloud (the reference's pcl::PointCloud<PointType>::Ptr, PointType = pcl::PointXYZI, common.h:42); a null pointer is
@@ -182,7 +186,7 @@ class LaserOdometry {
   void init() {}
   template <class TF> void init(std::shared_ptr<TF>&) {}   // laser_odometry.h:70 takes the vloam_tf blackboard
   // laser_odometry.cpp:135-146 deep-copies the five clouds it is handed.  What scan registration produced is already resident in HBM: such
-  // clouds (size + first / last point equal) cost nothing; anything else is uploaded and the odometry of this sweep — and, for the two
+  // clouds (equal bit for bit) cost nothing; anything else is uploaded and the odometry of this sweep — and, for the two
   // less-clouds, of the next sweep, whose CornerLast / SurfLast they become (laser_odometry.cpp:506-526) — works on it.
   void input(const Cloud& laserCloud, const Cloud& cornerPointsSharp, const Cloud& cornerPointsLessSharp, const Cloud& surfPointsFlat,
              const Cloud& surfPointsLessFlat) {
@@ -251,6 +255,7 @@ class LaserMapping {
     if (skip_frame != ((s_->frames_done % s_->config.mapping_skip_frame) != 0))   // (the flag only ever comes from LaserOdometry::output; the device applies the same rule)
       throw std::invalid_argument("vloam_hip: LaserMapping::input: skip_frame differs from frameCount % mapping_skip_frame (laser_odometry.cpp:618)");
     skip_frame_ = skip_frame;
+    solved_ = false;   // a new sweep: publish() runs its mapping unless solveMapping() does
     const Cloud* given[3] = {&laserCloudCornerLast, &laserCloudSurfLast, &laserCloudFullRes};
     static const int which[3] = {5, 6, 0};
     const float* ptr[3] = {nullptr, nullptr, nullptr}; int n[3] = {0, 0, 0}; bool any = false;
@@ -268,7 +273,7 @@ class LaserMapping {
     for (int i = 0; i < 3; i++) same_pose = same_pose && t[i] == td[i];
     if (any || !same_pose) check(vloam_set_mapping_input(s_->get(), ptr[0], n[0], ptr[1], n[1], ptr[2], n[2], same_pose ? nullptr : q, same_pose ? nullptr : t));
   }
-  void input() { skip_frame_ = (s_->frames_done % s_->config.mapping_skip_frame) != 0; }
+  void input() { skip_frame_ = (s_->frames_done % s_->config.mapping_skip_frame) != 0; solved_ = false; }
   template <class P, class Q, class V, detail::CloudPtrLike<P> = 0>
   void input(const P& laserCloudCornerLast_, const P& laserCloudSurfLast_, const P& laserCloudFullRes_, const Q& q_wodom_curr_, const V& t_wodom_curr_,
              const bool& skip_frame) {   // laser_mapping.h:88-91
@@ -277,6 +282,7 @@ class LaserMapping {
   // The reference's façade calls solveMapping() only `if (!skip_frame)` and publish() always (lidar_odometry_mapping.cpp:128-133); the
   // high-frequency pose of a skipped sweep comes out of publish() there.  vloam_laser_mapping does both (it applies the skip rule itself) and
   // closes the sweep, so either call order works: solveMapping() on every sweep, or the reference's conditional call followed by publish().
+  // input() opens the sweep: a solveMapping() left without its publish() does not make the next sweep's publish() a no-op.
   void solveMapping() { run(); solved_ = true; }
   void publish() { if (!solved_) run(); solved_ = false; }
   Cloud map() {   // /laser_cloud_map (laser_mapping.cpp:778-793)

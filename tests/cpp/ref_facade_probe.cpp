@@ -5,13 +5,17 @@
 // with their argument lists; only the logging / timing lines are not here.
 //   probe --selfcheck                         CPU only: conversions, pose accessors, Create() factories, Transform::as<tf2::Transform>()
 //   probe <sweeps.bin> <n> <pts> <skip>       GPU: n sweeps through the façade, one line of results per sweep
+//   probe --edits <sweeps.bin> <n> <pts> <dir>  GPU: same-size edits of the hand-overs, a refused edit, solveMapping() without publish() (see edits())
 #define VLOAM_HIP_WITH_PCL 1
 #define VLOAM_HIP_WITH_OPENCV 1
 #define VLOAM_HIP_WITH_CERES 1
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <memory>
+#include <string>
+#include <utility>
 #include <vector>
 #include <Eigen/Dense>
 #include <tf2/LinearMath/Transform.h>
@@ -116,8 +120,115 @@ static int selfcheck() {
   return 0;
 }
 
+// the device holds exactly the caller's cloud (all four floats of every point)
+static int held(const vloam::Session& s, int which, const pcl::PointCloud<PointType>::Ptr& c) {
+  const vloam::Cloud d = s.features(which), e = vloam::from_cloud_ptr(c);
+  return d.size() == e.size() && (d.empty() || std::memcmp(d.data(), e.data(), d.size() * sizeof(vloam::PointXYZI)) == 0);
+}
+
+// a within-line shuffle that keeps the first and the last point: every run of equal int(intensity) among points 1 .. n-2 reversed
+static void reverse_line_runs(pcl::PointCloud<PointType>& c) {
+  const size_t n = c.points.size();
+  for (size_t i = 1; i + 1 < n;) {
+    size_t j = i;
+    while (j + 1 < n - 1 && int(c.points[j + 1].intensity) == int(c.points[i].intensity)) j++;
+    for (size_t a = i, b = j; a < b; a++, b--) std::swap(c.points[a], c.points[b]);
+    i = j + 1;
+  }
+}
+
+// probe --edits <sweeps.bin> <n> <pts> <outdir>: mapping_skip_frame 2, hand-overs edited WITHOUT changing their size (compat.hpp must see
+// them as edits: the first and last point, the size, even the xyz of an edited point may stay the same), one refused edit, and a mapping
+// sweep that calls solveMapping() without publish() followed by a skipped sweep that calls publish() only.  One line per sweep:
+//   k held refused skip_frame q_wodom(4) t_wodom(3) q_map(4) t_map(3)
+// held: the device holds the edited odometry input after LaserOdometry::input (-1: no edit); refused: the refused edit threw
+// std::runtime_error (-1: none tried).  Files: <outdir>/registered3.bin (registeredCloud() of sweep 3), <outdir>/map.bin (map() at the end).
+static int edits(int argc, char** argv) {
+  if (argc < 6) return 64;
+  const int n_sweeps = std::atoi(argv[3]), n_pts = std::atoi(argv[4]);
+  const std::string outdir = argv[5];
+  std::FILE* f = std::fopen(argv[2], "rb");
+  if (!f) return 65;
+  vloam_config cfg; vloam_default_config(&cfg); cfg.mapping_skip_frame = 2;
+  auto session = std::make_shared<vloam::Session>(0, &cfg);
+  LidarOdometryMapping LOAM(session);
+  auto tf = std::make_shared<FakeTF>();
+  LOAM.init(tf);
+  pcl::PointCloud<pcl::PointXYZ> point_cloud_pcl;
+  for (int k = 0; k < n_sweeps; k++) {
+    point_cloud_pcl.points.resize((size_t)n_pts);
+    if (std::fread(point_cloud_pcl.points.data(), sizeof(pcl::PointXYZ), (size_t)n_pts, f) != (size_t)n_pts) return 2;
+    LOAM.reset();
+    LOAM.scanRegistrationIO(point_cloud_pcl);
+    int edited = -1, refused = -1;
+    if (k == 1) {   // an interior point of surfPointsFlat moved in z
+      auto& P = LOAM.surfPointsFlat->points;
+      P[P.size() / 2].z += 0.05f;
+      edited = 3;
+    }
+    if (k == 2) {   // the FIRST point of cornerPointsLessSharp: intensity (scan line + 0.1 relTime) only, xyz unchanged
+      LOAM.cornerPointsLessSharp->points[0].intensity += 0.03125f;
+      edited = 2;
+    }
+    if (k == 3) {   // surfPointsLessFlat reordered within its scan lines, first and last point in place
+      reverse_line_runs(*LOAM.surfPointsLessFlat);
+      edited = 4;
+    }
+    if (k == 4) {   // refused (c_api.h rule (i)): a NaN in cornerPointsSharp; the stage keeps scan registration's clouds
+      auto bad = boost::make_shared<pcl::PointCloud<PointType>>(*LOAM.cornerPointsSharp);
+      bad->points[bad->points.size() / 2].x = std::nanf("");
+      refused = 0;
+      try { LOAM.laser_odometry.input(LOAM.laserCloud, bad, LOAM.cornerPointsLessSharp, LOAM.surfPointsFlat, LOAM.surfPointsLessFlat); }
+      catch (const std::runtime_error&) { refused = 1; }
+    }
+    // laserOdometryIO spelled out: the device's clouds are read back between input() and solveLO()
+    LOAM.laser_odometry.input(LOAM.laserCloud, LOAM.cornerPointsSharp, LOAM.cornerPointsLessSharp, LOAM.surfPointsFlat, LOAM.surfPointsLessFlat);
+    const pcl::PointCloud<PointType>::Ptr* given[5] = {&LOAM.laserCloud, &LOAM.cornerPointsSharp, &LOAM.cornerPointsLessSharp, &LOAM.surfPointsFlat,
+                                                       &LOAM.surfPointsLessFlat};
+    const int held_flag = edited >= 0 ? held(*session, edited, *given[edited]) : -1;
+    LOAM.laser_odometry.solveLO();
+    LOAM.laser_odometry.publish();
+    LOAM.laser_odometry.output(LOAM.q_wodom_curr, LOAM.t_wodom_curr, LOAM.laserCloudCornerLast, LOAM.laserCloudSurfLast, LOAM.laserCloudFullRes, LOAM.skip_frame);
+    if (k == 3) {   // LaserMapping::input handed an interior point of laserCloudSurfLast and of laserCloudFullRes moved in z
+      auto& S = LOAM.laserCloudSurfLast->points;
+      S[S.size() / 2].z += 0.05f;
+      auto& F = LOAM.laserCloudFullRes->points;
+      F[F.size() / 2].z += 0.05f;
+    }
+    LOAM.laser_mapping.input(LOAM.laserCloudCornerLast, LOAM.laserCloudSurfLast, LOAM.laserCloudFullRes, LOAM.q_wodom_curr, LOAM.t_wodom_curr, LOAM.skip_frame);
+    if (k == 1) LOAM.laser_mapping.solveMapping();    // mapped sweep: solveMapping() and no publish()
+    else if (k == 2) LOAM.laser_mapping.publish();    // the skipped sweep after it: publish() only
+    else { if (!LOAM.skip_frame) LOAM.laser_mapping.solveMapping(); LOAM.laser_mapping.publish(); }
+    std::printf("%d %d %d %d", k, held_flag, refused, (int)LOAM.skip_frame);
+    std::printf(" %.17g %.17g %.17g %.17g", LOAM.q_wodom_curr.x(), LOAM.q_wodom_curr.y(), LOAM.q_wodom_curr.z(), LOAM.q_wodom_curr.w());
+    std::printf(" %.17g %.17g %.17g", LOAM.t_wodom_curr.x(), LOAM.t_wodom_curr.y(), LOAM.t_wodom_curr.z());
+    const vloam::Quaterniond& qm = LOAM.skip_frame ? LOAM.laser_mapping.q_w_curr_highfreq : LOAM.laser_mapping.q_w_curr;
+    const vloam::Vector3d& tm = LOAM.skip_frame ? LOAM.laser_mapping.t_w_curr_highfreq : LOAM.laser_mapping.t_w_curr;
+    for (int i = 0; i < 4; i++) std::printf(" %.17g", qm[i]);
+    for (int i = 0; i < 3; i++) std::printf(" %.17g", tm[i]);
+    std::printf("\n");
+    std::fflush(stdout);
+    if (k == 3) {
+      const vloam::Cloud reg = LOAM.laser_mapping.registeredCloud();
+      std::FILE* o = std::fopen((outdir + "/registered3.bin").c_str(), "wb");
+      if (!o || std::fwrite(reg.data(), sizeof(vloam::PointXYZI), reg.size(), o) != reg.size()) return 3;
+      std::fclose(o);
+    }
+  }
+  const vloam::Cloud map = LOAM.laser_mapping.map();
+  std::FILE* o = std::fopen((outdir + "/map.bin").c_str(), "wb");
+  if (!o || std::fwrite(map.data(), sizeof(vloam::PointXYZI), map.size(), o) != map.size()) return 3;
+  std::fclose(o);
+  std::fclose(f);
+  std::printf("done\n");
+  return 0;
+}
+
 int main(int argc, char** argv) {
   if (argc >= 2 && std::strcmp(argv[1], "--selfcheck") == 0) return selfcheck();
+  if (argc >= 2 && std::strcmp(argv[1], "--edits") == 0) {
+    try { return edits(argc, argv); } catch (const std::exception& e) { std::printf("exception %s\n", e.what()); return 4; }
+  }
   if (argc < 5) return 64;
   const int n_sweeps = std::atoi(argv[2]), n_pts = std::atoi(argv[3]), skip = std::atoi(argv[4]);
   std::FILE* f = std::fopen(argv[1], "rb");

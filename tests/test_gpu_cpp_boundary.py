@@ -232,3 +232,81 @@ def test_reference_typed_facade_on_the_gpu(tmp_path, orc, sweeps, vl):
     info = o.map_info()
     assert int(out[n].split()[1]) == info["total_corner"] + info["total_surf"]
     assert out[n + 1].split() == ["vo", "1", "0"]
+
+
+def reverse_line_runs(c):
+    """ref_facade_probe.cpp reverse_line_runs: every run of equal int(intensity) among points 1 .. n-2 reversed (first and last point stay)."""
+    c = c.copy()
+    n, i = c.shape[0], 1
+    L = np.trunc(c[:, 3].astype(np.float64)).astype(np.int64)
+    while i + 1 < n:
+        j = i
+        while j + 1 < n - 1 and L[j + 1] == L[i]:
+            j += 1
+        c[i:j + 1] = c[i:j + 1][::-1].copy()
+        i = j + 1
+    return c
+
+
+def nudged(c, dz=np.float32(0.05)):
+    c = c.copy()
+    c[c.shape[0] // 2, 2] += dz
+    return c
+
+
+def test_reference_typed_facade_same_size_edits(tmp_path, orc, sweeps, vl):
+    """ref_facade_probe --edits: hand-overs edited without changing their size — an interior z nudge of surfPointsFlat (sweep 1), the
+    intensity alone of the FIRST point of cornerPointsLessSharp (sweep 2, walked as CornerLast on sweep 3), surfPointsLessFlat reordered
+    within its lines with the first and last point in place (sweep 3, walked on sweep 4), interior nudges of laserCloudSurfLast and
+    laserCloudFullRes before LaserMapping::input (sweep 3).  compat.hpp must upload each of them (the device holds the edited cloud) and the
+    poses, the registered cloud and the published map equal the oracle's with the same edits.  Sweep 4: a NaN in cornerPointsSharp throws
+    std::runtime_error and the sweep runs on scan registration's clouds.  Sweep 1 calls solveMapping() without publish(), the skipped sweep 2
+    publish() only: its high-frequency pose is the oracle's and sweep 3 runs (no ERR_ORDER)."""
+    from test_gpu_laser_mapping import oracle_published_map, same_cloud
+    n, shape = 6, (64, 512)
+    clouds = [sweeps(shape[0], shape[1], k) for k in range(n)]
+    data = tmp_path / "sweeps.bin"
+    np.stack(clouds).astype(np.float32).tofile(data)
+    exe = tmp_path / "ref_probe"
+    libdir = os.path.join(ROOT, "vloam-cmu-16833_amd")
+    subprocess.check_call(["g++", "-std=c++14", "-O1", "-Wall", "-Werror", "-I", os.path.join(ROOT, "tests", "stubs"), "-I", os.path.join(ROOT, "include"),
+                           os.path.join(ROOT, "tests", "cpp", "ref_facade_probe.cpp"), "-o", str(exe),
+                           "-L", libdir, "-lvloam_hip", "-Wl,-rpath," + libdir, "-L/opt/rocm/lib", "-Wl,-rpath,/opt/rocm/lib"])
+    r = subprocess.run([str(exe), "--edits", str(data), str(n), str(clouds[0].shape[0]), str(tmp_path)], capture_output=True, text=True)
+    out = r.stdout.strip().split("\n")
+    o = orc.Oracle(with_mapping=True, mapping_skip_frame=2)
+    for k in range(n):
+        f = out[k].split() if k < len(out) else []
+        assert len(f) == 18 and int(f[0]) == k, (k, r.returncode, r.stdout[-3000:], r.stderr[-3000:])
+        assert o.stage_sr(clouds[k]) == 0
+        if k == 1:
+            o.set_sr_cloud(3, nudged(o.cloud(3)))
+        elif k == 2:
+            ls = o.cloud(2).copy()
+            ls[0, 3] += np.float32(0.03125)
+            o.set_sr_cloud(2, ls)
+        elif k == 3:
+            lf = o.cloud(4)
+            rev = reverse_line_runs(lf)
+            assert not np.array_equal(rev, lf) and np.array_equal(rev[[0, -1]], lf[[0, -1]])
+            o.set_sr_cloud(4, rev)
+        o.stage_lo()
+        kw = dict(surf=nudged(o.cloud(6)), full=nudged(o.cloud(0))) if k == 3 else {}
+        assert o.stage_map(**kw) == 0
+        held, refused, skipped = int(f[1]), int(f[2]), int(f[3])
+        assert held == (1 if k in (1, 2, 3) else -1), "sweep %d: LaserOdometry::input did not upload a same-size edit" % k
+        assert refused == (1 if k == 4 else -1), "sweep %d: the refused edit did not throw" % k
+        assert skipped == int(((k + 1) % 2) != 0)
+        v = np.array([float(x) for x in f[4:18]])
+        qw, tw, _, _ = o.lo_pose()
+        qm, tm = o.map_published_pose()
+        assert qdist(v[0:4], qw) < 1e-8 and np.linalg.norm(v[4:7] - tw) < 1e-8, "sweep %d odometry pose" % k
+        assert qdist(v[7:11], qm) < 1e-8 and np.linalg.norm(v[11:14] - tm) < 1e-8, "sweep %d mapping pose" % k
+        if k == 3:
+            reg = np.fromfile(tmp_path / "registered3.bin", dtype=np.float32).reshape(-1, 4)
+            ref = o.cloud(11)
+            assert reg.shape == ref.shape and np.allclose(reg[:, :3], ref[:, :3], rtol=0, atol=1e-5), "registered cloud of the nudged laserCloudFullRes"
+            assert np.array_equal(reg[:, 3].view(np.uint32), ref[:, 3].view(np.uint32))
+    assert r.returncode == 0 and len(out) == n + 1 and out[n] == "done", (r.returncode, r.stdout[-3000:], r.stderr[-3000:])
+    got = np.fromfile(tmp_path / "map.bin", dtype=np.float32).reshape(-1, 4)
+    assert same_cloud(got, oracle_published_map(o)), "published map"

@@ -541,6 +541,12 @@ class Handle:
 
 # ------------------------------------------------------------------------------------------------
 # Python mirror of the reference's class surface (same method names / call order / error behaviour).
+def _same_cloud(given, own):
+    """A handed-in cloud is the device's own when all four floats of every point are equal bit for bit (compat.hpp same_cloud)."""
+    a = np.ascontiguousarray(given, dtype=np.float32).reshape(-1, 4)
+    return a.shape == own.shape and np.array_equal(a.view(np.uint32), np.ascontiguousarray(own).view(np.uint32))
+
+
 class ScanRegistration:
     """vloam::ScanRegistration (scan_registration.h:71-77): init / reset / input / output."""
 
@@ -571,7 +577,19 @@ class LaserOdometry:
         pass
 
     def input(self, *clouds):
-        pass  # clouds stay resident in HBM; the reference deep-copies them here (laser_odometry.cpp:141-145)
+        """laser_odometry.cpp:135-146 deep-copies the five clouds it is handed (laserCloud, cornerPointsSharp, cornerPointsLessSharp,
+        surfPointsFlat, surfPointsLessFlat).  Scan registration's clouds are resident on the device; a cloud that differs from the device's bit
+        for bit is uploaded (vloam_set_odometry_input, under the rule c_api.h states).  No arguments: keep the device's."""
+        if not clouds:
+            return
+        if len(clouds) != 5:
+            raise TypeError("LaserOdometry.input takes the five clouds of ScanRegistration.output")
+        edits = {}
+        for k, (name, c) in enumerate(zip(("laserCloud", "cornerPointsSharp", "cornerPointsLessSharp", "surfPointsFlat", "surfPointsLessFlat"), clouds)):
+            if not _same_cloud(c, self.hd.features(k)):
+                edits[name] = c
+        if edits:
+            self.hd.set_odometry_input(**edits)
 
     def solveLO(self):
         self._pose = self.hd.laser_odometry()
@@ -602,7 +620,28 @@ class LaserMapping:
         pass
 
     def input(self, *args):
-        pass
+        """laser_mapping.cpp:167-196: input(laserCloudCornerLast, laserCloudSurfLast, laserCloudFullRes, q_wodom_curr, t_wodom_curr, skip_frame)
+        copies the three clouds (unless skip_frame) and the odometry pose.  What differs bit for bit from LaserOdometry.output's is uploaded
+        (vloam_set_mapping_input).  No arguments: keep the device's."""
+        if not args:
+            return
+        if len(args) != 6:
+            raise TypeError("LaserMapping.input takes (corner, surf, full, q_wodom_curr, t_wodom_curr, skip_frame)")
+        corner, surf, full, q, t, skip = args
+        if bool(skip) != (self.hd.frame_count() % self.hd.cfg.mapping_skip_frame != 0):
+            raise ValueError("LaserMapping.input: skip_frame differs from frameCount % mapping_skip_frame (laser_odometry.cpp:618)")
+        edits = {}
+        if not skip:
+            for name, c, which in (("laserCloudCornerLast", corner, 5), ("laserCloudSurfLast", surf, 6), ("laserCloudFullRes", full, 0)):
+                if not _same_cloud(c, self.hd.features(which)):
+                    edits[name] = c
+        qd, td = self.hd.odometry_pose()
+        q = np.asarray(q, dtype=np.float64)
+        t = np.asarray(t, dtype=np.float64)
+        if not (np.array_equal(q, qd) and np.array_equal(t, td)):
+            edits.update(q_wodom_curr=q, t_wodom_curr=t)
+        if edits:
+            self.hd.set_mapping_input(**edits)
 
     def solveMapping(self):
         self.pose = self.hd.laser_mapping()

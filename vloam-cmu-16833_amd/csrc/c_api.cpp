@@ -22,6 +22,7 @@
 #include "lo_kernels.h"
 #include "map_kernels.h"
 #include "sr_kernels.h"
+#include "stage_input_check.h"
 #include "vloam_device.h"
 #include "vo_kernels.h"
 #include "img_kernels.h"
@@ -41,6 +42,24 @@ static void set_err(const char* fmt, ...) {
   vsnprintf(buf, sizeof(buf), fmt, ap);
   va_end(ap);
   g_err = buf;
+}
+
+// The admission rule of substituted clouds (stage_input_check.h), applied to the HOST arrays before anything is synchronised or uploaded: a
+// refused call leaves the handle as it was.  Null clouds (keep the device's) are not checked.
+static_assert(vloam_stage_check::kStageLines == kMaxRings, "the walk-stop tables hold kMaxRings lines");
+static vloam_status check_stage_clouds(const char* call, int count, const char* const* names, const float* const* src, const int* n, const bool* walked) {
+  for (int k = 0; k < count; k++) {
+    if (!src[k]) continue;
+    const vloam_stage_check::Fault f = vloam_stage_check::check_cloud(src[k], n[k], walked[k]);
+    if (f.rule == vloam_stage_check::kOk) continue;
+    if (f.rule == vloam_stage_check::kLineOrder)
+      set_err("%s: %s, point %d: intensity %.9g, line %d after line %d: %s", call, names[k], f.point, (double)f.value, (int)f.value, f.max_line,
+              vloam_stage_check::rule_text(f.rule));
+    else
+      set_err("%s: %s, point %d: intensity %.9g: %s", call, names[k], f.point, (double)f.value, vloam_stage_check::rule_text(f.rule));
+    return VLOAM_ERR_INVALID;
+  }
+  return VLOAM_OK;
 }
 #define HIPCHK(expr)                                                                          \
   do {                                                                                        \
@@ -842,6 +861,13 @@ vloam_status vloam_set_odometry_input(vloam_handle* h, const float* laserCloud, 
     if (n[k] < 0) { set_err("negative cloud size"); return VLOAM_ERR_INVALID; }
     if (n[k] > cap[k]) { set_err("substituted cloud %d holds %d points, the buffer takes %d", k, n[k], cap[k]); return VLOAM_ERR_CAPACITY; }
   }
+  {   // the two less-clouds are the next sweep's CornerLast / SurfLast, walked by scan line (stage_input_check.h)
+    static const char* const names[5] = {"laserCloud (cloud 0)", "cornerPointsSharp (cloud 1)", "cornerPointsLessSharp (cloud 2)", "surfPointsFlat (cloud 3)",
+                                         "surfPointsLessFlat (cloud 4)"};
+    static const bool walked[5] = {false, false, true, false, true};
+    vloam_status s_ = check_stage_clouds("vloam_set_odometry_input", 5, names, src, n, walked);
+    if (s_ != VLOAM_OK) return s_;
+  }
   { vloam_status s_ = sync_all(h); if (s_ != VLOAM_OK) return s_; }
   const int cur = set_of(h->frame);
   const SRBuffers& b = h->sr[cur];
@@ -886,6 +912,14 @@ vloam_status vloam_set_mapping_input(vloam_handle* h, const float* laserCloudCor
   if ((laserCloudCornerLast && (n_corner < 0 || n_corner > kMaxLessSharp)) || (laserCloudSurfLast && (n_surf < 0 || n_surf > h->cfg.max_points)) ||
       (laserCloudFullRes && (n_full < 0 || n_full > h->cfg.max_points))) { set_err("substituted cloud does not fit its buffer"); return VLOAM_ERR_CAPACITY; }
   if ((q_wodom_curr == nullptr) != (t_wodom_curr == nullptr)) { set_err("the odometry pose is q AND t"); return VLOAM_ERR_INVALID; }
+  {   // mapping does not walk by line: finiteness only (stage_input_check.h)
+    static const char* const names[3] = {"laserCloudCornerLast (cloud 0)", "laserCloudSurfLast (cloud 1)", "laserCloudFullRes (cloud 2)"};
+    static const bool walked[3] = {false, false, false};
+    const float* src[3] = {laserCloudCornerLast, laserCloudSurfLast, laserCloudFullRes};
+    const int n[3] = {n_corner, n_surf, n_full};
+    vloam_status s_ = check_stage_clouds("vloam_set_mapping_input", 3, names, src, n, walked);
+    if (s_ != VLOAM_OK) return s_;
+  }
   { vloam_status s_ = sync_all(h); if (s_ != VLOAM_OK) return s_; }
   const int frame = h->frame, cur = set_of(frame);
   const bool skip = ((frame + 1) % h->cfg.mapping_skip_frame) != 0;
