@@ -23,6 +23,7 @@
 #include "map_kernels.h"
 #include "sr_kernels.h"
 #include "stage_input_check.h"
+#include "stream_plan.h"
 #include "vloam_device.h"
 #include "vo_kernels.h"
 #include "img_kernels.h"
@@ -82,6 +83,7 @@ struct vloam_handle {
   hipStream_t s_map = nullptr;    // laser mapping
   hipStream_t s_img = nullptr;    // image front-end of the coupled frame loop (needs the image only: next to the scan-registration stream)
   hipStream_t s_ds = nullptr;     // VoxelGrid of the scan features for mapping (needs the sweep's feature clouds only: off the SR stream's chain)
+  int prio[vloam_plan::kStreams] = {};   // the HIP priority each stream is created with (= its hardware-queue pool: stream_plan.h)
   static constexpr int kSets = kBufferSets;   // 3 suffice for correctness; the rest is run-ahead for the host (vloam_device.h)
   hipEvent_t ev_sr[kSets] = {}, ev_lo[kSets] = {}, ev_map[kSets] = {}, ev_stack[kSets] = {};  // "stage finished for the sweep in set c"
   static_assert(kSets == MapContext::kSets, "the stack sets rotate with the SR buffer sets");
@@ -111,7 +113,7 @@ struct vloam_handle {
   // buffer of its own (slot kInRing), the stream's order being the dependency.
   static constexpr int kInRing = 4;
   float4* d_in = nullptr;         // [kInRing + 1][max_points]
-  hipStream_t s_copy = nullptr;   // created by the first deferred host sweep
+  hipStream_t s_copy = nullptr;   // host-sweep copies: vloam_create (plan.copy_first) or the first deferred host sweep
   hipEvent_t ev_in_copied[kInRing] = {};
   hipEvent_t in_reader[kInRing] = {};
   int in_next = 0;                // next ring slot
@@ -313,20 +315,18 @@ vloam_status vloam_create_batch(const vloam_config* cfg, int device, int n_sessi
       ((cfg->image_width > 0) != (cfg->image_height > 0)) || (cfg->image_width > 0 && (cfg->image_width < 2 * kImgWin || cfg->image_height < 2 * kImgWin))) {
     set_err("image_width x image_height must be 0 x 0 (no image front-end) or between %d x %d and 2^24 pixels", 2 * kImgWin, 2 * kImgWin); return VLOAM_ERR_INVALID;
   }
-  // A handle drives four to six HIP streams that must run side by side (scan registration | scan-feature VoxelGrid | odometry | mapping
-  // [| images] [| host-input copies]); the runtime maps ALL streams of the process onto GPU_MAX_HW_QUEUES hardware queues (default 4) and two
-  // stages sharing a queue serialise — measured: 214 us per sweep instead of 164 with 4 queues; with 8 queues the same happens as soon as
-  // the host process keeps four streams of its own alive (6 400 -> 4 700 scans/s, 3 800 with five; 16 queues: 6 300 with any number,
-  // profiles/r05_hw_queues.txt).  The variable is read when the HIP runtime initialises, so it belongs to the HOST's environment
-  // (the Python package and bench.py export 16 before they load the runtime): a library must not setenv() behind a
-  // multi-threaded host's back (not thread-safe against a concurrent getenv, and silently without effect once HIP is up).
-  // Said once per process instead.
+  // A handle drives two to six HIP streams that must run side by side (scan registration | odometry [| mapping | scan-feature VoxelGrid]
+  // [| images] [| host-sweep copies]).  GPU_MAX_HW_QUEUES (read by the runtime when it initialises: it belongs to the HOST's environment, and a
+  // library must not setenv() behind a multi-threaded host) caps each of the runtime's three priority pools of hardware queues; the handle
+  // picks its streams' priorities from it (stream_plan.h).  Said once per process when the plan is the pooled one.
+  const int queue_budget = vloam_plan::budget_from_env(getenv("GPU_MAX_HW_QUEUES"));
+  const vloam_plan::Plan plan = vloam_plan::make_plan(queue_budget, cfg->with_mapping != 0, cfg->image_width > 0);
   {
     static std::atomic<bool> warned{false};   // (handles may be created from several threads)
-    const char* q = getenv("GPU_MAX_HW_QUEUES");
-    if ((!q || atoi(q) < 8) && !warned.exchange(true)) {
-      fprintf(stderr, "libvloam_hip: GPU_MAX_HW_QUEUES is %s: the stage streams of a handle will share hardware queues and a sweep takes ~30 %% longer; "
-                      "export GPU_MAX_HW_QUEUES=16 before the process initialises HIP\n", q ? q : "unset (runtime default 4)");
+    if (plan.pooled && !warned.exchange(true)) {
+      fprintf(stderr, "libvloam_hip: GPU_MAX_HW_QUEUES is %d: the stage streams of a handle take hardware queues from the runtime's three priority "
+                      "pools (scan registration low, odometry normal, mapping high), so that no two of them share one; export GPU_MAX_HW_QUEUES=16 "
+                      "to keep them all at normal priority\n", queue_budget);
     }
   }
   int ndev = 0;
@@ -353,11 +353,19 @@ vloam_status vloam_create_batch(const vloam_config* cfg, int device, int n_sessi
   vloam_status st = VLOAM_OK;
   do {
     {
-      // VLOAM_STREAM_PRIO = "sr,lo,map,ds" (0 = default priority, 1 = the device's highest, -1 = its lowest): which stage's workgroups the
-      // dispatcher places first when several stages have work pending (batched handles fill the chip; a single sequence does not)
-      int lo_p = 0, hi_p = 0, pr[5] = {0, 0, 0, 0, 0};   // (a fifth field: the image front-end's stream)
-      if (const char* e = getenv("VLOAM_STREAM_PRIO")) sscanf(e, "%d,%d,%d,%d,%d", &pr[0], &pr[1], &pr[2], &pr[3], &pr[4]);
+      // the plan's pools as HIP priorities; VLOAM_STREAM_PRIO = "sr,lo,map,ds[,img]" (experiment: 0 = normal, 1 = the device's highest, -1 =
+      // its lowest) overrides them
+      int lo_p = 0, hi_p = 0;
       if (hipDeviceGetStreamPriorityRange(&lo_p, &hi_p) != hipSuccess) { lo_p = hi_p = 0; }   // lo_p = numerically greatest = lowest priority
+      const int pool_prio[vloam_plan::kPools] = {0, hi_p, lo_p};
+      for (int w = 0; w < vloam_plan::kStreams; w++) h->prio[w] = pool_prio[plan.pool[w]];
+      if (const char* e = getenv("VLOAM_STREAM_PRIO")) {
+        using namespace vloam_plan;
+        int pr[5] = {0, 0, 0, 0, 0};
+        sscanf(e, "%d,%d,%d,%d,%d", &pr[0], &pr[1], &pr[2], &pr[3], &pr[4]);
+        const int which[5] = {kSR, kLO, kMap, kDS, kImg};
+        for (int k = 0; k < 5; k++) h->prio[which[k]] = pr[k] > 0 ? hi_p : (pr[k] < 0 ? lo_p : 0);
+      }
       // VLOAM_RESERVE_CUS = "n[,stride]" (experiment): the scan-registration, odometry and VoxelGrid streams are created with a CU mask that
       // leaves n compute units (every stride-th bit from 0) to the mapping stream alone
       int rsv = 0, rstride = 1;
@@ -365,21 +373,22 @@ vloam_status vloam_create_batch(const vloam_config* cfg, int device, int n_sessi
       hipDeviceProp_t prop;
       const int ncu = (rsv > 0 && hipGetDeviceProperties(&prop, device) == hipSuccess) ? prop.multiProcessorCount : 0;
       auto mk = [&](hipStream_t* s, int which) {
-        if (ncu > 0 && which != 2) {
+        if (ncu > 0 && which != vloam_plan::kMap) {
           uint32_t mask[16];
           for (int w = 0; w < 16; w++) mask[w] = 0;
           for (int c = 0; c < ncu && c < 512; c++) mask[c >> 5] |= 1u << (c & 31);
           for (int k = 0, c = 0; k < rsv && c < ncu; k++, c += rstride) mask[c >> 5] &= ~(1u << (c & 31));
           return hipExtStreamCreateWithCUMask(s, (uint32_t)((ncu + 31) / 32), mask) == hipSuccess;
         }
-        const int p = pr[which] > 0 ? hi_p : (pr[which] < 0 ? lo_p : 0);
-        return hipStreamCreateWithPriority(s, hipStreamNonBlocking, p) == hipSuccess;
+        return hipStreamCreateWithPriority(s, hipStreamNonBlocking, h->prio[which]) == hipSuccess;
       };
-      // The copy stream of the deferred host-sweep ring comes FIRST and is used once before any other stream of the handle has work: measured
-      // (tools/host_input_probe.py, extring / extring_late) a copy stream that gets its hardware queue after the compute streams runs host-fed
-      // sequences at 3 900 - 4 600 scans/s, one that got it before them at 5 650.
-      if (!g_stage_inline && !cfg->timing) {
-        if (hipStreamCreateWithFlags(&h->s_copy, hipStreamNonBlocking) != hipSuccess) { set_err("hipStreamCreate failed"); st = VLOAM_ERR_HIP; break; }
+      // the runtime gives a stream its hardware queue when the stream is created, so the order matters (stream_plan.h).  plan.copy_first: the
+      // copy stream of the deferred host-sweep ring comes FIRST and is used once before any other stream of the handle has work — measured
+      // (tools/host_input_probe.py, extring / extring_late; profiles/r06_host_input.txt) a copy stream that gets its hardware queue after the
+      // compute streams runs host-fed sequences at 3 900 - 4 600 scans/s, one that got it before them at 5 650
+      using namespace vloam_plan;
+      if (plan.copy_first && !g_stage_inline && !cfg->timing) {
+        if (hipStreamCreateWithPriority(&h->s_copy, hipStreamNonBlocking, h->prio[kCopy]) != hipSuccess) { set_err("hipStreamCreate failed"); st = VLOAM_ERR_HIP; break; }
         static int warm_src = 0;
         int* warm_dst = nullptr;
         if (hipMalloc(&warm_dst, sizeof(int)) == hipSuccess) {
@@ -388,10 +397,10 @@ vloam_status vloam_create_batch(const vloam_config* cfg, int device, int n_sessi
           (void)hipFree(warm_dst);
         }
       }
-      if (!mk(&h->stream, 0) || !mk(&h->s_lo, 1) || (cfg->with_mapping && (!mk(&h->s_map, 2) || !mk(&h->s_ds, 3))) ||   // no mapping: no further hardware queues
-          (cfg->image_width > 0 && !mk(&h->s_img, 4))) {
-        set_err("hipStreamCreate failed"); st = VLOAM_ERR_HIP; break;
-      }
+      bool ok = mk(&h->stream, kSR) && mk(&h->s_lo, kLO);
+      if (ok && cfg->with_mapping) ok = mk(&h->s_map, kMap) && mk(&h->s_ds, kDS);   // no mapping: no further hardware queues
+      if (ok && cfg->image_width > 0) ok = mk(&h->s_img, kImg);
+      if (!ok) { set_err("hipStreamCreate failed"); st = VLOAM_ERR_HIP; break; }
     }
     if (sr_init() != hipSuccess) { set_err("sr_init failed (no gfx950 code object for this device?)"); st = VLOAM_ERR_HIP; break; }
     if (cfg->image_width > 0 && img_init() != hipSuccess) { set_err("img_init failed"); st = VLOAM_ERR_HIP; break; }
@@ -592,7 +601,7 @@ static vloam_status enqueue_sr(vloam_handle* h, const BatchIn& bi) {
   if (h->cfg.timing) HIPCHK(hipEventRecord(h->ev[1], h->stream));
   // the mapping stage's VoxelGrid of the scan features only needs this sweep's clouds: run it here, off the mapping stream
   if (h->cfg.with_mapping && ((k + 1) % h->cfg.mapping_skip_frame) == 0) {
-    HIPCHK(hipStreamWaitEvent(h->s_ds, h->ev_sr[cur], 0));   // the feature clouds (ev_sr is bound to k_sr_compact); a live wait, on a stream that has the time
+    HIPCHK(hipStreamWaitEvent(h->s_ds, h->ev_sr[cur], 0));   // the feature clouds (ev_sr is bound to k_sr_compact); a live wait: on a queue of its own, or SR's (budget 1, or several handles alive at a small budget: stream_plan.h)
     if (map_stack_enqueue(&h->map, h->s_ds, h->sr[cur], cur, &h->prof, h->ev_stack[cur]) != VLOAM_OK) { set_err("map_stack_enqueue failed"); return VLOAM_ERR_HIP; }
   }
   h->last_n_in = n;
@@ -737,7 +746,7 @@ static vloam_status flush_pending(vloam_handle* h) {
 }
 static vloam_status host_scan_deferred(vloam_handle* h, const float* const* xyz_pad4, const int* n) {
   if (h->frame + (h->pend.valid ? 1 : 0) >= h->cfg.max_frames) { set_err("trajectory log full (max_frames=%d)", h->cfg.max_frames); return VLOAM_ERR_CAPACITY; }
-  if (!h->s_copy) HIPCHK(hipStreamCreateWithFlags(&h->s_copy, hipStreamNonBlocking));   // (normally created first of all streams: vloam_create)
+  if (!h->s_copy) HIPCHK(hipStreamCreateWithPriority(&h->s_copy, hipStreamNonBlocking, h->prio[vloam_plan::kCopy]));   // (plan.copy_first: created by vloam_create)
   if (!h->ev_in_copied[0]) for (int k = 0; k < vloam_handle::kInRing; k++) HIPCHK(hipEventCreateWithFlags(&h->ev_in_copied[k], hipEventDisableTiming));
   const int slot = h->in_next % vloam_handle::kInRing;
   h->in_next++;
