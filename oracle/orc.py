@@ -233,6 +233,15 @@ def eval_lidar_factor(ftype, curr, geom, q, t, s=1.0):
     return r[:n], J[:n]
 
 
+def eval_vo_factor(ftype, payload, angles, t):
+    """Residual + Jacobian [nres, 6] (angle-axis, t) of one VO functor: ftype 3 = CostFunctor32, 4 = CostFunctor22 (orc_solve's numbering)."""
+    L = lib()
+    payload, angles, t = [np.ascontiguousarray(a, dtype=np.float64) for a in (payload, angles, t)]
+    r, J = np.zeros(2), np.zeros((2, 6))
+    n = L.orc_eval_vo_factor(ftype, _p(payload, D), _p(angles, D), _p(t, D), _p(r, D), _p(J, D))
+    return r[:n], J[:n]
+
+
 def solve(factors, p0, p1, quaternion=True, huber_a=0.1, max_iters=4):
     """Run the Ceres-LM restatement on a list of factor rows (see orc_capi.cpp: orc_solve)."""
     L = lib()

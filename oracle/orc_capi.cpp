@@ -289,6 +289,20 @@ int orc_eval_lidar_factor_s(int type, const double* curr3, const double* geom, c
   return f->nres;
 }
 
+// type: 3 CostFunctor32 (payload x0, y0, z0, x1_bar, y1_bar), 4 CostFunctor22 (payload x0_bar, y0_bar, x1_bar, y1_bar) — the numbering of
+// orc_solve below.  Returns nres; residual[nres]; jac = nres x 6 row-major with respect to (angle-axis[3], t[3]); no loss applied.
+int orc_eval_vo_factor(int type, const double* p, const double* angles3, const double* t3, double* residual, double* jac) {
+  std::unique_ptr<CostFunction> f;
+  if (type == 3) f.reset(new AutoDiffCost<CostFunctor32, 2, 3>(CostFunctor32(p[0], p[1], p[2], p[3], p[4])));
+  else if (type == 4) f.reset(new AutoDiffCost<CostFunctor22, 1, 3>(CostFunctor22(p[0], p[1], p[2], p[3])));
+  else return -1;
+  double j0[6], j1[6];
+  f->Evaluate(angles3, t3, residual, j0, j1);
+  for (int k = 0; k < f->nres; k++)
+    for (int a = 0; a < 3; a++) { jac[k * 6 + a] = j0[k * 3 + a]; jac[k * 6 + 3 + a] = j1[k * 3 + a]; }
+  return f->nres;
+}
+
 // Generic driver for the LM restatement.  Factors: rows of 16 doubles {type, payload...}:
 //   type 0 edge      : curr[3], a[3], b[3]
 //   type 1 plane     : curr[3], j[3], l[3], m[3]

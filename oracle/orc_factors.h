@@ -1,4 +1,6 @@
-// ORACLE — TEST INFRASTRUCTURE ONLY (see orc_math.h header).  PARITY UNPINNED.
+// ORACLE — TEST INFRASTRUCTURE ONLY (see orc_math.h header).  PINNED to the reference's own functors: lidarFactor.hpp and
+// ceres_cost_function.h are compiled unmodified (oracle/ref_harness.cpp, stand-in Eigen / Ceres Jet in oracle/ref_shim/) and compared with
+// these restatements, residuals and Jacobians, in tests/test_ref_factors.py.  Eigen's and Ceres' own arithmetic behind them stays a stand-in.
 //
 // The reference's Ceres cost functors, restated with the oracle's own tiny vector / quaternion
 // templates (Eigen is not available).  Same operator() contract:

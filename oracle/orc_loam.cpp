@@ -1,4 +1,6 @@
-// ORACLE — TEST INFRASTRUCTURE ONLY (see orc_math.h header).  PARITY UNPINNED.
+// ORACLE — TEST INFRASTRUCTURE ONLY (see orc_math.h header).  scan_registration() below is PINNED to the reference's own
+// scan_registration.cpp, compiled unmodified (oracle/ref_harness.cpp; tests/test_ref_scan_registration.py: bit for bit); LaserOdometry and
+// LaserMapping stay UNPINNED restatements.
 // Line references are into /root/reference/src/lidar_odometry_mapping/.
 #include "orc_loam.h"
 #include <chrono>
@@ -11,8 +13,12 @@ static const double kEps = std::numeric_limits<double>::epsilon();
 
 // ====================================================================== ScanRegistration
 // src/scan_registration.cpp:131-449.  Float/double promotion follows the C++ expressions there,
-// with the float overloads of atan/sqrt/atan2 (the TU pulls in <math.h> via ROS/OpenCV headers and
-// `using std::atan2`, scan_registration.h:57-59).
+// with the float overloads of atan/sqrt/atan2: the TU pulls in <math.h> through tf/LinearMath/Scalar.h (scan_registration.h:47-48), which
+// brings the float overloads into the global namespace, and `using std::atan2` (scan_registration.h:58).  No longer an assumption: the
+// compiler's answer is read back from the reference build (ref_math_overloads_are_float, tests/test_ref_scan_registration.py), and the
+// <cmath>-only counter-factual is built and sized next to it.
+// One flag of the reference has no counterpart here: removeNaNFromPointCloud copies a cloud flagged is_dense without looking at it (:157);
+// the C ABI carries no such flag and non-finite points are always removed (stated deviation).
 bool scan_registration(const float* in, int n, const Config& cfg, ScanRegistrationResult* out) {
   *out = ScanRegistrationResult();
   const int N_SCANS = cfg.scan_line;

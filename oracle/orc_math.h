@@ -1,7 +1,9 @@
 // ORACLE — TEST INFRASTRUCTURE ONLY. Not shipped, not linked into libvloam_hip.so.
 // Only tests/, __graft_entry__.smoke() and bench.py's cpu_baseline leg may use it.
 //
-// PARITY UNPINNED: the reference (YukunXia/VLOAM-CMU-16833) has no tests and its
+// PARITY: scan registration and the eight cost functors are pinned to the reference's own text (compiled unmodified against the
+// stand-in headers of ref_shim/: ref_harness.cpp, tests/test_ref_*.py).  Everything else is UNPINNED: the reference
+// (YukunXia/VLOAM-CMU-16833) has no tests and its
 // arithmetic lives in Eigen 3.3 / Ceres 2.0 / PCL 1.10 / FLANN 1.9, none of which
 // exist in this image.  This header restates the handful of Eigen operations the
 // hot path uses, following the *published* Eigen 3.3 algorithms named per function.

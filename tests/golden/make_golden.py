@@ -1,8 +1,8 @@
 #!/usr/bin/env python3
-"""Generate tests/golden/*.npz from the CPU oracle (run in the dev container: `python tests/golden/make_golden.py`).
+"""Generate tests/golden/*.npz (run in the dev container: `python tests/golden/make_golden.py`; `... make_golden.py ref` for ref_sr_* only).
 
-The reference has no tests and no golden vectors and cannot be built or imported here, so these
-fixtures pin the ORACLE's outputs (regression vectors): the CPU tests check the oracle still reproduces them,
+ref_sr_*.npz are outputs of the reference's own scan_registration.cpp (see run_ref_sr_cases).  The reference has no tests and no golden
+vectors and the rest of it cannot be built here, so the other fixtures pin the ORACLE's outputs (regression vectors): the CPU tests check the oracle still reproduces them,
 the GPU tests check the HIP path reproduces them.  Inputs are stored too (the small case), so nothing depends
 on numpy's random stream staying stable.
 """
@@ -113,7 +113,38 @@ def run_image_case(w, h, n_images, seed):
     return out
 
 
+def run_ref_sr_cases():
+    """tests/golden/ref_sr_<case>.npz: outputs of the REFERENCE'S OWN scan_registration.cpp (oracle/_ref/libref.so, built from the reference
+    checkout by `make -C oracle ref`) for the small cases of tests/ref_cases.py — recorded results of the reference's program, not of the
+    oracle.  Layout and the loader: ref_cases.pack_golden / ref_cases.load_golden."""
+    import ref
+    import ref_cases
+    out = {}
+    for name, (scan_line, minimum_range, sweeps) in sorted(ref_cases.small_cases().items()):
+        lit = ref.ScanRegistration(scan_line, minimum_range, voxel_stable=False)
+        can = ref.ScanRegistration(scan_line, minimum_range, voxel_stable=True)
+        results = []
+        for c in sweeps:
+            assert lit.run(c) == 0 and can.run(c) == 0
+            results.append((lit.clouds(), can.cloud(4)))
+        out[name] = ref_cases.pack_golden(scan_line, minimum_range, sweeps, results)
+    return out
+
+
+def write_ref_sr_cases():
+    for name, d in run_ref_sr_cases().items():
+        np.savez_compressed(os.path.join(HERE, "ref_sr_%s.npz" % name), **d)
+
+
 if __name__ == "__main__":
+    if len(sys.argv) > 1 and sys.argv[1] == "ref":   # only the reference recordings (needs the reference checkout or a built oracle/_ref/)
+        write_ref_sr_cases()
+        sys.exit(0)
+    import ref
+    if ref.available():
+        write_ref_sr_cases()
+    else:
+        print("ref_sr_*.npz left as they are:", ref.SKIP_REASON)
     np.savez_compressed(os.path.join(HERE, "image_320x96_3frames.npz"), **run_image_case(320, 96, 3, seed=21))
     vl4 = run_vloam_case(64, 256, 5)
     np.savez_compressed(os.path.join(HERE, "vloam_64x256_5frames.npz"), **vl4)
