@@ -18,7 +18,7 @@ import numpy as np
 _DIR = os.path.dirname(os.path.abspath(__file__))
 REF_OUT = os.path.join(_DIR, "_ref")
 REFERENCE_DIR_DEFAULT = "/root/reference"   # outside the repository: see the module docstring
-VARIANTS = ("libref.so", "libref_cmath_only.so")
+VARIANTS = ("libref.so", "libref_cmath_only.so", "libref_loam.so")
 
 
 def reference_dir():
@@ -124,3 +124,153 @@ def eval_factor(ftype, payload, p0, p1, long_double=False):
            J.ctypes.data_as(C.c_void_p))
     assert n == nres
     return r[:n].copy(), J.reshape(-1)[:n * (n0 + 3)].reshape(n, n0 + 3).copy()
+
+
+# ---------------------------------------------------------------- laser odometry and mapping (oracle/_ref/libref_loam.so, ref_loam_harness.cpp)
+LOAM_LIB = "libref_loam.so"
+U32 = C.c_uint
+_P = C.c_void_p
+
+
+def loam_lib():
+    if LOAM_LIB not in _libs:
+        if build() is None or not os.path.exists(os.path.join(REF_OUT, LOAM_LIB)):
+            raise RuntimeError(SKIP_REASON)
+        L = C.CDLL(os.path.join(REF_OUT, LOAM_LIB))
+        L.ref_loam_create.restype = _P
+        L.ref_loam_create.argtypes = [I, D, D, D, I, I]
+        L.ref_loam_destroy.argtypes = [_P]
+        L.ref_loam_set_vo_prior.argtypes = [_P] * 5
+        L.ref_loam_stage_sr.argtypes = [_P, _P, I]
+        L.ref_loam_set_sr_cloud.argtypes = [_P, I, _P, I]
+        L.ref_loam_set_map_cloud.argtypes = [_P, I, _P, I]
+        L.ref_loam_stage_lo.argtypes = [_P]
+        L.ref_loam_stage_map.argtypes = [_P, _P, _P]
+        L.ref_loam_skip_frame.argtypes = [_P]
+        L.ref_loam_get_cloud.argtypes = [_P, I, _P, I]
+        L.ref_loam_get_map_cube_counts.argtypes = [_P, _P, I]
+        L.ref_loam_get_lo_pose.argtypes = [_P, _P, _P]
+        L.ref_loam_get_published_pose.argtypes = [_P, I, _P, _P]
+        L.ref_loam_get_tf.argtypes = [_P, I, _P, _P]
+        L.ref_loam_map_ran.argtypes = [_P]
+        L.ref_loam_get_map_filter_log.argtypes = [_P, _P, I]
+        L.ref_loam_num_solves.argtypes = [_P, I]
+        L.ref_loam_get_solve.argtypes = [_P, I, I, _P, _P, _P]
+        L.ref_loam_get_solve_blocks.argtypes = [_P, I, I, _P, _P, _P, _P]
+        _libs[LOAM_LIB] = L
+    return _libs[LOAM_LIB]
+
+
+def _vp(a):
+    return a.ctypes.data_as(_P)
+
+
+class Loam:
+    """The reference's ScanRegistration, LaserOdometry and LaserMapping objects chained as its façade chains them; mirrors orc.Oracle's
+    stage calls.  Sessions may coexist: each keeps its own copies of what it published and observed (the stand-in parameter server is
+    process-wide, but it is only read while a session is being created).  Not thread-safe."""
+    ODOMETRY, MAPPING = 0, 1
+    N_CUBES = 21 * 21 * 11
+
+    def __init__(self, scan_line=64, minimum_range=5.0, line_res=0.4, plane_res=0.8, mapping_skip_frame=1, detach_vo_lo=True, voxel_stable=True):
+        self.L = loam_lib()
+        self.voxel_stable = voxel_stable
+        self.h = _P(self.L.ref_loam_create(scan_line, minimum_range, float(np.float32(line_res)), float(np.float32(plane_res)), mapping_skip_frame, int(detach_vo_lo)))
+
+    def __del__(self):
+        try:
+            self.L.ref_loam_destroy(self.h)
+        except Exception:
+            pass
+
+    def set_vo_prior(self, q, t):
+        """Stores velo_last_VOT_velo_curr; returns (q, t) as the reference will read them back out of the tf2 transform."""
+        q = np.ascontiguousarray(q, dtype=np.float64)
+        t = np.ascontiguousarray(t, dtype=np.float64)
+        qb, tb = np.zeros(4), np.zeros(3)
+        self.L.ref_loam_set_vo_prior(self.h, _vp(q), _vp(t), _vp(qb), _vp(tb))
+        return qb, tb
+
+    def stage_sr(self, cloud):
+        c = np.ascontiguousarray(cloud, dtype=np.float32)
+        self.L.ref_set_voxel_stable_order(int(self.voxel_stable))
+        return self.L.ref_loam_stage_sr(self.h, _vp(c), c.shape[0])
+
+    def set_sr_cloud(self, which, pts):
+        c = np.ascontiguousarray(pts, dtype=np.float32).reshape(-1, 4)
+        assert self.L.ref_loam_set_sr_cloud(self.h, which, _vp(c), c.shape[0]) == 0
+
+    def stage_lo(self):
+        self.L.ref_set_voxel_stable_order(int(self.voxel_stable))
+        return self.L.ref_loam_stage_lo(self.h)
+
+    def stage_map(self, corner=None, surf=None, full=None, q=None, t=None):
+        self.L.ref_set_voxel_stable_order(int(self.voxel_stable))
+        for which, a in ((5, corner), (6, surf), (7, full)):
+            if a is not None:
+                c = np.ascontiguousarray(a, dtype=np.float32).reshape(-1, 4)
+                assert self.L.ref_loam_set_map_cloud(self.h, which, _vp(c), c.shape[0]) == 0
+        qa = None if q is None else np.ascontiguousarray(q, dtype=np.float64)
+        ta = None if t is None else np.ascontiguousarray(t, dtype=np.float64)
+        return self.L.ref_loam_stage_map(self.h, None if qa is None else _vp(qa), None if ta is None else _vp(ta))
+
+    def skip_frame(self):
+        return bool(self.L.ref_loam_skip_frame(self.h))
+
+    def cloud(self, which):
+        """0-4 scan registration; 5 / 6 / 7 the hand-over of output(); 8 /laser_cloud_map; 9 /velodyne_cloud_registered (None before the first)."""
+        n = self.L.ref_loam_get_cloud(self.h, which, None, 0)
+        if n < 0:
+            return None
+        buf = np.zeros((max(n, 1), 4), dtype=np.float32)
+        self.L.ref_loam_get_cloud(self.h, which, _vp(buf), n)
+        return buf[:n]
+
+    def map_cube_counts(self):
+        """[2, 4851] points per cube of the last published map: row 0 corner, row 1 surface."""
+        buf = np.zeros(2 * self.N_CUBES, dtype=np.uint32)
+        n = self.L.ref_loam_get_map_cube_counts(self.h, _vp(buf), buf.shape[0])
+        assert n == 2 * self.N_CUBES, n
+        return buf.reshape(self.N_CUBES, 2).T.astype(np.int64)
+
+    def lo_pose(self):
+        q, t = np.zeros(4), np.zeros(3)
+        self.L.ref_loam_get_lo_pose(self.h, _vp(q), _vp(t))
+        return q, t
+
+    def published_pose(self, topic):
+        q, t = np.zeros(4), np.zeros(3)
+        assert self.L.ref_loam_get_published_pose(self.h, topic, _vp(q), _vp(t)) == 0
+        return q, t
+
+    def tf(self, which):
+        """0 base_prev_LOT_base_curr, 1 world_LOT_base_last, 2 world_MOT_base_last of VloamTF, rotation as tf2 returns it."""
+        q, t = np.zeros(4), np.zeros(3)
+        self.L.ref_loam_get_tf(self.h, which, _vp(q), _vp(t))
+        return q, t
+
+    def map_ran(self):
+        return bool(self.L.ref_loam_map_ran(self.h))
+
+    def map_filter_log(self):
+        n = self.L.ref_loam_get_map_filter_log(self.h, None, 0)
+        buf = np.zeros((max(n, 1), 2), dtype=np.int32)
+        self.L.ref_loam_get_map_filter_log(self.h, _vp(buf), n)
+        return buf[:n]
+
+    def num_solves(self, stage):
+        return self.L.ref_loam_num_solves(self.h, stage)
+
+    def solve(self, stage, k):
+        """One ceres::Solve of the last stage call: q_in / t_in / q_out / t_out, max_num_iterations, types [blocks] (0 LidarEdgeFactor,
+        1 LidarPlaneFactor, 2 LidarPlaneNormFactor, 3 LidarDistanceFactor), nres [blocks], payload [blocks, 13] (the functor's members in
+        declaration order), residuals0 (raw, at the initial point, in AddResidualBlock order)."""
+        b, a = np.zeros(7), np.zeros(7)
+        cnt = np.zeros(3, dtype=np.int32)
+        assert self.L.ref_loam_get_solve(self.h, stage, k, _vp(b), _vp(a), _vp(cnt)) == 0
+        nb, nr = int(cnt[0]), int(cnt[1])
+        types, nres = np.zeros(max(nb, 1), dtype=np.int32), np.zeros(max(nb, 1), dtype=np.int32)
+        payload, raw = np.zeros((max(nb, 1), 13)), np.zeros(max(nr, 1))
+        assert self.L.ref_loam_get_solve_blocks(self.h, stage, k, _vp(types), _vp(nres), _vp(payload), _vp(raw)) == 0
+        return dict(q_in=b[:4], t_in=b[4:], q_out=a[:4], t_out=a[4:], max_num_iterations=int(cnt[2]), types=types[:nb], nres=nres[:nb],
+                    payload=payload[:nb], residuals0=raw[:nr])

@@ -15,6 +15,7 @@
 #include <cmath>
 #include <cstdint>
 #include <limits>
+#include <utility>
 #include <vector>
 #include <pcl/filters/filter.h>
 #include <pcl/point_cloud.h>
@@ -23,6 +24,13 @@
 namespace pcl {
 namespace refshim {
 inline bool& voxel_stable_order() { static bool v = false; return v; }
+// observation only: (points in, points out) of every filter() call since the harness last cleared it — the first two calls of
+// LaserMapping::solveMapping (laser_mapping.cpp:432-440) are the corner and the surface stack, which live in locals there
+// (opt-in: nothing is logged unless filter_log_on() is set — the harness sets it around LaserMapping::solveMapping only)
+inline bool& filter_log_on() { static bool v = false; return v; }
+inline void log_filter(int in, int out);
+inline std::vector<std::pair<int, int>>& filter_log() { static std::vector<std::pair<int, int>> v; return v; }
+inline void log_filter(int in, int out) { if (filter_log_on()) filter_log().push_back({in, out}); }
 }  // namespace refshim
 
 template <class PointT>
@@ -39,7 +47,7 @@ class VoxelGrid {
     out.height = 1;
     out.is_dense = true;
     const std::vector<PointT>& in = input_->points;
-    if (in.empty()) { out.width = 0; return; }
+    if (in.empty()) { out.width = 0; refshim::log_filter(0, 0); return; }
     float lo[3], hi[3];
     for (int a = 0; a < 3; a++) { lo[a] = std::numeric_limits<float>::max(); hi[a] = -std::numeric_limits<float>::max(); }
     for (const PointT& p : in) {
@@ -51,6 +59,7 @@ class VoxelGrid {
     for (int a = 0; a < 3; a++) cells *= static_cast<std::int64_t>((hi[a] - lo[a]) * inv_[a]) + 1;
     if (cells > static_cast<std::int64_t>(std::numeric_limits<std::int32_t>::max())) {  // PCL warns and returns the input
       out = *input_;
+      refshim::log_filter(static_cast<int>(in.size()), static_cast<int>(out.points.size()));
       return;
     }
     int bmin[3], bdiv[3];
@@ -88,6 +97,7 @@ class VoxelGrid {
       first = last;
     }
     out.width = static_cast<std::uint32_t>(out.points.size());
+    refshim::log_filter(static_cast<int>(in.size()), static_cast<int>(out.points.size()));
   }
 
  private:

@@ -2,12 +2,14 @@
 // roscpp, reduced to what the reference's classes touch:
 //  * ros::param::get(name, value) — the parameter server is a map the harness fills (ros::param::shim_store()); like roscpp it returns
 //    false and leaves `value` untouched when the name is unknown, and converts a stored number to the requested type;
-//  * NodeHandle / Publisher / Time — no-ops (nothing is published; the harness reads the objects' outputs directly);
+//  * NodeHandle / Publisher — advertise(topic) hands out a Publisher bound to the topic; publish(msg) keeps a copy of the LAST message per
+//    topic in ros::shim_topics(), where the harness reads it back (ros::shim_last<M>(topic)); Time — always zero;
 //  * ROS_INFO / ROS_WARN / ROS_ERROR / ROS_DEBUG — no-ops; ROS_BREAK — aborts, as ros/assert.h does.
 // No math header is included and no math function is declared here on purpose: see tf/LinearMath/Scalar.h.
 #pragma once
 #include <cstdlib>
 #include <map>
+#include <memory>
 #include <string>
 
 namespace ros {
@@ -46,9 +48,21 @@ struct Time {
   double toSec() const { return sec; }
 };
 
+inline std::map<std::string, std::shared_ptr<const void>>& shim_topics() { static std::map<std::string, std::shared_ptr<const void>> m; return m; }
+// the last message published on `topic`, or null; M must be the type that was published there
+template <class M> inline const M* shim_last(const std::string& topic) {
+  auto it = shim_topics().find(topic);
+  return it == shim_topics().end() ? nullptr : static_cast<const M*>(it->second.get());
+}
+
 class Publisher {
  public:
-  template <class M> void publish(const M&) const {}
+  Publisher() {}
+  explicit Publisher(const std::string& topic) : topic_(topic) {}
+  template <class M> void publish(const M& m) const { shim_topics()[topic_] = std::make_shared<const M>(m); }
+
+ private:
+  std::string topic_;
 };
 
 class Subscriber {};
@@ -57,7 +71,7 @@ class NodeHandle {
  public:
   NodeHandle() {}
   explicit NodeHandle(const std::string&) {}
-  template <class M> Publisher advertise(const std::string&, unsigned) { return Publisher(); }
+  template <class M> Publisher advertise(const std::string& topic, unsigned) { return Publisher(topic); }
 };
 
 }  // namespace ros

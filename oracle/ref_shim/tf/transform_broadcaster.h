@@ -1,8 +1,11 @@
 // REFERENCE-BUILD STAND-IN — TEST INFRASTRUCTURE ONLY (our own text).
-// tf/transform_broadcaster.h: unused by scan registration; includes what the real header includes first (see tf/LinearMath/Scalar.h).
+// tf/transform_broadcaster.h: includes what the real header includes first (see tf/LinearMath/Scalar.h); sendTransform sends nothing.
 #pragma once
 #include <tf/transform_datatypes.h>
 
 namespace tf {
-class TransformBroadcaster {};
+class TransformBroadcaster {
+ public:
+  void sendTransform(const StampedTransform&) {}
+};
 }  // namespace tf

@@ -1,0 +1,121 @@
+// REFERENCE-BUILD STAND-IN — TEST INFRASTRUCTURE ONLY (our own text; functional).
+//
+// tf2::Vector3 / Quaternion / Matrix3x3 / Transform as laser_odometry.cpp:225-232, :563-571 and laser_mapping.cpp:728-755 use them
+// through the reference's own vloam_tf.h.  Restated from geometry2 (ROS Noetic) tf2/LinearMath/{Matrix3x3,Transform}.h: a Transform is a
+// 3 x 3 basis plus an origin, so setRotation() stores a MATRIX (s = 2 / |q|^2; 1 - (yy + zz), xy - wz, ... ) and getRotation() extracts a
+// quaternion from it again (trace > 0: s = sqrt(trace + 1), w = s / 2, the off-diagonal differences times 0.5 / s; otherwise the
+// largest diagonal element leads) — what the reference reads back from velo_last_VOT_velo_curr is therefore NOT bit for bit what was
+// stored, and the harness hands the oracle the read-back values.  inverse() = (basis^T, basis^T * -origin); a * b = (basis_a basis_b,
+// basis_a origin_b + origin_a).  Unlike tf2, a default-constructed Transform is the identity rather than uninitialised memory.
+#pragma once
+#include <cmath>
+
+namespace tf2 {
+
+class Vector3 {
+ public:
+  Vector3() : v_{0, 0, 0} {}
+  Vector3(double x, double y, double z) : v_{x, y, z} {}
+  double x() const { return v_[0]; }
+  double y() const { return v_[1]; }
+  double z() const { return v_[2]; }
+  double dot(const Vector3& o) const { return v_[0] * o.v_[0] + v_[1] * o.v_[1] + v_[2] * o.v_[2]; }
+  Vector3 operator-() const { return Vector3(-v_[0], -v_[1], -v_[2]); }
+  Vector3 operator+(const Vector3& o) const { return Vector3(v_[0] + o.v_[0], v_[1] + o.v_[1], v_[2] + o.v_[2]); }
+  double operator[](int i) const { return v_[i]; }
+
+ private:
+  double v_[3];
+};
+
+class Quaternion {
+ public:
+  Quaternion() : q_{0, 0, 0, 1} {}
+  Quaternion(double x, double y, double z, double w) : q_{x, y, z, w} {}
+  double x() const { return q_[0]; }
+  double y() const { return q_[1]; }
+  double z() const { return q_[2]; }
+  double w() const { return q_[3]; }
+  double length2() const { return q_[0] * q_[0] + q_[1] * q_[1] + q_[2] * q_[2] + q_[3] * q_[3]; }
+
+ private:
+  double q_[4];
+};
+
+class Matrix3x3 {
+ public:
+  Matrix3x3() { setIdentity(); }
+  void setIdentity() { r_[0] = Vector3(1, 0, 0); r_[1] = Vector3(0, 1, 0); r_[2] = Vector3(0, 0, 1); }
+  void setValue(double xx, double xy, double xz, double yx, double yy, double yz, double zx, double zy, double zz) {
+    r_[0] = Vector3(xx, xy, xz); r_[1] = Vector3(yx, yy, yz); r_[2] = Vector3(zx, zy, zz);
+  }
+  void setRotation(const Quaternion& q) {
+    double d = q.length2();
+    double s = 2.0 / d;
+    double xs = q.x() * s, ys = q.y() * s, zs = q.z() * s;
+    double wx = q.w() * xs, wy = q.w() * ys, wz = q.w() * zs;
+    double xx = q.x() * xs, xy = q.x() * ys, xz = q.x() * zs;
+    double yy = q.y() * ys, yz = q.y() * zs, zz = q.z() * zs;
+    setValue(1.0 - (yy + zz), xy - wz, xz + wy, xy + wz, 1.0 - (xx + zz), yz - wx, xz - wy, yz + wx, 1.0 - (xx + yy));
+  }
+  void getRotation(Quaternion& q) const {
+    double trace = r_[0].x() + r_[1].y() + r_[2].z();
+    double temp[4];
+    if (trace > 0.0) {
+      double s = std::sqrt(trace + 1.0);
+      temp[3] = s * 0.5;
+      s = 0.5 / s;
+      temp[0] = (r_[2].y() - r_[1].z()) * s;
+      temp[1] = (r_[0].z() - r_[2].x()) * s;
+      temp[2] = (r_[1].x() - r_[0].y()) * s;
+    } else {
+      int i = r_[0].x() < r_[1].y() ? (r_[1].y() < r_[2].z() ? 2 : 1) : (r_[0].x() < r_[2].z() ? 2 : 0);
+      int j = (i + 1) % 3;
+      int k = (i + 2) % 3;
+      double s = std::sqrt(r_[i][i] - r_[j][j] - r_[k][k] + 1.0);
+      temp[i] = s * 0.5;
+      s = 0.5 / s;
+      temp[3] = (r_[k][j] - r_[j][k]) * s;
+      temp[j] = (r_[j][i] + r_[i][j]) * s;
+      temp[k] = (r_[k][i] + r_[i][k]) * s;
+    }
+    q = Quaternion(temp[0], temp[1], temp[2], temp[3]);
+  }
+  const Vector3& operator[](int i) const { return r_[i]; }
+  Matrix3x3 transpose() const {
+    Matrix3x3 m;
+    m.setValue(r_[0].x(), r_[1].x(), r_[2].x(), r_[0].y(), r_[1].y(), r_[2].y(), r_[0].z(), r_[1].z(), r_[2].z());
+    return m;
+  }
+  Vector3 operator*(const Vector3& v) const { return Vector3(r_[0].dot(v), r_[1].dot(v), r_[2].dot(v)); }
+  Matrix3x3 operator*(const Matrix3x3& o) const {
+    Matrix3x3 t = o.transpose(), m;
+    m.setValue(r_[0].dot(t[0]), r_[0].dot(t[1]), r_[0].dot(t[2]), r_[1].dot(t[0]), r_[1].dot(t[1]), r_[1].dot(t[2]), r_[2].dot(t[0]),
+               r_[2].dot(t[1]), r_[2].dot(t[2]));
+    return m;
+  }
+
+ private:
+  Vector3 r_[3];
+};
+
+class Transform {
+ public:
+  Transform() {}
+  Transform(const Matrix3x3& b, const Vector3& o) : basis_(b), origin_(o) {}
+  void setIdentity() { basis_.setIdentity(); origin_ = Vector3(0, 0, 0); }
+  void setOrigin(const Vector3& o) { origin_ = o; }
+  void setRotation(const Quaternion& q) { basis_.setRotation(q); }
+  const Vector3& getOrigin() const { return origin_; }
+  Quaternion getRotation() const { Quaternion q; basis_.getRotation(q); return q; }
+  const Matrix3x3& getBasis() const { return basis_; }
+  Vector3 operator()(const Vector3& x) const { return basis_ * x + origin_; }
+  Transform inverse() const { Matrix3x3 inv = basis_.transpose(); return Transform(inv, inv * -origin_); }
+  Transform operator*(const Transform& t) const { return Transform(basis_ * t.basis_, (*this)(t.origin_)); }
+
+ private:
+  Matrix3x3 basis_;
+  Vector3 origin_;
+};
+
+}  // namespace tf2

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Generate tests/golden/*.npz (run in the dev container: `python tests/golden/make_golden.py`; `... make_golden.py ref` for ref_sr_* only).
+"""Generate tests/golden/*.npz (run in the dev container: `python tests/golden/make_golden.py`; `... make_golden.py ref` for ref_sr_* / ref_lo_* / ref_map_* only).
 
 ref_sr_*.npz are outputs of the reference's own scan_registration.cpp (see run_ref_sr_cases).  The reference has no tests and no golden
 vectors and the rest of it cannot be built here, so the other fixtures pin the ORACLE's outputs (regression vectors): the CPU tests check the oracle still reproduces them,
@@ -131,9 +131,20 @@ def run_ref_sr_cases():
     return out
 
 
+def run_ref_loam_cases():
+    """tests/golden/ref_lo_<case>.npz / ref_map_<case>.npz: what the REFERENCE'S OWN laser_odometry.cpp / laser_mapping.cpp computed
+    (oracle/_ref/libref_loam.so) for the small sequences of ref_cases.loam_golden_cases — data only; layout: ref_cases.record_loam."""
+    import ref
+    import ref_cases
+    return {stem: ref_cases.record_loam(ref, params, sweeps, priors, with_mapping)
+            for stem, (params, sweeps, priors, with_mapping) in sorted(ref_cases.loam_golden_cases().items())}
+
+
 def write_ref_sr_cases():
     for name, d in run_ref_sr_cases().items():
         np.savez_compressed(os.path.join(HERE, "ref_sr_%s.npz" % name), **d)
+    for stem, d in run_ref_loam_cases().items():
+        np.savez_compressed(os.path.join(HERE, stem + ".npz"), **d)
 
 
 if __name__ == "__main__":

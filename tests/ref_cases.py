@@ -175,6 +175,21 @@ def fuzz_cloud(rings, n_az, seed):
     return test_gpu_fuzz.random_cloud(conftest.load_synth(), rings, n_az, seed)
 
 
+def long_ring_sweep(n_long=16384, seed=23):
+    """A scan line of exactly n_long returns (the top of the opt-in long ring tier, max_ring_points = 16 384) next to two ordinary scan
+    lines of 256, in firing order by azimuth, one turn."""
+    rng = np.random.default_rng(seed)
+    parts = []
+    for el, n in ((-10.43, n_long), (-3.0, 256), (-15.08, 256)):
+        az = -2.0 * np.pi * (np.arange(n) + rng.uniform(-0.3, 0.3, n)) / n
+        rad = 20.0 + 3.0 * np.sin(3 * az) + 0.02 * rng.standard_normal(n)
+        rad[(np.arange(n) * 64 // n) % 2 == 1] += 1.0      # range steps: corner candidates
+        parts.append((az, _polar(rad, el, az)))
+    az = np.concatenate([a for a, _ in parts])
+    pts = np.concatenate([p for _, p in parts])
+    return np.ascontiguousarray(pts[np.argsort(-az, kind="stable")])
+
+
 FUZZ = [(64, 600, 103), (32, 1500, 105), (16, 257, 107), (64, 2048, 927), (16, 1800, 908), (32, 2000, 945), (64, 1500, 940), (64, 2000, 1013), (16, 1900, 1014)]
 
 
@@ -192,6 +207,7 @@ def small_cases():
         "filters": (64, 5.0, [range_and_nan_sweep(5.0)]),
         "start_a": (64, 5.0, start_sweeps()[:6]),
         "start_b": (64, 5.0, start_sweeps()[6:]),
+        "ring16384": (64, 5.0, [long_ring_sweep()]),       # handles need max_ring_points = 16384 for it (longest_ring)
     }
     return cases
 
@@ -231,6 +247,12 @@ def pack_golden(scan_line, minimum_range, sweeps, results):
     return d
 
 
+def longest_ring(clouds):
+    """Points of the fullest scan line of a recorded laserCloud: what a handle's max_ring_points has to cover."""
+    full = clouds[0]
+    return int(np.bincount(full[:, 3].astype(np.int64)).max()) if full.shape[0] else 0
+
+
 def load_golden(path):
     """(scan_line, minimum_range, [input sweep [n, 4]], [(five clouds, canonical surfPointsLessFlat)]) of one ref_sr_*.npz."""
     z = np.load(path)
@@ -246,3 +268,189 @@ def load_golden(path):
         sweeps.append(c)
         results.append((clouds, z["s%d_c4_canonical" % k]))
     return int(z["scan_line"]), float(z["minimum_range"]), sweeps, results
+
+
+# ---------------------------------------------------------------- sequences for laser odometry and mapping (tests/test_ref_laser_*.py)
+def synth_sequence(n_rings, n_az, n, sensor="default", **kw):
+    synth = conftest.load_synth()
+    args = dict(n_rings=n_rings, n_sweeps=n + 1, sensor=sensor)
+    if n_az is not None:
+        args["n_azimuth"] = n_az
+    args.update(kw)
+    seq = synth.SynthSequence(**args)
+    return [np.ascontiguousarray(seq.sweep(k), dtype=_F) for k in range(n)]
+
+
+def moving_fuzz_sequence(rings, n_az, seed, n=4, step=0.3):
+    """One random range image of the fuzz generator seen from a sensor that advances `step` metres per sweep along x: ragged rings,
+    dropouts and repeats, with real scan-to-scan correspondences."""
+    base = fuzz_cloud(rings, n_az, seed)
+    out = []
+    for k in range(n):
+        c = base.copy()
+        c[:, 0] -= _F(step * k)
+        out.append(c)
+    return out
+
+
+def nearby_scan_clouds():
+    """(corner tree, surf tree, sharp query, flat query, expected corner triple, expected plane quadruple): candidates exactly 2 and 3 scan
+    lines above the closest point, the one 3 lines away NEARER — `> closestPointScanID + NEARBY_SCAN` (2.5) ends the walk before it
+    (laser_odometry.cpp:286, :371), so the point 2 lines away is paired; a bound of 3.5 would pair the other, 1.5 none.  Below the closest
+    point the same two distances are occupied by farther points, so the upward side decides."""
+    def P(x, y, z, ring):
+        return [x, y, z, ring]
+    corner = np.array([P(10, 0, -0.9, 7), P(10, 0, -1.2, 8), P(10, 0, 0, 10), P(10, 0, 1.0, 12), P(10, 0, 0.5, 13)], _F)
+    surf = np.array([P(11, 0, -0.9, 7), P(11, 0, -1.2, 8), P(10, 0, 0, 10), P(10, 1, 0, 10), P(11, 0, 1.0, 12), P(11, 0, 0.5, 13)], _F)
+    sharp = np.array([P(10, 0.01, 0, 10)], _F)
+    flat = np.array([P(10, 0.3, 0.01, 10)], _F)
+    return corner, surf, sharp, flat, (0, 2, 3), (0, 2, 3, 4)
+
+
+def vo_priors(n, seed=4):
+    """A non-trivial velo_last_VOT_velo_curr per sweep: a few centimetres and milliradians off the true motion's scale."""
+    rng = np.random.default_rng(seed)
+    out = []
+    for _ in range(n):
+        v = rng.normal(0, 0.01, 3)
+        q = np.array([v[0], v[1], v[2], 1.0])
+        out.append((q / np.linalg.norm(q), np.array([0.4, 0.0, 0.0]) + rng.normal(0, 0.05, 3)))
+    return out
+
+
+def loam_sequences():
+    """{name: (parameters of the session, sweeps, what to hand LaserMapping::input instead of the odometry pose or None, VO priors or None)}"""
+    import branch_cases
+    import degenerate_cases
+    import test_gpu_launch_configs as lc
+    synth = conftest.load_synth()
+    cases = {
+        "64x256": (dict(), synth_sequence(64, 256, 8), None, None),
+        "64x512": (dict(), synth_sequence(64, 512, 6), None, None),
+        "64x2048": (dict(), synth_sequence(64, 2048, 3), None, None),
+        "hdl64e": (dict(), synth_sequence(64, None, 3, sensor="hdl64e"), None, None),
+        "fuzz": (dict(), moving_fuzz_sequence(64, 600, 103), None, None),
+        "no_correspondence": (dict(), degenerate_cases.lo_sequence(synth, n=6, far_at=(3,)), None, None),
+        "fewer_than_ten": (dict(), degenerate_cases.lo_sequence(synth, n=6, far_at=(), wedge_at=(3,)), None, None),
+        "small_map": (dict(scan_line=16), degenerate_cases.sparse_map_sequence(synth, n=6), None, None),
+        "skip2": (dict(mapping_skip_frame=2), synth_sequence(64, 256, 7), None, None),
+        "skip5": (dict(mapping_skip_frame=5), synth_sequence(64, 256, 11), None, None),
+        "ground_only": (dict(), branch_cases.ground_only_sequence(synth, n=5), None, None),
+        "repeated_sweep": (dict(), branch_cases.repeated_sweep_sequence(synth, n=5), None, None),
+        "vo_prior": (dict(detach_vo_lo=False), synth_sequence(64, 256, 6), None, vo_priors(6)),
+        "vo_prior_skip2": (dict(detach_vo_lo=False, mapping_skip_frame=2), synth_sequence(64, 256, 6), None, vo_priors(6, seed=8)),
+    }
+    for name, (rings, az, p) in lc.LAUNCH.items():
+        cases[name] = (dict(scan_line=rings, minimum_range=p["minimum_range"], line_res=p["mapping_line_resolution"], plane_res=p["mapping_plane_resolution"],
+                            mapping_skip_frame=p["mapping_skip_frame"]), lc.sequence(synth, name, 4, 2.0), None, None)
+    # a full turn on the spot-ish: the drive of 64 x 256 with the sensor yawed 0.11 rad more every sweep (tests/test_gpu_turns.py), 60 sweeps = 6.6 rad
+    import test_gpu_turns
+    cases["full_turn"] = (dict(), [test_gpu_turns.spun(c, 0.11 * k) for k, c in enumerate(synth_sequence(64, 256, 60))], None, None)
+    walk = branch_cases.six_way_walk()
+    cases["six_way_walk"] = (dict(), synth_sequence(64, 256, len(walk) - 1 + 1)[:len(walk)], walk, None)
+    return cases
+
+
+# ---------------------------------------------------------------- committed recordings of laser odometry / mapping (tests/golden/ref_lo_*.npz, ref_map_*.npz)
+def loam_golden_cases():
+    """{file stem: (session parameters, sweeps, VO priors or None, with mapping)} — small on purpose: each file holds its input sweeps."""
+    return {
+        "ref_lo_64x128": (dict(), synth_sequence(64, 128, 3), None, False),
+        "ref_lo_16x256_prior_skip2": (dict(scan_line=16, detach_vo_lo=False, mapping_skip_frame=2), synth_sequence(16, 256, 5), vo_priors(5, seed=11), False),
+        "ref_map_16x256": (dict(scan_line=16), synth_sequence(16, 256, 5), None, True),
+        "ref_map_64x128": (dict(), synth_sequence(64, 128, 3), None, True),
+        "ref_map_16x256_skip2": (dict(scan_line=16, mapping_skip_frame=2), synth_sequence(16, 256, 6), None, True),
+    }
+
+
+def _unique_index(points_f64, table, what):
+    key = {}
+    for i, r in enumerate(np.ascontiguousarray(table[:, :3])):
+        assert r.tobytes() not in key, "%s: the cloud holds a point twice, indices would not be unique" % what
+        key[r.tobytes()] = i
+    return np.array([key[r.tobytes()] for r in np.ascontiguousarray(points_f64, dtype=_F)], dtype=np.int32)
+
+
+def record_loam(ref, params, sweeps, priors, with_mapping):
+    """The sweeps through the reference binary (ref.Loam, canonical VoxelGrid order: what the device computes); everything the CPU tests
+    compare with the oracle, as plain arrays.  Correspondences are stored as indices into the sweep's own clouds (recovered from the
+    functors' points, which must be unique there)."""
+    r = ref.Loam(**params)
+    d = {"n_sweeps": np.int32(len(sweeps)), "with_mapping": np.int32(with_mapping), "has_prior": np.int32(priors is not None)}
+    for k, v in dict(scan_line=64, minimum_range=5.0, line_res=0.4, plane_res=0.8, mapping_skip_frame=1, detach_vo_lo=True).items():
+        d["p_" + k] = np.float64(params.get(k, v))
+    tree_c = tree_s = np.zeros((0, 4), _F)
+    for k, c in enumerate(sweeps):
+        d["in_%d" % k] = np.ascontiguousarray(c[:, :3])
+        if priors is not None:
+            q, t = r.set_vo_prior(*priors[k])
+            d["prior_%d" % k] = np.concatenate([q, t])
+        assert r.stage_sr(c) == 0
+        cl = [r.cloud(i) for i in range(5)]
+        assert r.stage_lo() == 0
+        n = r.num_solves(r.ODOMETRY)
+        d["lo%d_n" % k] = np.int32(n)
+        for o in range(n):
+            s = r.solve(r.ODOMETRY, o)
+            nc = int(np.count_nonzero(s["types"] == 0))
+            pc, pp = s["payload"][:nc], s["payload"][nc:]
+            w = "sweep %d round %d" % (k, o)
+            d["lo%d_%d_corner" % (k, o)] = np.stack([_unique_index(pc[:, 0:3], cl[1], w), _unique_index(pc[:, 3:6], tree_c, w), _unique_index(pc[:, 6:9], tree_c, w)], 1).reshape(-1, 3)
+            d["lo%d_%d_plane" % (k, o)] = np.stack([_unique_index(pp[:, 0:3], cl[3], w)] + [_unique_index(pp[:, 3 * j:3 * j + 3], tree_s, w) for j in (1, 2, 3)], 1).reshape(-1, 4)
+            d["lo%d_%d_res0" % (k, o)] = s["residuals0"]
+            d["lo%d_%d_x" % (k, o)] = np.concatenate([s["q_in"], s["t_in"], s["q_out"], s["t_out"]])
+        d["lo%d_pose" % k] = np.concatenate(r.lo_pose())
+        d["lo%d_skip" % k] = np.int32(r.skip_frame())
+        if not with_mapping:     # (the mapping recordings leave the hand-over clouds to the odometry recordings: file size)
+            d["lo%d_c2" % k], d["lo%d_c4" % k] = cl[2], cl[4]
+            # laserCloudFullRes is a selection of input rows plus an intensity, stored that way (as pack_golden does)
+            xyz = np.ascontiguousarray(c[:, :3])
+            d["lo%d_full_src" % k] = _rows_index(np.ascontiguousarray(cl[0][:, :3]), xyz)
+            d["lo%d_full_intensity" % k] = cl[0][:, 3].copy()
+            if not r.skip_frame():
+                assert np.array_equal(r.cloud(7).view(np.uint32), cl[0].view(np.uint32)) and np.array_equal(r.cloud(5).view(np.uint32), cl[2].view(np.uint32))
+        tree_c, tree_s = cl[2], cl[4]
+        if not with_mapping:
+            continue
+        assert r.stage_map() == 0
+        n = r.num_solves(r.MAPPING)
+        d["map%d_n" % k] = np.int32(n)
+        d["map%d_pub" % k] = np.concatenate(r.published_pose(1))
+        if r.skip_frame():
+            continue
+        d["map%d_stacks" % k] = r.map_filter_log()[:2, 1].astype(np.int32)
+        for o in range(n):
+            s = r.solve(r.MAPPING, o)
+            ne = int(np.count_nonzero(s["types"] == 0))
+            assert np.all(s["types"][:ne] == 0) and np.all(s["types"][ne:] == 2)
+            d["map%d_%d_ne" % (k, o)] = np.int32(ne)
+            d["map%d_%d_curr" % (k, o)] = s["payload"][:, 0:3].astype(_F)
+            d["map%d_%d_cab" % (k, o)] = s["payload"][:ne, 3:9]
+            d["map%d_%d_spl" % (k, o)] = s["payload"][ne:, 3:7]
+            d["map%d_%d_res0" % (k, o)] = s["residuals0"]
+            d["map%d_%d_x" % (k, o)] = np.concatenate([s["q_in"], s["t_in"], s["q_out"], s["t_out"]])
+        d["map%d_counts" % k] = r.map_cube_counts().astype(np.int32)
+    if with_mapping:
+        d["map_cloud"] = r.cloud(8)
+    return d
+
+
+def loam_golden_params(z):
+    return dict(scan_line=int(z["p_scan_line"]), minimum_range=float(z["p_minimum_range"]), line_res=float(z["p_line_res"]), plane_res=float(z["p_plane_res"]),
+                mapping_skip_frame=int(z["p_mapping_skip_frame"]), detach_vo_lo=bool(z["p_detach_vo_lo"]))
+
+
+def loam_golden_full(z, k):
+    """laserCloudFullRes of sweep k of a ref_lo_* recording."""
+    xyz = z["in_%d" % k]
+    full = np.zeros((z["lo%d_full_src" % k].shape[0], 4), dtype=_F)
+    full[:, :3] = xyz[z["lo%d_full_src" % k]]
+    full[:, 3] = z["lo%d_full_intensity" % k]
+    return full
+
+
+def loam_golden_sweep(z, k):
+    xyz = z["in_%d" % k]
+    c = np.zeros((xyz.shape[0], 4), dtype=_F)
+    c[:, :3] = xyz
+    return c

@@ -81,6 +81,20 @@ def test_ring_of_exactly_the_capacity_and_one_more(vl, orc):
     assert ei.value.status == vl.ERR_CAPACITY and "8192" in str(ei.value)
 
 
+def test_ring_of_exactly_the_long_tier_limit_and_one_more(vl, orc):
+    """The top of the opt-in tier: a ring of exactly 16 384 points goes through (stage-wise against the oracle), one of 16 385 is refused."""
+    h = vl.Handle(0, max_ring_points=16384, debug=1, with_mapping=0)
+    cloud = one_ring(16384, noise=0.05)
+    o = orc.Oracle(with_mapping=False)
+    check_stagewise(h, o, cloud, "16 384-point ring")
+    assert o.cloud(0).shape[0] == 16384
+    with pytest.raises(vl.VloamError) as ei:
+        h.reset_frame()
+        h.scan_registration(one_ring(16385, noise=0.05))
+        h.laser_odometry()   # (the stage that reads the sweep's error word)
+    assert ei.value.status == vl.ERR_CAPACITY and "16384" in str(ei.value)
+
+
 def test_long_rings_with_a_voxel_for_almost_every_point(vl, orc, synth):
     """Returns from 120 m lie 0.1 m apart at 7 500 columns and from 400 m 0.33 m: nearly every lessFlat point is a voxel of its own."""
     n_az = 7500

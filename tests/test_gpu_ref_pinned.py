@@ -44,7 +44,10 @@ def test_the_recordings_are_all_here():
 @pytest.mark.parametrize("path", GOLDEN, ids=[os.path.basename(p)[7:-4] for p in GOLDEN])
 def test_device_against_the_reference_binarys_recorded_output(vl, path):
     scan_line, minimum_range, sweeps, results = ref_cases.load_golden(path)
-    h = vl.Handle(0, scan_line=scan_line, minimum_range=minimum_range, with_mapping=0)
+    kw = {}
+    if max(ref_cases.longest_ring(r[0]) for r in results) > 4096:     # beyond the default tier: the opt-in long ring tier, sized for its limit
+        kw = dict(max_ring_points=16384, max_points=max(max(c.shape[0] for c in sweeps), 1024))
+    h = vl.Handle(0, scan_line=scan_line, minimum_range=minimum_range, with_mapping=0, **kw)
     for k, c in enumerate(sweeps):     # several sweeps: one handle, like the one ScanRegistration object of the recording
         h.reset_frame()
         h.scan_registration(c)

@@ -602,7 +602,9 @@ class LaserOdometry:
 
     def output(self):
         qw, tw, _, _ = self._pose
-        skip = (self.hd.frame_count() + (0 if self.hd.cfg.with_mapping else 0)) % self.hd.cfg.mapping_skip_frame != 0
+        # laser_odometry.cpp:535,618: frameCount is incremented by solveLO before output() tests it.  The handle counts a sweep when its last
+        # stage is done: with mapping that is still to come here, without it solveLO was the last stage
+        skip = (self.hd.frame_count() + (1 if self.hd.cfg.with_mapping else 0)) % self.hd.cfg.mapping_skip_frame != 0
         return qw, tw, self.hd.features(5), self.hd.features(6), self.hd.features(0), skip
 
 
@@ -628,7 +630,7 @@ class LaserMapping:
         if len(args) != 6:
             raise TypeError("LaserMapping.input takes (corner, surf, full, q_wodom_curr, t_wodom_curr, skip_frame)")
         corner, surf, full, q, t, skip = args
-        if bool(skip) != (self.hd.frame_count() % self.hd.cfg.mapping_skip_frame != 0):
+        if bool(skip) != ((self.hd.frame_count() + 1) % self.hd.cfg.mapping_skip_frame != 0):   # (this sweep is not counted yet: see LaserOdometry.output)
             raise ValueError("LaserMapping.input: skip_frame differs from frameCount % mapping_skip_frame (laser_odometry.cpp:618)")
         edits = {}
         if not skip:
