@@ -32,7 +32,8 @@ enum {
   VLOAM_ERR_INVALID = -1,     /* bad argument / unsupported scan_line (the reference ROS_BREAK()s) */
   VLOAM_ERR_HIP = -2,         /* a HIP runtime call failed; vloam_last_error() has the text */
   VLOAM_ERR_CAPACITY = -3,    /* more points / ring length / map entries than the handle was sized for (a scan line of more than
-                                 vloam_config::max_ring_points points: raise it, up to 16384) */
+                                 vloam_config::max_ring_points points: raise it, up to 16384; more surf points after the mapping stage's
+                                 VoxelGrid than vloam_limits::max_surf_stack_points: raise it, up to 131072) */
   VLOAM_ERR_EMPTY = -4,       /* no point survived NaN / minimum_range removal (reference: UB, scan_registration.cpp:166) */
   VLOAM_ERR_NO_DEVICE = -5,   /* no usable gfx950 device: there is NO CPU fallback */
   VLOAM_ERR_ORDER = -6        /* stage called out of the façade's order */
@@ -73,6 +74,23 @@ const char* vloam_version(void);
 
 vloam_status vloam_create(const vloam_config* cfg, int device, vloam_handle** out);
 vloam_status vloam_destroy(vloam_handle* h);
+
+/* Capacities that are not in vloam_config (whose size compiled callers depend on).  The reference has no capacity on the mapping stage's
+ * input: laserCloudSurfStack is whatever downSizeFilterSurf returns (laser_mapping.cpp:432-440).  A default handle takes 24576 surf points
+ * there (a 64-line sweep at the KITTI leaf of 0.8 m has ~6000; at a 0.2 m leaf ~27000) and vloam_sync reports VLOAM_ERR_CAPACITY beyond; a
+ * larger max_surf_stack_points adds the large stack tier: everything the mapping stage indexes by a stack point is sized by it (~2.8 KB of
+ * device memory per point and session), the scan-to-map kernels run their run-time-capacity forms and the solve
+ * compacts its factors in a launch of its own.  The corner stack (8192 >= the 7680 lessSharp points a sweep can have) has no such limit.
+ * struct_size: sizeof(vloam_limits) as the caller compiled it (0: this header's), so that fields can be added behind the ones it knows. */
+typedef struct vloam_limits {
+  int struct_size;             /* sizeof(vloam_limits) as the caller compiled it */
+  int max_surf_stack_points;   /* capacity of laserCloudSurfStack: 24576 (0 = 24576); multiples of 8192 up to 131072 add the large stack tier */
+} vloam_limits;
+void vloam_default_limits(vloam_limits* lim);
+/* vloam_create_batch with limits.  lim == NULL or the defaults: the same handle as vloam_create_batch(cfg, device, n_sessions, out).
+ * VLOAM_ERR_INVALID (before any device call): max_surf_stack_points other than 0, 24576 or a multiple of 8192 in (24576, 131072], or such a
+ * multiple above cfg->max_points; a struct_size that is neither 0 nor >= sizeof(vloam_limits).  VLOAM_ERR_HIP: the arenas do not fit the device's memory. */
+vloam_status vloam_create_with_limits(const vloam_config* cfg, const vloam_limits* lim, int device, int n_sessions, vloam_handle** out);
 
 /* ---- Batched execution: one handle, n_sessions independent sequences advanced in lock step.  Every kernel of the sweep chain is
  * launched once per sweep for ALL sessions (session index in blockIdx.z), so n_sessions sequences cost one launch chain — the way to

@@ -114,9 +114,14 @@ inline Cloud from_cloud_ptr(const P& in) {
 // an HDL-32E at 5 Hz, an HDL-64E with two lasers in one scan line, 4 096-column heads).
 class Session {  // one vloam_handle == one sequence on one GPU; shared by the three stage objects
  public:
-  explicit Session(int device = 0, const vloam_config* cfg = nullptr) {
+  // max_surf_stack_points != 0: vloam_limits::max_surf_stack_points (the constructor LaserMapping(device, cfg, max_surf_stack_points) uses it)
+  explicit Session(int device = 0, const vloam_config* cfg = nullptr, int max_surf_stack_points = 0) {
     if (cfg) config = *cfg; else vloam_default_config(&config);
-    check(vloam_create(&config, device, &h_));
+    if (!max_surf_stack_points) { check(vloam_create(&config, device, &h_)); return; }
+    vloam_limits lim;
+    vloam_default_limits(&lim);
+    lim.max_surf_stack_points = max_surf_stack_points;
+    check(vloam_create_with_limits(&config, &lim, device, 1, &h_));
   }
   vloam_config config;
   int frames_done = 0;   // sweeps whose laser odometry has run == LaserOdometry::frameCount
@@ -243,6 +248,9 @@ class LaserMapping {
  public:
   LaserMapping() : s_(Session::get_default()) {}   // like the reference's: the stages of a process share Session::get_default()
   explicit LaserMapping(std::shared_ptr<Session> s) : s_(std::move(s)) {}
+  // a mapping stage on a session of its own whose laserCloudSurfStack takes max_surf_stack_points points (vloam_limits; dense leaves on
+  // 64-line sensors: INTEGRATION.md §5).  Stages that share one session are handed a Session constructed with the same third argument.
+  LaserMapping(int device, const vloam_config* cfg, int max_surf_stack_points = 0) : s_(std::make_shared<Session>(device, cfg, max_surf_stack_points)) {}
   void init() {}
   template <class TF> void init(std::shared_ptr<TF>&) {}   // laser_mapping.h:85
   void reset() {}

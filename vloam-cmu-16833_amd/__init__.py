@@ -44,6 +44,11 @@ class Config(C.Structure):
                 ("max_ring_points", C.c_int)]
 
 
+class Limits(C.Structure):
+    """vloam_limits: capacities that are not in vloam_config (c_api.h)."""
+    _fields_ = [("struct_size", C.c_int), ("max_surf_stack_points", C.c_int)]
+
+
 class Calib(C.Structure):
     _fields_ = [("cam_T_velo", C.c_float * 16), ("rect0_T_cam", C.c_float * 16), ("P_rect0", C.c_float * 12)]
 
@@ -90,6 +95,16 @@ def default_config(**kw):
     return c
 
 
+def default_limits(**kw):
+    lim = Limits()
+    lib().vloam_default_limits(C.byref(lim))
+    for k, v in kw.items():
+        if not hasattr(lim, k):
+            raise AttributeError("vloam_limits has no field %r" % k)
+        setattr(lim, k, v)
+    return lim
+
+
 def _fp(a):
     return a.ctypes.data_as(C.c_void_p)
 
@@ -97,14 +112,17 @@ def _fp(a):
 class Handle:
     """One sequence on one GPU (``vloam_handle``)."""
 
-    def __init__(self, device=0, n_sessions=1, **cfg):
+    def __init__(self, device=0, n_sessions=1, max_surf_stack_points=None, **cfg):
         """n_sessions > 1: a batched handle — that many independent sequences advanced in lock step by batch_process_scan*;
-        select(b) chooses the session the getters read."""
+        select(b) chooses the session the getters read.  max_surf_stack_points: vloam_limits::max_surf_stack_points (None: the default,
+        24576; multiples of 8192 up to 131072 add the large stack tier)."""
         self.L = lib()
         self.cfg = default_config(**cfg)
+        self.limits = default_limits() if max_surf_stack_points is None else default_limits(max_surf_stack_points=int(max_surf_stack_points))
+        self.surf_stack_cap = self.limits.max_surf_stack_points or K_STACK_CAP_SURF
         self.h = C.c_void_p()
         self.n_sessions = int(n_sessions)
-        self._chk(self.L.vloam_create_batch(C.byref(self.cfg), int(device), self.n_sessions, C.byref(self.h)))
+        self._chk(self.L.vloam_create_with_limits(C.byref(self.cfg), C.byref(self.limits), int(device), self.n_sessions, C.byref(self.h)))
 
     def _chk(self, st):
         if st != VLOAM_OK:
@@ -489,7 +507,7 @@ class Handle:
 
 
     def map_debug(self, outer):
-        cap = K_MAP_FACTOR_CAP
+        cap = K_STACK_CAP_CORNER + self.surf_stack_cap   # (== K_MAP_FACTOR_CAP on a default handle)
         types = self.debug_raw(2, outer * 16 + 0, np.int32)
         A = self.debug_raw(2, outer * 16 + 1, np.float64).reshape(3, cap).T
         B = self.debug_raw(2, outer * 16 + 2, np.float64).reshape(3, cap).T

@@ -292,8 +292,29 @@ void vloam_default_config(vloam_config* c) {
 const char* vloam_last_error(void) { return g_err.c_str(); }
 const char* vloam_version(void) { return "vloam_hip 0.1 (gfx950)"; }
 
+void vloam_default_limits(vloam_limits* lim) {
+  lim->struct_size = (int)sizeof(vloam_limits);
+  lim->max_surf_stack_points = kStackCapSurf;
+}
+
 vloam_status vloam_create_batch(const vloam_config* cfg, int device, int n_sessions, vloam_handle** out) {
+  return vloam_create_with_limits(cfg, nullptr, device, n_sessions, out);
+}
+
+vloam_status vloam_create_with_limits(const vloam_config* cfg, const vloam_limits* lim, int device, int n_sessions, vloam_handle** out) {
   if (!cfg || !out) { set_err("null argument"); return VLOAM_ERR_INVALID; }
+  int surf_cap = kStackCapSurf;
+  if (lim) {
+    const int S = lim->max_surf_stack_points;
+    const bool size_ok = lim->struct_size == 0 || lim->struct_size >= (int)sizeof(vloam_limits);
+    const bool value_ok = S == 0 || S == kStackCapSurf || (S > kStackCapSurf && S <= kStackCapSurfMax && S % kStackCapSurfStep == 0);
+    if (!size_ok || !value_ok || (S > kStackCapSurf && S > cfg->max_points)) {   // (the default holds whatever max_points is, as it always has)
+      set_err("vloam_limits: max_surf_stack_points must be 0 or %d (default), or a multiple of %d up to %d, and at most max_points; struct_size 0 or >= %d",
+              kStackCapSurf, kStackCapSurfStep, kStackCapSurfMax, (int)sizeof(vloam_limits));
+      return VLOAM_ERR_INVALID;
+    }
+    if (S != 0) surf_cap = S;
+  }
   if (n_sessions < 1 || n_sessions > kMaxBatch) { set_err("n_sessions must be 1..%d", kMaxBatch); return VLOAM_ERR_INVALID; }
   if (cfg->scan_line != 16 && cfg->scan_line != 32 && cfg->scan_line != 64) {
     set_err("only support velodyne with 16, 32 or 64 scan line!");  // scan_registration.cpp:54-58
@@ -348,6 +369,7 @@ vloam_status vloam_create_batch(const vloam_config* cfg, int device, int n_sessi
   vloam_handle* h = new vloam_handle;
   h->cfg = *cfg;
   if (h->cfg.max_ring_points == 0) h->cfg.max_ring_points = kMaxRingLen;   // zero-initialised configs: the default
+  h->map.surf_cap = surf_cap;   // before the layout: the mapping stage's arrays are sized by it (map_layout)
   h->device = device;
   *out = nullptr;
   vloam_status st = VLOAM_OK;
@@ -1502,7 +1524,10 @@ vloam_status vloam_sync(vloam_handle* h) {
     if (merr & kErrEmpty) { set_err("no point survived NaN / minimum_range removal in at least one sweep since the last vloam_sync"); return VLOAM_ERR_EMPTY; }
     if (merr & kErrRingTooLong) { set_err("a ring held more than %d points (dropped) in at least one sweep since the last vloam_sync", h->cfg.max_ring_points); return VLOAM_ERR_CAPACITY; }
     if (merr & kErrMapFull) { set_err("voxel hash full (map_capacity_log2=%d)", h->cfg.map_capacity_log2); return VLOAM_ERR_CAPACITY; }
-    if (merr & kErrStackFull) { set_err("mapping factor table full"); return VLOAM_ERR_CAPACITY; }
+    if (merr & kErrStackFull) {
+      set_err("mapping factor table full: more than %d surf points after VoxelGrid; raise vloam_limits::max_surf_stack_points", h->map.surf_cap);
+      return VLOAM_ERR_CAPACITY;
+    }
     if (merr & kErrMapDeferred) { set_err("raw-point capacity of the map exceeded (more than 255 un-merged points in a voxel of a cube outside the valid block, or more than 64 raw voxels around one query)"); return VLOAM_ERR_CAPACITY; }
     if (merr & kErrSolverSync) { set_err("a workgroup of the scan-feature VoxelGrid gave up waiting for the bins in front of it"); return VLOAM_ERR_HIP; }
     if (merr & kErrVoDegenerate) { set_err("a VO solve returned a zero rotation angle: poses are NaN from that frame on, as in the reference (visual_odometry.cpp:427-430)"); return VLOAM_ERR_INVALID; }

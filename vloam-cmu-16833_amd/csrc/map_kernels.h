@@ -19,6 +19,11 @@ constexpr int kCubeW = 21, kCubeH = 21, kCubeD = 11, kCubeNum = kCubeW * kCubeH 
 constexpr int kStackCapCorner = 8192;   // >= kMaxLessSharp
 constexpr int kStackCapSurf = 24576;    // voxels of one sweep's lessFlat cloud at the plane resolution (with the corner stack: 32 768 slots = the 512 mask rows of a solve)
 constexpr int kMapFactorCap = kStackCapCorner + kStackCapSurf;
+// Large stack tier (vloam_limits::max_surf_stack_points): a handle may size its surf stack — and everything indexed by a stack slot — up to
+// kStackCapSurfMax in steps of kStackCapSurfStep.  Corner slots stay [0, kStackCapCorner), surf slots behind them.  Such a handle launches the
+// *_tier forms of the kernels that bake the constants above in (map_kernels.hip) and solves in the packed form (more than 512 mask rows).
+constexpr int kStackCapSurfStep = 8192, kStackCapSurfMax = 131072;
+static_assert(kStackCapSurfMax <= (1 << 17), "the tier's raw-point arrival stamp keeps 17 bits of stack index (k_map_finalize_tier)");
 constexpr int kPendCap = 16;            // stack points that may land in one map voxel in one sweep
 // Voxel indices one axis of a 50 m cube can take at a leaf of 1 / inv (+ slack: the first index of a cube is taken one cell early, and the
 // cube test runs in f64 on the point while the voxel index is an f32 product): the radix of k_map_assoc's 32-bit tie rank — the position of
@@ -107,9 +112,12 @@ struct MapContext {
   int* newraw[2] = {nullptr, nullptr};        // ... the ones that turned raw in the sweep being finalized
   FactorTable F[2];        // one per outer round (kept for the parity hooks)
   LMRecord* rec = nullptr; // [2]
-  float4* nbr = nullptr;   // [kMapFactorCap][5] the 5 nearest map points of every stack point (.w of the first: 1 = accepted, LM:479 / LM:547)
-  int4* cbox = nullptr;    // [kMapFactorCap][2] voxel-index search box + candidate count of the first outer round's 5-NN search
-  float4* ccand = nullptr; // [kMapFactorCap][pass size <= kCandCache] its candidates (centroid, tie rank): the second round re-ranks them without a hash probe
+  int surf_cap = kStackCapSurf;   // capacity of laserCloudSurfStack of this handle (set before map_layout); > kStackCapSurf: the large stack tier
+  int factor_cap() const { return kStackCapCorner + surf_cap; }   // slots of everything below that is indexed by a stack slot
+  bool tier() const { return surf_cap > kStackCapSurf; }
+  float4* nbr = nullptr;   // [factor_cap()][5] the 5 nearest map points of every stack point (.w of the first: 1 = accepted, LM:479 / LM:547)
+  int4* cbox = nullptr;    // [factor_cap()][2] voxel-index search box + candidate count of the first outer round's 5-NN search
+  float4* ccand = nullptr; // [factor_cap()][pass size <= kCandCache] its candidates (centroid, tie rank): the second round re-ranks them without a hash probe
   VoxelRec* rebuild_tmp = nullptr;  // live records while a table is being rebuilt (tombstone reclamation after grid rolls)
   int rebuild_cap = 0;
   int* rebuild_n = nullptr;

@@ -129,117 +129,7 @@ __device__ __forceinline__ void dquat_rot(const double* q, const double* v, doub
 }
 
 // ---------------------------------------------------------------------------------------------- prepare
-__global__ __launch_bounds__(256) void k_map_prepare(MapState* ms, MapFrame* fr, const LOState* lo, int* cube_cnt, int skip_frame,
-                                                     double* traj_row14, StackInfo* si, int* deferred0, int* deferred1, const int* newraw0,
-                                                     const int* newraw1, long long* ts_log, size_t ss) {
-  VL_SESSION(ss); RB(ms); RB(fr); RB(lo); RB(cube_cnt); RB(traj_row14); RB(si); RB(deferred0); RB(deferred1); RB(newraw0); RB(newraw1); RB(ts_log);
-  const long long ts_begin = ts_log ? (long long)wall_clock64() : 0;
-  __shared__ int shift[3], s_cen[3];
-  const int tid = threadIdx.x;
-  // Every load that does not depend on another one is issued up front (one memory round trip for the lot): this launch is a single
-  // workgroup at the head of the stream that bounds the throughput, and each dependent trip costs ~1 us there.
-  const int nn0 = min(fr->n_newraw[0], kStackCapCorner), nn1 = min(fr->n_newraw[1], kStackCapSurf);
-  const int nd0 = fr->n_deferred[0], nd1 = fr->n_deferred[1];
-  double row[7], qmw[4], tmw[3];
-  int cen[3] = {0, 0, 0}, nst[2] = {0, 0}, si_err = 0, fr_err = 0, sweep_no = 0;
-  if (tid == 0) {
-    // the odometry pose of THIS sweep as k_lo_finish logged it (the live LOState may already belong to the next sweep: the
-    // odometry stream runs ahead of the mapping stream)
-    (void)lo;
-    for (int k = 0; k < 7; k++) row[k] = traj_row14[k];
-    for (int k = 0; k < 4; k++) qmw[k] = ms->q_wmap_wodom[k];
-    for (int k = 0; k < 3; k++) tmw[k] = ms->t_wmap_wodom[k];
-    cen[0] = ms->cenW; cen[1] = ms->cenH; cen[2] = ms->cenD;
-    nst[0] = si->n_stack[0]; nst[1] = si->n_stack[1];
-    si_err = si->error; fr_err = fr->error; sweep_no = ms->sweep_no;
-  }
-  // voxels that turned raw in the previous sweep join the list of raw voxels (k_map_finalize could not append to the list it compacts)
-  if (nn0 > 0) for (int e = tid; e < nn0; e += 256) { if (nd0 + e < kStackCapCorner) deferred0[nd0 + e] = newraw0[e]; }
-  if (nn1 > 0) for (int e = tid; e < nn1; e += 256) { if (nd1 + e < kStackCapSurf) deferred1[nd1 + e] = newraw1[e]; }
-  // every wavefront holds its copy of the four counters (and has issued its share of the merge) before thread 0 rewrites them below:
-  // the barrier's fence completes the loads above, so a wavefront that starts late can neither see the zeroed n_newraw nor the bumped n_deferred
-  __syncthreads();
-  if (tid == 0) {
-    if (nd0 + nn0 > kStackCapCorner || nd1 + nn1 > kStackCapSurf) { atomicOr(&fr->error, kErrMapFull); fr_err |= kErrMapFull; }
-    if (nn0 | nn1) {
-      fr->n_deferred[0] = min(nd0 + nn0, kStackCapCorner); fr->n_deferred[1] = min(nd1 + nn1, kStackCapSurf);
-      fr->n_newraw[0] = 0; fr->n_newraw[1] = 0;
-    }
-    // LaserMapping::input LM:182-195: q_w_curr = q_wmap_wodom * q_wodom_curr, t_w_curr = q_wmap_wodom * t_wodom_curr + t_wmap_wodom
-    for (int k = 0; k < 4; k++) ms->q_wodom_curr[k] = row[k];
-    for (int k = 0; k < 3; k++) ms->t_wodom_curr[k] = row[4 + k];
-    double q[4], t[3];
-    dquat_mul(qmw, row, q);
-    dquat_rot(qmw, row + 4, t);
-    for (int k = 0; k < 3; k++) t[k] = t[k] + tmw[k];
-    shift[0] = shift[1] = shift[2] = 0;
-    int rolled = 0;
-    if (skip_frame) {  // only the high-frequency pose is produced (LM:186-190)
-      if (traj_row14) { for (int k = 0; k < 4; k++) traj_row14[7 + k] = q[k]; for (int k = 0; k < 3; k++) traj_row14[11 + k] = t[k]; }
-    } else {
-      for (int k = 0; k < 4; k++) ms->parameters[k] = q[k];
-      for (int k = 0; k < 3; k++) ms->parameters[4 + k] = t[k];
-      // LM:207-216
-      int cI = cube_abs(t[0]) + cen[0], cJ = cube_abs(t[1]) + cen[1], cK = cube_abs(t[2]) + cen[2];
-      // LM:218-402: the six while loops only move cube pointers and the centre offsets
-      while (cI < 3) { cI++; cen[0]++; shift[0]++; }
-      while (cI >= kCubeW - 3) { cI--; cen[0]--; shift[0]--; }
-      while (cJ < 3) { cJ++; cen[1]++; shift[1]++; }
-      while (cJ >= kCubeH - 3) { cJ--; cen[1]--; shift[1]--; }
-      while (cK < 3) { cK++; cen[2]++; shift[2]++; }
-      while (cK >= kCubeD - 3) { cK--; cen[2]--; shift[2]--; }
-      ms->centerCube[0] = cI; ms->centerCube[1] = cJ; ms->centerCube[2] = cK;
-      s_cen[0] = cI; s_cen[1] = cJ; s_cen[2] = cK;
-      if (shift[0] | shift[1] | shift[2]) { rolled = 1; ms->cenW = cen[0]; ms->cenH = cen[1]; ms->cenD = cen[2]; }
-      // the scan features were voxelised on the scan-registration stream (k_map_ds_*): adopt this sweep's stack
-      if (si_err) { atomicOr(&fr->error, si_err); fr_err |= si_err; si->error = 0; }
-      if (fr_err & (kErrMapFull | kErrSolverSync)) nst[0] = nst[1] = 0;  // the map cannot take this sweep (table full), or its stack has holes (a bin of the scan-feature VoxelGrid timed out): no association, no insert; the pose stays the odometry guess (vloam_sync reports it)
-      for (int k = 0; k < 2; k++) { fr->n_stack[k] = nst[k]; fr->n_touched[k] = 0; }
-      ms->n_corner_stack = nst[0]; ms->n_surf_stack = nst[1];
-      for (int k = 0; k < 4; k++) (&fr->n_factors[0][0])[k] = 0;
-      ms->sweep_no = sweep_no + 1;
-      if (ts_log) ts_log[2 * (sweep_no & 1023)] = ts_begin;
-    }
-    fr->rolled = rolled;
-  }
-  __syncthreads();
-  if (skip_frame) return;
-  // shift the per-cube point counters exactly like the reference shifts its cube arrays (cleared slabs -> 0)
-  if (shift[0] | shift[1] | shift[2]) {
-    for (int kind = 0; kind < 2; kind++) {
-      int* cnt = cube_cnt + kind * kCubeNum;
-      // gather-with-offset through registers: new[i][j][k] = old[i - sx][j - sy][k - sz] or 0
-      int vals[(kCubeNum + 255) / 256];
-      int n = 0;
-      for (int c = tid; c < kCubeNum; c += 256, n++) {
-        const int i = c % kCubeW, j = (c / kCubeW) % kCubeH, k = c / (kCubeW * kCubeH);
-        const int si = i - shift[0], sj = j - shift[1], sk = k - shift[2];
-        vals[n] = (si >= 0 && si < kCubeW && sj >= 0 && sj < kCubeH && sk >= 0 && sk < kCubeD) ? cnt[si + kCubeW * sj + kCubeW * kCubeH * sk] : 0;
-      }
-      __syncthreads();
-      n = 0;
-      for (int c = tid; c < kCubeNum; c += 256, n++) cnt[c] = vals[n];
-      __syncthreads();
-    }
-  }
-  // LM:404-430,448: points in the valid 5x5x3 block decide whether the optimisation runs
-  if (tid < 64) {
-    int s0 = 0, s1 = 0;
-    for (int c = tid; c < 75; c += 64) {
-      const int i = s_cen[0] - 2 + c / 15, j = s_cen[1] - 2 + (c / 3) % 5, k = s_cen[2] - 1 + c % 3;
-      if (i >= 0 && i < kCubeW && j >= 0 && j < kCubeH && k >= 0 && k < kCubeD) {
-        const int ci = i + kCubeW * j + kCubeW * kCubeH * k;
-        s0 += cube_cnt[ci]; s1 += cube_cnt[kCubeNum + ci];
-      }
-    }
-    for (int d = 32; d > 0; d >>= 1) { s0 += __shfl_xor(s0, d); s1 += __shfl_xor(s1, d); }
-    if (tid == 0) {
-      ms->n_map_corner = s0; ms->n_map_surf = s1;
-      ms->do_optimize = (s0 > 10 && s1 > 50) ? 1 : 0;
-    }
-  }
-}
-
+// k_map_prepare (and, below, k_map_fit): map_kernels_capped.inc, included once per form further down
 // Drop voxels whose cube left the window (the reference clears the slab that wraps, LM:240-241 etc.).  Only after a roll.
 // The window is +-500 m around the sensor while queries and inserts stay within the +-125 m valid block, so nothing of the
 // sweep that rolled can touch such a voxel: the sweep's last launch (k_map_finalize) does the purge on its way out, instead
@@ -1048,75 +938,19 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(5))) void k
   }
 }
 
-__global__ __launch_bounds__(256) void k_map_fit(const float4* __restrict__ stack0, const float4* __restrict__ stack1, VoxelTable T0,
-                                                 VoxelTable T1, const MapState* __restrict__ ms, MapFrame* fr, const float4* __restrict__ nbr,
-                                                 FactorTable F, int outer, size_t ss) {
-  VL_SESSION(ss); RB(stack0); RB(stack1); RB(ms); RB(fr); RB(nbr); F.rebase(so_);
-  const int slot = blockIdx.x * 256 + threadIdx.x;
-  if (slot >= kMapFactorCap) return;
-  const int kind = slot < kStackCapCorner ? 0 : 1;
-  const int i = kind ? slot - kStackCapCorner : slot;
-  const int nst = kind ? ms->n_surf_stack : ms->n_corner_stack;
-  int type = 0;
-  (void)T0; (void)T1;
-  if (ms->do_optimize && i < nst && nbr[slot * 5].w != 0.0f) {
-    const float4 pointOri = kind ? stack1[i] : stack0[i];
-    double P[5][3];
-#pragma unroll
-    for (int j = 0; j < 5; j++) {
-      const float4 p = nbr[slot * 5 + j];
-      P[j][0] = p.x; P[j][1] = p.y; P[j][2] = p.z;
-    }
-    double A3[3] = {0, 0, 0}, B3[3] = {0, 0, 0};
-    if (kind == 0) {  // LM:481-517
-      double center[3] = {0, 0, 0};
-#pragma unroll
-      for (int j = 0; j < 5; j++) for (int a = 0; a < 3; a++) center[a] = center[a] + P[j][a];
-      for (int a = 0; a < 3; a++) center[a] = center[a] / 5.0;
-      double cov[3][3] = {{0, 0, 0}, {0, 0, 0}, {0, 0, 0}};
-#pragma unroll
-      for (int j = 0; j < 5; j++) {
-        const double z[3] = {P[j][0] - center[0], P[j][1] - center[1], P[j][2] - center[2]};
-        for (int a = 0; a < 3; a++) for (int b = 0; b < 3; b++) cov[a][b] = cov[a][b] + z[a] * z[b];
-      }
-      double e_mid, e_max, dir[3];
-      sym_eig3_top(cov, &e_mid, &e_max, dir);
-      if (e_max > 3 * e_mid) {
-        for (int a = 0; a < 3; a++) { A3[a] = 0.1 * dir[a] + center[a]; B3[a] = -0.1 * dir[a] + center[a]; }
-        type = 1;
-      }
-    } else {          // LM:545-581
-      double matA0[15], matB0[5], nrm[3];
-#pragma unroll
-      for (int j = 0; j < 5; j++) { matA0[j * 3] = P[j][0]; matA0[j * 3 + 1] = P[j][1]; matA0[j * 3 + 2] = P[j][2]; matB0[j] = -1.0; }
-      if (householder_ls_5x3(matA0, matB0, nrm)) {
-        const double nn_ = sqrt(nrm[0] * nrm[0] + nrm[1] * nrm[1] + nrm[2] * nrm[2]);
-        const double negative_OA_dot_norm = 1 / nn_;
-        nrm[0] = nrm[0] / nn_; nrm[1] = nrm[1] / nn_; nrm[2] = nrm[2] / nn_;
-        bool planeValid = true;
-#pragma unroll
-        for (int j = 0; j < 5; j++)
-          if (fabs(nrm[0] * P[j][0] + nrm[1] * P[j][1] + nrm[2] * P[j][2] + negative_OA_dot_norm) > 0.2) planeValid = false;
-        if (planeValid) { A3[0] = nrm[0]; A3[1] = nrm[1]; A3[2] = nrm[2]; B3[0] = negative_OA_dot_norm; type = 3; }
-      }
-    }
-    if (type) {
-      const int cap = F.cap;
-      F.p[slot] = pointOri.x; F.p[cap + slot] = pointOri.y; F.p[2 * cap + slot] = pointOri.z;
-      F.A[slot] = A3[0]; F.A[cap + slot] = A3[1]; F.A[2 * cap + slot] = A3[2];
-      F.B[slot] = B3[0]; F.B[cap + slot] = B3[1]; F.B[2 * cap + slot] = B3[2];
-      factor_digest(F, slot, type, A3, B3);   // the solve's form of the factor, ready when the solve starts (lm_solve.hip)
-    }
-  }
-  F.type[slot] = type;
-  // a wavefront == one 64-slot row of the table: its accepted slots as one mask (every row, every launch: nothing to clear); the solve
-  // compacts from the masks on its own
-  const unsigned long long m = __ballot(type != 0);
-  if ((threadIdx.x & 63) == 0) {
-    F.rowmask[slot >> 6] = m;
-    if (m) atomicAdd(&fr->n_factors[outer][kind], __popcll(m));
-  }
-}
+// k_map_prepare / k_map_fit in their two forms (the include file takes its five parameters as macros and undefines them at its end)
+#define VL_MAP_TIER 0
+#define VL_MAP_KERNEL(name) name
+#define VL_MAP_CAP_PARAM
+#define VL_MAP_SURF_CAP kStackCapSurf
+#define VL_MAP_FACTOR_CAP kMapFactorCap
+#include "map_kernels_capped.inc"
+#define VL_MAP_TIER 1
+#define VL_MAP_KERNEL(name) name##_tier
+#define VL_MAP_CAP_PARAM , int surf_cap
+#define VL_MAP_SURF_CAP surf_cap
+#define VL_MAP_FACTOR_CAP F.cap
+#include "map_kernels_capped.inc"
 
 // ---------------------------------------------------------------------------------------------- update / insert / finalize
 // transformUpdate + the map half of the trajectory row; done by one lane of k_map_insert (nothing else in that launch reads
@@ -1151,7 +985,7 @@ __device__ bool map_publish_block(const VoxelTable& T, int Ai, int Aj, int Ak, i
 }
 
 // One raw point of a voxel as a record of its own: key | seq, sum = the point, count = 1, pend_cnt = arrival stamp (sweep << 14 | stack
-// index; 0 for a centroid that became raw point number one).  find-or-insert: a purged record of the same key is reused.
+// index — sweep << 17 | stack index on a handle of the large stack tier, k_map_finalize; 0 for a centroid that became raw point number one).  find-or-insert: a purged record of the same key is reused.
 __device__ bool map_put_raw_point(const VoxelTable& T, u64 voxel_key, int seq, float4 p, int stamp) {
   const u64 key = key_with_seq(voxel_key, seq);
   unsigned s = (unsigned)mix64(key) & T.mask;
@@ -1180,11 +1014,12 @@ __device__ void map_drop_raw_points(const VoxelTable& T, u64 voxel_key, int n) {
   if (dead) atomicAdd(&T.stats[1], dead);
 }
 
-__global__ __launch_bounds__(256) void k_map_insert(const float4* __restrict__ stack0, const float4* __restrict__ stack1,
-                                                    float4* __restrict__ smap0, float4* __restrict__ smap1, VoxelTable T0, VoxelTable T1,
-                                                    float inv0, float inv1, MapState* ms, MapFrame* fr, int* __restrict__ touched0,
-                                                    int* __restrict__ touched1, int* __restrict__ deferred0, int* __restrict__ deferred1,
-                                                    double* traj_row14, size_t ss) {
+template <bool TIER>
+__device__ __forceinline__ void map_insert_body(const float4* __restrict__ stack0, const float4* __restrict__ stack1,
+                                                float4* __restrict__ smap0, float4* __restrict__ smap1, VoxelTable T0, VoxelTable T1,
+                                                float inv0, float inv1, MapState* ms, MapFrame* fr, int* __restrict__ touched0,
+                                                int* __restrict__ touched1, int* __restrict__ deferred0, int* __restrict__ deferred1,
+                                                double* traj_row14, size_t ss, int surf_cap) {
   VL_SESSION(ss); RB(stack0); RB(stack1); RB(smap0); RB(smap1); T0.rebase(so_); T1.rebase(so_); RB(ms); RB(fr); RB(touched0); RB(touched1);
   RB(deferred0); RB(deferred1); RB(traj_row14);
   if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) map_update(ms, traj_row14);  // LM:636
@@ -1196,7 +1031,7 @@ __global__ __launch_bounds__(256) void k_map_insert(const float4* __restrict__ s
   int* touched = kind ? touched1 : touched0;
   (void)deferred0; (void)deferred1;
   const int n = kind ? ms->n_surf_stack : ms->n_corner_stack;
-  const int cap = kind ? kStackCapSurf : kStackCapCorner;
+  const int cap = kind ? (TIER ? surf_cap : kStackCapSurf) : kStackCapCorner;
   const int lane = threadIdx.x & 63;
   // the thread's first stack point is requested together with the stack size, not behind it (the stale tail of the array is valid memory)
   const int i_first = blockIdx.x * 256 + threadIdx.x;
@@ -1246,12 +1081,22 @@ __global__ __launch_bounds__(256) void k_map_insert(const float4* __restrict__ s
     }
   }
 }
+#define VL_MAP_INSERT_PARAMS const float4* __restrict__ stack0, const float4* __restrict__ stack1, float4* __restrict__ smap0, float4* __restrict__ smap1, \
+    VoxelTable T0, VoxelTable T1, float inv0, float inv1, MapState* ms, MapFrame* fr, int* __restrict__ touched0, int* __restrict__ touched1,      \
+    int* __restrict__ deferred0, int* __restrict__ deferred1, double* traj_row14, size_t ss
+#define VL_MAP_INSERT_ARGS stack0, stack1, smap0, smap1, T0, T1, inv0, inv1, ms, fr, touched0, touched1, deferred0, deferred1, traj_row14, ss
+__global__ __launch_bounds__(256) void k_map_insert(VL_MAP_INSERT_PARAMS) { map_insert_body<false>(VL_MAP_INSERT_ARGS, kStackCapSurf); }
+__global__ __launch_bounds__(256) void k_map_insert_tier(VL_MAP_INSERT_PARAMS, int surf_cap) { map_insert_body<true>(VL_MAP_INSERT_ARGS, surf_cap); }
+#undef VL_MAP_INSERT_PARAMS
+#undef VL_MAP_INSERT_ARGS
 
-__global__ __launch_bounds__(256) void k_map_finalize(const float4* __restrict__ smap0, const float4* __restrict__ smap1, VoxelTable T0,
-                                                      VoxelTable T1, MapState* ms, MapFrame* fr,
-                                                      const int* __restrict__ touched0, const int* __restrict__ touched1,
-                                                      int* __restrict__ deferred0, int* __restrict__ deferred1, int* __restrict__ newraw0,
-                                                      int* __restrict__ newraw1, int* __restrict__ cube_cnt, int* host_flags, long long* ts_log, size_t ss) {
+template <bool TIER>
+__device__ __forceinline__ void map_finalize_body(const float4* __restrict__ smap0, const float4* __restrict__ smap1, VoxelTable T0,
+                                                  VoxelTable T1, MapState* ms, MapFrame* fr,
+                                                  const int* __restrict__ touched0, const int* __restrict__ touched1,
+                                                  int* __restrict__ deferred0, int* __restrict__ deferred1, int* __restrict__ newraw0,
+                                                  int* __restrict__ newraw1, int* __restrict__ cube_cnt, int* host_flags, long long* ts_log, size_t ss,
+                                                  int surf_cap) {
   VL_SESSION(ss); RB(smap0); RB(smap1); T0.rebase(so_); T1.rebase(so_); RB(ms); RB(fr); RB(touched0); RB(touched1); RB(deferred0); RB(deferred1);
   RB(newraw0); RB(newraw1); RB(cube_cnt); RB(ts_log);
   if (ts_log && blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) ts_log[2 * ((ms->sweep_no - 1) & 1023) + 1] = (long long)wall_clock64();   // START of the sweep's last launch
@@ -1260,7 +1105,7 @@ __global__ __launch_bounds__(256) void k_map_finalize(const float4* __restrict__
   const VoxelTable T = kind ? T1 : T0;
   const float4* smap = kind ? smap1 : smap0;
   const int* touched = kind ? touched1 : touched0;
-  const int cap = kind ? kStackCapSurf : kStackCapCorner;
+  const int cap = kind ? (TIER ? surf_cap : kStackCapSurf) : kStackCapCorner;
   const int t = blockIdx.x * 256 + threadIdx.x;
   const int s_spec = touched[t < cap ? t : 0];   // requested together with the list's length, not behind it (stale entries are valid slots)
   const int nt = min(fr->n_touched[kind], cap);
@@ -1315,7 +1160,10 @@ __global__ __launch_bounds__(256) void k_map_finalize(const float4* __restrict__
         const float4 p = smap[idx[a]];
         acc.x += p.x; acc.y += p.y; acc.z += p.z; acc.w += p.w;
         seq++;
-        if (seq > 255 || !map_put_raw_point(T, rv.key, seq, p, ((ms->sweep_no & 0x3ffff) << 14) | idx[a])) overflow = true;
+        // arrival stamp = (sweep, stack index): the order key of un-merged points in k_map_export.  The default form's 14 index bits date from
+        // the 16 384-point stack; the tier form takes 17 (indices up to kStackCapSurfMax - 1) and 15 sweep bits
+        const int stamp = TIER ? (int)(((unsigned)ms->sweep_no & 0x7fffu) << 17) | idx[a] : ((ms->sweep_no & 0x3ffff) << 14) | idx[a];
+        if (seq > 255 || !map_put_raw_point(T, rv.key, seq, p, stamp)) overflow = true;
       }
       if (overflow) atomicOr(&fr->error, kErrMapDeferred);   // more than 255 raw points in one voxel, or no slot for one
       atomicAdd(cube_n, np);
@@ -1379,6 +1227,14 @@ __global__ __launch_bounds__(256) void k_map_finalize(const float4* __restrict__
     }
   }
 }
+#define VL_MAP_FINALIZE_PARAMS const float4* __restrict__ smap0, const float4* __restrict__ smap1, VoxelTable T0, VoxelTable T1, MapState* ms, MapFrame* fr, \
+    const int* __restrict__ touched0, const int* __restrict__ touched1, int* __restrict__ deferred0, int* __restrict__ deferred1,                      \
+    int* __restrict__ newraw0, int* __restrict__ newraw1, int* __restrict__ cube_cnt, int* host_flags, long long* ts_log, size_t ss
+#define VL_MAP_FINALIZE_ARGS smap0, smap1, T0, T1, ms, fr, touched0, touched1, deferred0, deferred1, newraw0, newraw1, cube_cnt, host_flags, ts_log, ss
+__global__ __launch_bounds__(256) void k_map_finalize(VL_MAP_FINALIZE_PARAMS) { map_finalize_body<false>(VL_MAP_FINALIZE_ARGS, kStackCapSurf); }
+__global__ __launch_bounds__(256) void k_map_finalize_tier(VL_MAP_FINALIZE_PARAMS, int surf_cap) { map_finalize_body<true>(VL_MAP_FINALIZE_ARGS, surf_cap); }
+#undef VL_MAP_FINALIZE_PARAMS
+#undef VL_MAP_FINALIZE_ARGS
 
 // ---------------------------------------------------------------------------------------------- table rebuild (tombstone reclamation)
 // Purged entries keep their key so that probe chains stay intact; on a long drive they would fill the table.  When the host sees
@@ -1445,7 +1301,7 @@ vloam_status map_layout(MapContext* m, const vloam_config& cfg, Arena& A) {
     T.bslots_mask = (unsigned)(bslots - 1);
     DsScratch& D = m->ds[k];
     if (k == 0) for (int c = 0; c < MapContext::kSets; c++) ok = ok && A.take(&m->stack_info[c], 1);
-    D.stack_cap = k ? kStackCapSurf : kStackCapCorner;
+    D.stack_cap = k ? m->surf_cap : kStackCapCorner;
     ok = ok && A.take(&D.region, (size_t)kDsMaxBins * kDsBinCap) && A.take(&D.over, (size_t)cfg.max_points) && A.take(&D.tmp, (size_t)cfg.max_points) &&
          A.take(&D.sorted, (size_t)cfg.max_points) && A.take(&D.splitters, (size_t)kDsMaxBins) && A.take(&D.cursor, (size_t)kDsMaxBins + 4) &&
          A.take(&D.done, (size_t)kDsMaxBins);
@@ -1454,18 +1310,20 @@ vloam_status map_layout(MapContext* m, const vloam_config& cfg, Arena& A) {
     ok = ok && A.take(&m->stack_map[k], (size_t)D.stack_cap) && A.take(&m->touched[k], (size_t)D.stack_cap) && A.take(&m->deferred[k], (size_t)D.stack_cap) &&
          A.take(&m->newraw[k], (size_t)D.stack_cap);
     FactorTable& F = m->F[k];
-    F.cap = kMapFactorCap;
+    F.cap = m->factor_cap();
     ok = ok && A.take(&F.type, (size_t)F.cap) && A.take(&F.p, 3 * (size_t)F.cap) && A.take(&F.A, 3 * (size_t)F.cap) && A.take(&F.B, 3 * (size_t)F.cap) &&
          A.take(&F.resid, 3 * (size_t)F.cap) && A.take(&F.ctype, (size_t)F.cap) && A.take(&F.cslot, (size_t)F.cap) && A.take(&F.cpack, 11 * (size_t)F.cap) && A.take(&F.dg, 8 * (size_t)F.cap) &&
-         A.take(&F.rowcnt, (size_t)F.cap / 64 + 1) && A.take(&F.rowmask, (size_t)F.cap / 64 + 2);
+         A.take(&F.rowcnt, (size_t)F.cap / 64 + 1);
+    if (m->tier()) F.rowmask = nullptr;   // more than 512 rows: k_map_fit_tier leaves row counts and the solve takes the packed form (lm_launch)
+    else ok = ok && A.take(&F.rowmask, (size_t)F.cap / 64 + 2);
     F.gsync = nullptr;  // the handle places the sync words (lm_sync_calibrate)
     F.err = ok ? &m->frame->error : nullptr;
     F.fallbacks = ok ? &m->frame->fallback_solves : nullptr;
     F.host_degraded = nullptr;   // (the handle points it at its host-mapped word)
     F.gen = 0; F.spin_limit = 1 << 18;
   }
-  ok = ok && A.take(&m->rec, 2) && A.take(&m->nbr, 5 * (size_t)kMapFactorCap);
-  ok = ok && A.take(&m->cbox, 2 * (size_t)kMapFactorCap) && A.take(&m->ccand, (size_t)kMapFactorCap * kCandCache);
+  ok = ok && A.take(&m->rec, 2) && A.take(&m->nbr, 5 * (size_t)m->factor_cap());
+  ok = ok && A.take(&m->cbox, 2 * (size_t)m->factor_cap()) && A.take(&m->ccand, (size_t)m->factor_cap() * kCandCache);
   m->rebuild_cap = (int)(slots / 2);
   ok = ok && A.take(&m->rebuild_tmp, (size_t)m->rebuild_cap) && A.take(&m->rebuild_n, 2);
   ok = ok && A.take(&m->registered, (size_t)cfg.max_points) && A.take(&m->assoc_cyc, 16) && A.take(&m->ts_log, 2048);
@@ -1514,7 +1372,7 @@ static vloam_status map_rebuild_enqueue(MapContext* m0, hipStream_t st, int sess
   MapContext* m = &ms_;
   VoxelTable& T = m->tab[kind];
   const size_t slots = (size_t)T.mask + 1, bslots = (size_t)T.bslots_mask + 1;
-  const int cap = kind ? kStackCapSurf : kStackCapCorner;
+  const int cap = kind ? m->surf_cap : kStackCapCorner;
   if (hipMemsetAsync(m->rebuild_n, 0, sizeof(int), st) != hipSuccess) return VLOAM_ERR_HIP;
   VL_RAW_LAUNCH(k_map_rebuild_gather, dim3(1024), dim3(256), 0, st, T, m->rebuild_tmp, m->rebuild_cap, m->rebuild_n, m->frame, kind);
   if (hipMemsetAsync(T.rec, 0, slots * sizeof(VoxelRec), st) != hipSuccess) return VLOAM_ERR_HIP;
@@ -1554,8 +1412,16 @@ vloam_status map_enqueue(MapContext* m, const vloam_config& cfg, hipStream_t st,
       }
   }
   // `done` (mapping of this sweep finished) rides on the sweep's last dispatch: a marker packet behind it costs ~5 us of idle stream
-  VLOAM_LAUNCH_EV(ph, kKMapPrepare, st, skip_frame ? done : nullptr, k_map_prepare, dim3(1, 1, Z), dim3(256), 0, st, ms, fr, lo, m->cube_cnt,
-                  skip_frame ? 1 : 0, traj_row14, m->stack_info[set], m->deferred[0], m->deferred[1], m->newraw[0], m->newraw[1], g_ts_log ? m->ts_log : (long long*)nullptr, ss);
+  // A handle of the large stack tier (surf capacity S > kStackCapSurf) launches the *_tier forms — the same bodies with S at run time — under
+  // the same kernel ids, on grids sized by S; a default handle launches exactly what it always did.
+  const bool tier = m->tier();
+  const int S = m->surf_cap;
+#define VL_PREPARE(KERN, ...)                                                                                                                          \
+  VLOAM_LAUNCH_EV(ph, kKMapPrepare, st, skip_frame ? done : nullptr, KERN, dim3(1, 1, Z), dim3(256), 0, st, ms, fr, lo, m->cube_cnt, skip_frame ? 1 : 0, \
+                  traj_row14, m->stack_info[set], m->deferred[0], m->deferred[1], m->newraw[0], m->newraw[1], g_ts_log ? m->ts_log : (long long*)nullptr, __VA_ARGS__)
+  if (tier) VL_PREPARE(k_map_prepare_tier, ss, S);
+  else VL_PREPARE(k_map_prepare, ss);
+#undef VL_PREPARE
   if (skip_frame) return hipGetLastError() == hipSuccess ? VLOAM_OK : VLOAM_ERR_HIP;
   for (int outer = 0; outer < 2; outer++) {  // LM:458
     // lanes per query of the 5-NN search: a batch fills the chip with 16-lane groups (four queries per wavefront); a single sequence
@@ -1563,7 +1429,7 @@ vloam_status map_enqueue(MapContext* m, const vloam_config& cfg, hipStream_t st,
     // the round-2 form — one wavefront per query, rank counting in LDS — measured 27.8 / 184 us at B = 1 / 8 against 16 / 105 here).
     static const int g_env = getenv("VLOAM_MAP_ASSOC_LANES") ? atoi(getenv("VLOAM_MAP_ASSOC_LANES")) : -1;
     const int G = g_env >= 0 ? g_env : (m->se.B > 1 ? 16 : 32);
-    auto grid_for = [](int g) { const int qw = 256 / g; return dim3(8 * ((kStackCapCorner / qw + 7) / 8 + (kStackCapSurf / qw + 7) / 8), 1, 1); };
+    auto grid_for = [S](int g) { const int qw = 256 / g; return dim3(8 * ((kStackCapCorner / qw + 7) / 8 + (S / qw + 7) / 8), 1, 1); };   // (k_map_assoc itself bakes in the corner capacity only: the grid is what grows with the tier)
 #define VL_MAP_ASSOC(KERN, GRID)                                                                                                      \
     VLOAM_LAUNCH(ph, kKMapAssoc, st, KERN, dim3((GRID).x, 1, Z), dim3(256), 0, st, m->stack[0], m->stack[1], m->tab[0], m->tab[1], \
                  m->inv_leaf[0], m->inv_leaf[1], ms, fr, m->nbr, outer, m->cbox, m->ccand, cfg.debug ? m->assoc_cyc : (long long*)nullptr, ss)
@@ -1573,14 +1439,25 @@ vloam_status map_enqueue(MapContext* m, const vloam_config& cfg, hipStream_t st,
     else if (G == 64) VL_MAP_ASSOC((k_map_assoc<64, 1>), grid_for(64));
     else VL_MAP_ASSOC((k_map_assoc<32, 1>), grid_for(32));
 #undef VL_MAP_ASSOC
-    VLOAM_LAUNCH(ph, kKMapFit, st, k_map_fit, dim3(kMapFactorCap / 256, 1, Z), dim3(256), 0, st, m->stack[0], m->stack[1], m->tab[0], m->tab[1], ms, fr, m->nbr,
-                 m->F[outer], outer, ss);
+#define VL_FIT(KERN, GRID_X)                                                                                                               \
+    VLOAM_LAUNCH(ph, kKMapFit, st, KERN, dim3((GRID_X), 1, Z), dim3(256), 0, st, m->stack[0], m->stack[1], m->tab[0], m->tab[1], ms, fr, m->nbr, \
+                 m->F[outer], outer, ss)
+    if (tier) VL_FIT(k_map_fit_tier, m->factor_cap() / 256);
+    else VL_FIT(k_map_fit, kMapFactorCap / 256);
+#undef VL_FIT
     lm_launch(st, m->se, m->F[outer], kStackCapCorner, ms->parameters, m->rec + outer, 4, 0.1, true, &ms->do_optimize, ph);
   }
-  VLOAM_LAUNCH(ph, kKMapInsert, st, k_map_insert, dim3(64, 2, Z), dim3(256), 0, st, m->stack[0], m->stack[1], m->stack_map[0], m->stack_map[1],
-               m->tab[0], m->tab[1], m->inv_leaf[0], m->inv_leaf[1], ms, fr, m->touched[0], m->touched[1], m->deferred[0], m->deferred[1], traj_row14, ss);
-  VLOAM_LAUNCH_EV(ph, kKMapFinalize, st, done, k_map_finalize, dim3(kStackCapSurf / 256, 2, Z), dim3(256), 0, st, m->stack_map[0], m->stack_map[1],
-                  m->tab[0], m->tab[1], ms, fr, m->touched[0], m->touched[1], m->deferred[0], m->deferred[1], m->newraw[0], m->newraw[1], m->cube_cnt, m->host_flags, g_ts_log ? m->ts_log : (long long*)nullptr, ss);
+#define VL_INSERT(KERN, ...)                                                                                                                  \
+  VLOAM_LAUNCH(ph, kKMapInsert, st, KERN, dim3(64, 2, Z), dim3(256), 0, st, m->stack[0], m->stack[1], m->stack_map[0], m->stack_map[1], m->tab[0], \
+               m->tab[1], m->inv_leaf[0], m->inv_leaf[1], ms, fr, m->touched[0], m->touched[1], m->deferred[0], m->deferred[1], traj_row14, __VA_ARGS__)
+#define VL_FINALIZE(KERN, GRID_X, ...)                                                                                                           \
+  VLOAM_LAUNCH_EV(ph, kKMapFinalize, st, done, KERN, dim3((GRID_X), 2, Z), dim3(256), 0, st, m->stack_map[0], m->stack_map[1], m->tab[0], m->tab[1], \
+                  ms, fr, m->touched[0], m->touched[1], m->deferred[0], m->deferred[1], m->newraw[0], m->newraw[1], m->cube_cnt, m->host_flags,      \
+                  g_ts_log ? m->ts_log : (long long*)nullptr, __VA_ARGS__)
+  if (tier) { VL_INSERT(k_map_insert_tier, ss, S); VL_FINALIZE(k_map_finalize_tier, S / 256, ss, S); }
+  else { VL_INSERT(k_map_insert, ss); VL_FINALIZE(k_map_finalize, kStackCapSurf / 256, ss); }
+#undef VL_INSERT
+#undef VL_FINALIZE
   return hipGetLastError() == hipSuccess ? VLOAM_OK : VLOAM_ERR_HIP;
 }
 
@@ -1692,7 +1569,7 @@ static vloam_status copy_dev(const void* src, size_t bytes, void* buf, long long
   return VLOAM_OK;
 }
 
-// item = outer * 16 + k:  k = 0 factor types i32[kMapFactorCap], 1 A f64[3][cap], 2 B f64[3][cap], 3 LM record, 4 residuals f64[3][cap],
+// item = outer * 16 + k:  k = 0 factor types i32[cap = 8 192 + the surf capacity], 1 A f64[3][cap], 2 B f64[3][cap], 3 LM record, 4 residuals f64[3][cap],
 //                         5 p f64[3][cap].  item 64: MapState.  item 65: MapFrame.  item 66: cube_cnt i32[2][4851].
 //                         item 67/68: dump of the corner / surf table as rows {key lo, key hi, count, x, y, z, w} (7 x 4 bytes) for live slots.
 vloam_status map_debug_get(MapContext* m0, int item, void* buf, long long cap, long long* n) {
@@ -1721,7 +1598,7 @@ vloam_status map_debug_get(MapContext* m0, int item, void* buf, long long cap, l
     return VLOAM_OK;
   }
   if (item == 72) return copy_dev(m->ts_log, sizeof(long long) * 2048, buf, cap, n);   // VLOAM_TS_LOG=1: [sweep % 1024][prepare start, finalize start], 100 MHz ticks
-  if (item == 73) return copy_dev(m->cbox, sizeof(int4) * 2 * (size_t)kMapFactorCap, buf, cap, n);   // per stack slot: the first round's search box + its candidate count (-1: not cached)
+  if (item == 73) return copy_dev(m->cbox, sizeof(int4) * 2 * (size_t)m->factor_cap(), buf, cap, n);   // per stack slot: the first round's search box + its candidate count (-1: not cached)
   if (item == 71) return copy_dev(m->assoc_cyc, sizeof(long long) * 16, buf, cap, n);   // k_map_assoc phase cycles (debug handles): [outer][6 phases, spare, wavefronts]
   if (item == 69) {  // table health: {keys, purged, block keys, spare} x {corner, surf}, rebuilds, largest candidate list
     int out[12] = {0};
