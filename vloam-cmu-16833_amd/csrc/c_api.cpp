@@ -33,7 +33,6 @@ using namespace vloam;
 static thread_local std::string g_err;
 static const bool g_host_prof = getenv("VLOAM_HOST_PROF") != nullptr;
 namespace vloam { int g_vl_plain_events = getenv("VLOAM_PLAIN_EVENTS") ? atoi(getenv("VLOAM_PLAIN_EVENTS")) : 0; }
-static const int g_enqueue_order = getenv("VLOAM_ENQUEUE_ORDER") ? atoi(getenv("VLOAM_ENQUEUE_ORDER")) : 0;
 static const int g_stage_inline = getenv("VLOAM_STAGE_INLINE") ? atoi(getenv("VLOAM_STAGE_INLINE")) : 0;   // 1: vloam_process_scan / vloam_batch_process_scan stage inline too (no deferred ring)
 static inline double now_s() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 static void set_err(const char* fmt, ...) {
@@ -69,6 +68,13 @@ static vloam_status check_stage_clouds(const char* call, int count, const char* 
       set_err("%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__);     \
       return VLOAM_ERR_HIP;                                                                   \
     }                                                                                         \
+  } while (0)
+
+// a helper's refusal or failure is the caller's
+#define TRY(expr)                              \
+  do {                                         \
+    const vloam_status try_s_ = (expr);        \
+    if (try_s_ != VLOAM_OK) return try_s_;     \
   } while (0)
 
 struct vloam_handle {
@@ -240,8 +246,7 @@ static vloam_status handle_layout(vloam_handle* h, Arena& A) {
   TAKE(h->sub.less_flat, (size_t)P);
   TAKE(h->sub_row, 14);
   TAKE(h->lo, 1);
-  vloam_status s = take_factor_table(A, &h->lo_F, kMaxLoFactors);
-  if (s != VLOAM_OK) return s;
+  TRY(take_factor_table(A, &h->lo_F, kMaxLoFactors));
   for (int k = 0; k < 2; k++) { TAKE(h->lo_corr[k], kMaxLoFactors * 4); TAKE(h->lo_resid[k], 3 * kMaxLoFactors); if (h->cfg.debug) TAKE(h->lo_cyc[k], 4 * kMaxLoFactors); }
   TAKE(h->lo_rec, 2);
   TAKE(h->lo_queue, kMaxLoFactors);
@@ -264,6 +269,160 @@ static std::atomic<int> g_single_handles{0};   // single-sequence handles alive 
 // session-relative pointer for the host-side getters
 template <class T>
 static inline T* SEL(const vloam_handle* h, T* p) { return p ? (T*)((char*)p + (size_t)h->sel * h->se.ss) : p; }
+
+// ------------------------------------------------------------------ vloam_create, in three parts
+// 1. What a configuration must satisfy, checked before any HIP call (so without a device too).  *surf_cap: the surf stack capacity to build with.
+static vloam_status validate_create(const vloam_config* cfg, const vloam_limits* lim, int n_sessions, int* surf_cap) {
+  *surf_cap = kStackCapSurf;
+  if (lim) {
+    const int S = lim->max_surf_stack_points;
+    const bool size_ok = lim->struct_size == 0 || lim->struct_size >= (int)sizeof(vloam_limits);
+    const bool value_ok = S == 0 || S == kStackCapSurf || (S > kStackCapSurf && S <= kStackCapSurfMax && S % kStackCapSurfStep == 0);
+    if (!size_ok || !value_ok || (S > kStackCapSurf && S > cfg->max_points)) {   // (the default holds whatever max_points is, as it always has)
+      set_err("vloam_limits: max_surf_stack_points must be 0 or %d (default), or a multiple of %d up to %d, and at most max_points; struct_size 0 or >= %d",
+              kStackCapSurf, kStackCapSurfStep, kStackCapSurfMax, (int)sizeof(vloam_limits));
+      return VLOAM_ERR_INVALID;
+    }
+    if (S != 0) *surf_cap = S;
+  }
+  if (n_sessions < 1 || n_sessions > kMaxBatch) { set_err("n_sessions must be 1..%d", kMaxBatch); return VLOAM_ERR_INVALID; }
+  if (cfg->scan_line != 16 && cfg->scan_line != 32 && cfg->scan_line != 64) {
+    set_err("only support velodyne with 16, 32 or 64 scan line!");  // scan_registration.cpp:54-58
+    return VLOAM_ERR_INVALID;
+  }
+  if (cfg->max_points < 64 || cfg->max_points > (1 << 24) || cfg->max_frames < 1 || cfg->mapping_skip_frame < 1) {  // 24-bit point tags
+    set_err("bad capacity"); return VLOAM_ERR_INVALID;
+  }
+  if (cfg->max_ring_points != 0 && (cfg->max_ring_points < kMaxRingLen || cfg->max_ring_points > kMaxRingLenLong)) {
+    set_err("max_ring_points must be 0 or %d (default) .. %d", kMaxRingLen, kMaxRingLenLong); return VLOAM_ERR_INVALID;
+  }
+  // laser_mapping.cpp:95-101 takes any leaf; the reference's launch files use 0.2 / 0.4 (VLP-16, HDL-32) and 0.4 / 0.8 (KITTI).  Here the
+  // position of a voxel in the gathered map cloud (the 5-NN tie rank) is a 32-bit mixed-radix number: 75 cubes x radix^3 voxels.
+  for (const float leaf : {cfg->mapping_line_resolution, cfg->mapping_plane_resolution}) {
+    const double nv = leaf > 0.f ? (double)vox_radix(1.0f / leaf) : 1e9;
+    if (!(leaf > 0.f) || 75.0 * nv * nv * nv >= 4294967295.0) { set_err("mapping resolutions below 0.132 m are not supported"); return VLOAM_ERR_INVALID; }
+  }
+  if (cfg->image_width < 0 || cfg->image_height < 0 || (long long)cfg->image_width * cfg->image_height > (1ll << 24) ||
+      ((cfg->image_width > 0) != (cfg->image_height > 0)) || (cfg->image_width > 0 && (cfg->image_width < 2 * kImgWin || cfg->image_height < 2 * kImgWin))) {
+    set_err("image_width x image_height must be 0 x 0 (no image front-end) or between %d x %d and 2^24 pixels", 2 * kImgWin, 2 * kImgWin); return VLOAM_ERR_INVALID;
+  }
+  return VLOAM_OK;
+}
+
+// 2. The handle's streams, each with the HIP priority of its pool in the plan.
+static vloam_status create_streams(vloam_handle* h, const vloam_plan::Plan& plan, const vloam_config* cfg) {
+  using namespace vloam_plan;
+  int lo_p = 0, hi_p = 0;
+  if (hipDeviceGetStreamPriorityRange(&lo_p, &hi_p) != hipSuccess) { lo_p = hi_p = 0; }   // lo_p = numerically greatest = lowest priority
+  const int pool_prio[kPools] = {0, hi_p, lo_p};
+  for (int w = 0; w < kStreams; w++) h->prio[w] = pool_prio[plan.pool[w]];
+  auto mk = [&](hipStream_t* s, int which) { return hipStreamCreateWithPriority(s, hipStreamNonBlocking, h->prio[which]) == hipSuccess; };
+  // the runtime gives a stream its hardware queue when the stream is created, so the order matters (stream_plan.h).  plan.copy_first: the
+  // copy stream of the deferred host-sweep ring comes FIRST and is used once before any other stream of the handle has work — measured
+  // (tools/host_input_probe.py, extring / extring_late; profiles/r06_host_input.txt) a copy stream that gets its hardware queue after the
+  // compute streams runs host-fed sequences at 3 900 - 4 600 scans/s, one that got it before them at 5 650
+  if (plan.copy_first && !g_stage_inline && !cfg->timing) {
+    if (!mk(&h->s_copy, kCopy)) { set_err("hipStreamCreate failed"); return VLOAM_ERR_HIP; }
+    static int warm_src = 0;
+    int* warm_dst = nullptr;
+    if (hipMalloc(&warm_dst, sizeof(int)) == hipSuccess) {
+      (void)hipMemcpyAsync(warm_dst, &warm_src, sizeof(int), hipMemcpyHostToDevice, h->s_copy);
+      (void)hipStreamSynchronize(h->s_copy);
+      (void)hipFree(warm_dst);
+    }
+  }
+  bool ok = mk(&h->stream, kSR) && mk(&h->s_lo, kLO);
+  if (ok && cfg->with_mapping) ok = mk(&h->s_map, kMap) && mk(&h->s_ds, kDS);   // no mapping: no further hardware queues
+  if (ok && cfg->image_width > 0) ok = mk(&h->s_img, kImg);
+  if (!ok) { set_err("hipStreamCreate failed"); return VLOAM_ERR_HIP; }
+  return VLOAM_OK;
+}
+
+// 3. One allocation for all sessions, session 0 laid out and initialised, the others copied from it.  n_cus: the device's compute units,
+// from the one property query of vloam_create (a failed query fails the creation; there is no second query left to fall back from).
+static vloam_status init_sessions(vloam_handle* h, int n_sessions, int n_cus) {
+  // measure one session, then one allocation for all sessions (zeroed), then lay session 0 out for real
+  Arena dry;
+  TRY(handle_layout(h, dry));
+  // 2 MB granules + a skew: with arenas exactly 2 MB-aligned every session's hot words (bucket counters, cursors, table heads) share
+  // their low address bits, i.e. ALL sessions of a batch hit the same memory channels at the same time (k_lo_grid_count's atomics:
+  // 2 150 cycles of vector-memory latency alone, 8 160 at B = 16, profiles/r05_batch_pmc.txt); the skew walks the sessions over the channels
+  static const size_t skew = getenv("VLOAM_ARENA_SKEW") ? (size_t)atol(getenv("VLOAM_ARENA_SKEW")) & ~(size_t)255 : 0;
+  const size_t ss = ((dry.off + ((size_t)2 << 20) - 1) & ~(((size_t)2 << 20) - 1)) + (n_sessions > 1 ? skew : 0);
+  h->se.B = n_sessions;
+  h->se.ss = ss;
+  // The cooperative solves of a single sequence are placed on ONE XCD each (lm_solve.hip: lm_coop_block): 8 + 8 compute units of XCDs 2 and
+  // 6.  Several single-sequence handles in one process would crowd those two XCDs (and their solves wait for each other's compute
+  // units): only the first two alive get the placement, the others launch spread over the XCDs like before round 4.  Same arithmetic.
+  if (n_sessions == 1) { h->se.crowd = g_single_handles.fetch_add(1); h->counted_single = true; }
+  // ... and only on the device the placement was measured on: 256 compute units dealt round-robin to 8 XCDs (SPX mode).  Anything else
+  // (a CPX / NPS partition, a CU-masked context, another part) keeps the plain spread launch; and whatever the placement, a solve
+  // whose workgroups do not end up resident together degrades to one workgroup instead of failing (lm_solve.hip).
+  if (n_cus != 256) h->se.crowd = 1 << 20;
+  h->arena_bytes = ss * (size_t)n_sessions;
+  if (hipMalloc((void**)&h->arena, h->arena_bytes) != hipSuccess) {
+    set_err("hipMalloc of %zu MB for %d session(s) failed", h->arena_bytes >> 20, n_sessions); h->arena = nullptr; return VLOAM_ERR_HIP;
+  }
+  HIPCHK(hipMemsetAsync(h->arena, 0, h->arena_bytes, h->stream));
+  Arena A;
+  A.base = h->arena; A.cap = ss; A.dry = false;
+  TRY(handle_layout(h, A));
+  h->map.se = h->se;
+  h->vo.se = h->se;
+  // ---- initial state of session 0
+  for (int k = 0; k < vloam_handle::kSets; k++) {
+    int arm[4 * kMaxRings];
+    for (int q = 0; q < 4 * kMaxRings; q++) arm[q] = ((q / kMaxRings) & 1) ? -1 : INT_MAX;
+    HIPCHK(hipMemcpyAsync(h->grid[k].occ, arm, sizeof(arm), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+  }
+  LOState init;
+  memset(&init, 0, sizeof(init));
+  init.para_q[3] = 1.0; init.q_w_curr[3] = 1.0; init.prior_q[3] = 1.0;  // laser_odometry.cpp:80-90
+  tf_identity(&init.tf.base_T_cam0); tf_identity(&init.tf.velo_T_cam0); tf_identity(&init.tf.cam0_curr_T_cam0_last);  // visual_odometry.cpp:73-74
+  tf_identity(&init.tf.cam0_curr_LOT_cam0_prev); tf_identity(&init.tf.world_VOT_base_last);                            // vloam_tf.cpp:10-11
+  HIPCHK(hipMemcpyAsync(h->lo, &init, sizeof(init), hipMemcpyHostToDevice, h->stream));
+  if (hipHostMalloc((void**)&h->ring_watch, sizeof(int) * 2 * kMaxBatch, hipHostMallocMapped) != hipSuccess) { h->ring_watch = nullptr; set_err("hipHostMalloc failed"); return VLOAM_ERR_HIP; }
+  for (int b = 0; b < 2 * kMaxBatch; b++) h->ring_watch[b] = 0;
+  if (hipHostMalloc((void**)&h->coop_flag, sizeof(int), hipHostMallocMapped) != hipSuccess) { h->coop_flag = nullptr; set_err("hipHostMalloc failed"); return VLOAM_ERR_HIP; }
+  *h->coop_flag = 0;
+  h->lo_F.host_degraded = h->coop_flag; h->map.F[0].host_degraded = h->coop_flag; h->map.F[1].host_degraded = h->coop_flag;
+  {
+    // patience of the workgroups of a cooperative solve (polls before one gives up on its partners, ~0.2 s by default): read ONCE per handle,
+    // here — not on the enqueue path, where a getenv per launch would also race a host thread's setenv.  Tests force the degraded path
+    // with VLOAM_LM_SPIN_LIMIT=1; anything below 1 (a typo, an empty string) would degrade every solve for good and means "default".
+    const char* e = getenv("VLOAM_LM_SPIN_LIMIT");
+    const int v = e ? atoi(e) : 0;
+    const int limit = v >= 1 ? v : (1 << 18);
+    h->lo_F.spin_limit = limit; h->map.F[0].spin_limit = limit; h->map.F[1].spin_limit = limit; h->vo.F.spin_limit = limit;
+  }
+  if (map_init(&h->map, h->stream) != VLOAM_OK) { set_err("map_init failed: %s", hipGetErrorString(hipGetLastError())); return VLOAM_ERR_HIP; }
+  {
+    // sync words of the three cooperative solves (odometry, mapping outer rounds): the fastest of 48 candidate lines, probed
+    // on session 0 (the other sessions' arenas start on 2 MB boundaries: same low address bits)
+    int order[kSyncCand];
+    if (lm_sync_calibrate(h->stream, h->sync_pool, kSyncCand - 1, kSyncStride, order) != 0) { set_err("lm_sync_calibrate failed"); return VLOAM_ERR_HIP; }
+    auto slot = [&](int r) { return reinterpret_cast<double*>(reinterpret_cast<char*>(h->sync_pool) + kSyncStride * (size_t)order[r]); };
+    h->lo_F.gsync = slot(0);
+    h->map.F[0].gsync = slot(1);
+    h->map.F[1].gsync = slot(2);
+  }
+  for (int k = 0; k < 6; k++) HIPCHK(hipEventCreate(&h->ev[k]));
+  for (int k = 0; k < vloam_handle::kSets; k++) {
+    HIPCHK(hipEventCreateWithFlags(&h->ev_sr[k], hipEventDisableTiming));
+    HIPCHK(hipEventCreateWithFlags(&h->ev_lo[k], hipEventDisableTiming | hipEventBlockingSync));   // the host throttle sleeps on these
+    HIPCHK(hipEventCreateWithFlags(&h->ev_map[k], hipEventDisableTiming | hipEventBlockingSync));
+    HIPCHK(hipEventCreateWithFlags(&h->ev_stack[k], hipEventDisableTiming));
+    HIPCHK(hipEventCreateWithFlags(&h->ev_vo[k], hipEventDisableTiming));
+    HIPCHK(hipEventCreateWithFlags(&h->ev_img[k], hipEventDisableTiming));
+  }
+  HIPCHK(hipStreamSynchronize(h->stream));
+  // ---- the other sessions start as byte-for-byte copies of session 0
+  for (int b = 1; b < n_sessions; b++)
+    HIPCHK(hipMemcpyAsync(h->arena + (size_t)b * ss, h->arena, dry.off, hipMemcpyDeviceToDevice, h->stream));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  return VLOAM_OK;
+}
 
 extern "C" {
 
@@ -303,39 +462,8 @@ vloam_status vloam_create_batch(const vloam_config* cfg, int device, int n_sessi
 
 vloam_status vloam_create_with_limits(const vloam_config* cfg, const vloam_limits* lim, int device, int n_sessions, vloam_handle** out) {
   if (!cfg || !out) { set_err("null argument"); return VLOAM_ERR_INVALID; }
-  int surf_cap = kStackCapSurf;
-  if (lim) {
-    const int S = lim->max_surf_stack_points;
-    const bool size_ok = lim->struct_size == 0 || lim->struct_size >= (int)sizeof(vloam_limits);
-    const bool value_ok = S == 0 || S == kStackCapSurf || (S > kStackCapSurf && S <= kStackCapSurfMax && S % kStackCapSurfStep == 0);
-    if (!size_ok || !value_ok || (S > kStackCapSurf && S > cfg->max_points)) {   // (the default holds whatever max_points is, as it always has)
-      set_err("vloam_limits: max_surf_stack_points must be 0 or %d (default), or a multiple of %d up to %d, and at most max_points; struct_size 0 or >= %d",
-              kStackCapSurf, kStackCapSurfStep, kStackCapSurfMax, (int)sizeof(vloam_limits));
-      return VLOAM_ERR_INVALID;
-    }
-    if (S != 0) surf_cap = S;
-  }
-  if (n_sessions < 1 || n_sessions > kMaxBatch) { set_err("n_sessions must be 1..%d", kMaxBatch); return VLOAM_ERR_INVALID; }
-  if (cfg->scan_line != 16 && cfg->scan_line != 32 && cfg->scan_line != 64) {
-    set_err("only support velodyne with 16, 32 or 64 scan line!");  // scan_registration.cpp:54-58
-    return VLOAM_ERR_INVALID;
-  }
-  if (cfg->max_points < 64 || cfg->max_points > (1 << 24) || cfg->max_frames < 1 || cfg->mapping_skip_frame < 1) {  // 24-bit point tags
-    set_err("bad capacity"); return VLOAM_ERR_INVALID;
-  }
-  if (cfg->max_ring_points != 0 && (cfg->max_ring_points < kMaxRingLen || cfg->max_ring_points > kMaxRingLenLong)) {
-    set_err("max_ring_points must be 0 or %d (default) .. %d", kMaxRingLen, kMaxRingLenLong); return VLOAM_ERR_INVALID;
-  }
-  // laser_mapping.cpp:95-101 takes any leaf; the reference's launch files use 0.2 / 0.4 (VLP-16, HDL-32) and 0.4 / 0.8 (KITTI).  Here the
-  // position of a voxel in the gathered map cloud (the 5-NN tie rank) is a 32-bit mixed-radix number: 75 cubes x radix^3 voxels.
-  for (const float leaf : {cfg->mapping_line_resolution, cfg->mapping_plane_resolution}) {
-    const double nv = leaf > 0.f ? (double)vox_radix(1.0f / leaf) : 1e9;
-    if (!(leaf > 0.f) || 75.0 * nv * nv * nv >= 4294967295.0) { set_err("mapping resolutions below 0.132 m are not supported"); return VLOAM_ERR_INVALID; }
-  }
-  if (cfg->image_width < 0 || cfg->image_height < 0 || (long long)cfg->image_width * cfg->image_height > (1ll << 24) ||
-      ((cfg->image_width > 0) != (cfg->image_height > 0)) || (cfg->image_width > 0 && (cfg->image_width < 2 * kImgWin || cfg->image_height < 2 * kImgWin))) {
-    set_err("image_width x image_height must be 0 x 0 (no image front-end) or between %d x %d and 2^24 pixels", 2 * kImgWin, 2 * kImgWin); return VLOAM_ERR_INVALID;
-  }
+  int surf_cap = 0;
+  TRY(validate_create(cfg, lim, n_sessions, &surf_cap));
   // A handle drives two to six HIP streams that must run side by side (scan registration | odometry [| mapping | scan-feature VoxelGrid]
   // [| images] [| host-sweep copies]).  GPU_MAX_HW_QUEUES (read by the runtime when it initialises: it belongs to the HOST's environment, and a
   // library must not setenv() behind a multi-threaded host) caps each of the runtime's three priority pools of hardware queues; the handle
@@ -357,14 +485,12 @@ vloam_status vloam_create_with_limits(const vloam_config* cfg, const vloam_limit
   }
   if (device < 0 || device >= ndev) { set_err("device %d out of range (%d visible)", device, ndev); return VLOAM_ERR_NO_DEVICE; }
   HIPCHK(hipSetDevice(device));
-  {
-    // co-residency of the cooperative solves (c_api.h): 4 + 6 workgroups per session may have to be resident at once
-    hipDeviceProp_t prop;
-    HIPCHK(hipGetDeviceProperties(&prop, device));
-    if (10 * n_sessions > prop.multiProcessorCount) {
-      set_err("%d sessions need %d co-resident solver workgroups, the device has %d compute units", n_sessions, 10 * n_sessions, prop.multiProcessorCount);
-      return VLOAM_ERR_CAPACITY;
-    }
+  // co-residency of the cooperative solves (c_api.h): 4 + 6 workgroups per session may have to be resident at once
+  hipDeviceProp_t prop;
+  HIPCHK(hipGetDeviceProperties(&prop, device));
+  if (10 * n_sessions > prop.multiProcessorCount) {
+    set_err("%d sessions need %d co-resident solver workgroups, the device has %d compute units", n_sessions, 10 * n_sessions, prop.multiProcessorCount);
+    return VLOAM_ERR_CAPACITY;
   }
   vloam_handle* h = new vloam_handle;
   h->cfg = *cfg;
@@ -372,151 +498,10 @@ vloam_status vloam_create_with_limits(const vloam_config* cfg, const vloam_limit
   h->map.surf_cap = surf_cap;   // before the layout: the mapping stage's arrays are sized by it (map_layout)
   h->device = device;
   *out = nullptr;
-  vloam_status st = VLOAM_OK;
-  do {
-    {
-      // the plan's pools as HIP priorities; VLOAM_STREAM_PRIO = "sr,lo,map,ds[,img]" (experiment: 0 = normal, 1 = the device's highest, -1 =
-      // its lowest) overrides them
-      int lo_p = 0, hi_p = 0;
-      if (hipDeviceGetStreamPriorityRange(&lo_p, &hi_p) != hipSuccess) { lo_p = hi_p = 0; }   // lo_p = numerically greatest = lowest priority
-      const int pool_prio[vloam_plan::kPools] = {0, hi_p, lo_p};
-      for (int w = 0; w < vloam_plan::kStreams; w++) h->prio[w] = pool_prio[plan.pool[w]];
-      if (const char* e = getenv("VLOAM_STREAM_PRIO")) {
-        using namespace vloam_plan;
-        int pr[5] = {0, 0, 0, 0, 0};
-        sscanf(e, "%d,%d,%d,%d,%d", &pr[0], &pr[1], &pr[2], &pr[3], &pr[4]);
-        const int which[5] = {kSR, kLO, kMap, kDS, kImg};
-        for (int k = 0; k < 5; k++) h->prio[which[k]] = pr[k] > 0 ? hi_p : (pr[k] < 0 ? lo_p : 0);
-      }
-      // VLOAM_RESERVE_CUS = "n[,stride]" (experiment): the scan-registration, odometry and VoxelGrid streams are created with a CU mask that
-      // leaves n compute units (every stride-th bit from 0) to the mapping stream alone
-      int rsv = 0, rstride = 1;
-      if (const char* e = getenv("VLOAM_RESERVE_CUS")) sscanf(e, "%d,%d", &rsv, &rstride);
-      hipDeviceProp_t prop;
-      const int ncu = (rsv > 0 && hipGetDeviceProperties(&prop, device) == hipSuccess) ? prop.multiProcessorCount : 0;
-      auto mk = [&](hipStream_t* s, int which) {
-        if (ncu > 0 && which != vloam_plan::kMap) {
-          uint32_t mask[16];
-          for (int w = 0; w < 16; w++) mask[w] = 0;
-          for (int c = 0; c < ncu && c < 512; c++) mask[c >> 5] |= 1u << (c & 31);
-          for (int k = 0, c = 0; k < rsv && c < ncu; k++, c += rstride) mask[c >> 5] &= ~(1u << (c & 31));
-          return hipExtStreamCreateWithCUMask(s, (uint32_t)((ncu + 31) / 32), mask) == hipSuccess;
-        }
-        return hipStreamCreateWithPriority(s, hipStreamNonBlocking, h->prio[which]) == hipSuccess;
-      };
-      // the runtime gives a stream its hardware queue when the stream is created, so the order matters (stream_plan.h).  plan.copy_first: the
-      // copy stream of the deferred host-sweep ring comes FIRST and is used once before any other stream of the handle has work — measured
-      // (tools/host_input_probe.py, extring / extring_late; profiles/r06_host_input.txt) a copy stream that gets its hardware queue after the
-      // compute streams runs host-fed sequences at 3 900 - 4 600 scans/s, one that got it before them at 5 650
-      using namespace vloam_plan;
-      if (plan.copy_first && !g_stage_inline && !cfg->timing) {
-        if (hipStreamCreateWithPriority(&h->s_copy, hipStreamNonBlocking, h->prio[kCopy]) != hipSuccess) { set_err("hipStreamCreate failed"); st = VLOAM_ERR_HIP; break; }
-        static int warm_src = 0;
-        int* warm_dst = nullptr;
-        if (hipMalloc(&warm_dst, sizeof(int)) == hipSuccess) {
-          (void)hipMemcpyAsync(warm_dst, &warm_src, sizeof(int), hipMemcpyHostToDevice, h->s_copy);
-          (void)hipStreamSynchronize(h->s_copy);
-          (void)hipFree(warm_dst);
-        }
-      }
-      bool ok = mk(&h->stream, kSR) && mk(&h->s_lo, kLO);
-      if (ok && cfg->with_mapping) ok = mk(&h->s_map, kMap) && mk(&h->s_ds, kDS);   // no mapping: no further hardware queues
-      if (ok && cfg->image_width > 0) ok = mk(&h->s_img, kImg);
-      if (!ok) { set_err("hipStreamCreate failed"); st = VLOAM_ERR_HIP; break; }
-    }
-    if (sr_init() != hipSuccess) { set_err("sr_init failed (no gfx950 code object for this device?)"); st = VLOAM_ERR_HIP; break; }
-    if (cfg->image_width > 0 && img_init() != hipSuccess) { set_err("img_init failed"); st = VLOAM_ERR_HIP; break; }
-    auto body = [&]() -> vloam_status {
-      // 1. measure one session, 2. one allocation for all sessions (zeroed), 3. lay session 0 out for real
-      Arena dry;
-      vloam_status s = handle_layout(h, dry);
-      if (s != VLOAM_OK) return s;
-      // 2 MB granules + a skew: with arenas exactly 2 MB-aligned every session's hot words (bucket counters, cursors, table heads) share
-      // their low address bits, i.e. ALL sessions of a batch hit the same memory channels at the same time (k_lo_grid_count's atomics:
-      // 2 150 cycles of vector-memory latency alone, 8 160 at B = 16, profiles/r05_batch_pmc.txt); the skew walks the sessions over the channels
-      static const size_t skew = getenv("VLOAM_ARENA_SKEW") ? (size_t)atol(getenv("VLOAM_ARENA_SKEW")) & ~(size_t)255 : 0;
-      const size_t ss = ((dry.off + ((size_t)2 << 20) - 1) & ~(((size_t)2 << 20) - 1)) + (n_sessions > 1 ? skew : 0);
-      h->se.B = n_sessions;
-      h->se.ss = ss;
-      // The cooperative solves of a single sequence are placed on ONE XCD each (lm_solve.hip: lm_coop_block): 8 + 8 compute units of XCDs 2 and
-      // 6.  Several single-sequence handles in one process would crowd those two XCDs (and their solves wait for each other's compute
-      // units): only the first two alive get the placement, the others launch spread over the XCDs like before round 4.  Same arithmetic.
-      if (n_sessions == 1) { h->se.crowd = g_single_handles.fetch_add(1); h->counted_single = true; }
-      {
-        // ... and only on the device the placement was measured on: 256 compute units dealt round-robin to 8 XCDs (SPX mode).  Anything else
-        // (a CPX / NPS partition, a CU-masked context, another part) keeps the plain spread launch; and whatever the placement, a solve
-        // whose workgroups do not end up resident together degrades to one workgroup instead of failing (lm_solve.hip).
-        hipDeviceProp_t prop2;
-        if (hipGetDeviceProperties(&prop2, device) != hipSuccess || prop2.multiProcessorCount != 256) h->se.crowd = 1 << 20;
-      }
-      h->arena_bytes = ss * (size_t)n_sessions;
-      if (hipMalloc((void**)&h->arena, h->arena_bytes) != hipSuccess) {
-        set_err("hipMalloc of %zu MB for %d session(s) failed", h->arena_bytes >> 20, n_sessions); h->arena = nullptr; return VLOAM_ERR_HIP;
-      }
-      HIPCHK(hipMemsetAsync(h->arena, 0, h->arena_bytes, h->stream));
-      Arena A;
-      A.base = h->arena; A.cap = ss; A.dry = false;
-      s = handle_layout(h, A);
-      if (s != VLOAM_OK) return s;
-      h->map.se = h->se;
-      h->vo.se = h->se;
-      // ---- initial state of session 0
-      for (int k = 0; k < vloam_handle::kSets; k++) {
-        int arm[4 * kMaxRings];
-        for (int q = 0; q < 4 * kMaxRings; q++) arm[q] = ((q / kMaxRings) & 1) ? -1 : INT_MAX;
-        HIPCHK(hipMemcpyAsync(h->grid[k].occ, arm, sizeof(arm), hipMemcpyHostToDevice, h->stream));
-        HIPCHK(hipStreamSynchronize(h->stream));
-      }
-      LOState init;
-      memset(&init, 0, sizeof(init));
-      init.para_q[3] = 1.0; init.q_w_curr[3] = 1.0; init.prior_q[3] = 1.0;  // laser_odometry.cpp:80-90
-      tf_identity(&init.tf.base_T_cam0); tf_identity(&init.tf.velo_T_cam0); tf_identity(&init.tf.cam0_curr_T_cam0_last);  // visual_odometry.cpp:73-74
-      tf_identity(&init.tf.cam0_curr_LOT_cam0_prev); tf_identity(&init.tf.world_VOT_base_last);                            // vloam_tf.cpp:10-11
-      HIPCHK(hipMemcpyAsync(h->lo, &init, sizeof(init), hipMemcpyHostToDevice, h->stream));
-      if (hipHostMalloc((void**)&h->ring_watch, sizeof(int) * 2 * kMaxBatch, hipHostMallocMapped) != hipSuccess) { h->ring_watch = nullptr; set_err("hipHostMalloc failed"); return VLOAM_ERR_HIP; }
-      for (int b = 0; b < 2 * kMaxBatch; b++) h->ring_watch[b] = 0;
-      if (hipHostMalloc((void**)&h->coop_flag, sizeof(int), hipHostMallocMapped) != hipSuccess) { h->coop_flag = nullptr; set_err("hipHostMalloc failed"); return VLOAM_ERR_HIP; }
-      *h->coop_flag = 0;
-      h->lo_F.host_degraded = h->coop_flag; h->map.F[0].host_degraded = h->coop_flag; h->map.F[1].host_degraded = h->coop_flag;
-      {
-        // patience of the workgroups of a cooperative solve (polls before one gives up on its partners, ~0.2 s by default): read ONCE per handle,
-        // here — not on the enqueue path, where a getenv per launch would also race a host thread's setenv.  Tests force the degraded path
-        // with VLOAM_LM_SPIN_LIMIT=1; anything below 1 (a typo, an empty string) would degrade every solve for good and means "default".
-        const char* e = getenv("VLOAM_LM_SPIN_LIMIT");
-        const int v = e ? atoi(e) : 0;
-        const int limit = v >= 1 ? v : (1 << 18);
-        h->lo_F.spin_limit = limit; h->map.F[0].spin_limit = limit; h->map.F[1].spin_limit = limit; h->vo.F.spin_limit = limit;
-      }
-      s = map_init(&h->map, h->stream);
-      if (s != VLOAM_OK) { set_err("map_init failed: %s", hipGetErrorString(hipGetLastError())); return VLOAM_ERR_HIP; }
-      {
-        // sync words of the three cooperative solves (odometry, mapping outer rounds): the fastest of 48 candidate lines, probed
-        // on session 0 (the other sessions' arenas start on 2 MB boundaries: same low address bits)
-        int order[kSyncCand];
-        if (lm_sync_calibrate(h->stream, h->sync_pool, kSyncCand - 1, kSyncStride, order) != 0) { set_err("lm_sync_calibrate failed"); return VLOAM_ERR_HIP; }
-        auto slot = [&](int r) { return reinterpret_cast<double*>(reinterpret_cast<char*>(h->sync_pool) + kSyncStride * (size_t)order[r]); };
-        h->lo_F.gsync = slot(0);
-        h->map.F[0].gsync = slot(1);
-        h->map.F[1].gsync = slot(2);
-      }
-      for (int k = 0; k < 6; k++) HIPCHK(hipEventCreate(&h->ev[k]));
-      for (int k = 0; k < vloam_handle::kSets; k++) {
-        HIPCHK(hipEventCreateWithFlags(&h->ev_sr[k], hipEventDisableTiming));
-        HIPCHK(hipEventCreateWithFlags(&h->ev_lo[k], hipEventDisableTiming | hipEventBlockingSync));   // the host throttle sleeps on these
-        HIPCHK(hipEventCreateWithFlags(&h->ev_map[k], hipEventDisableTiming | hipEventBlockingSync));
-        HIPCHK(hipEventCreateWithFlags(&h->ev_stack[k], hipEventDisableTiming));
-        HIPCHK(hipEventCreateWithFlags(&h->ev_vo[k], hipEventDisableTiming));
-        HIPCHK(hipEventCreateWithFlags(&h->ev_img[k], hipEventDisableTiming));
-      }
-      HIPCHK(hipStreamSynchronize(h->stream));
-      // ---- the other sessions start as byte-for-byte copies of session 0
-      for (int b = 1; b < n_sessions; b++)
-        HIPCHK(hipMemcpyAsync(h->arena + (size_t)b * ss, h->arena, dry.off, hipMemcpyDeviceToDevice, h->stream));
-      HIPCHK(hipStreamSynchronize(h->stream));
-      return VLOAM_OK;
-    };
-    st = body();
-  } while (0);
+  vloam_status st = create_streams(h, plan, cfg);
+  if (st == VLOAM_OK && sr_init() != hipSuccess) { set_err("sr_init failed (no gfx950 code object for this device?)"); st = VLOAM_ERR_HIP; }
+  if (st == VLOAM_OK && cfg->image_width > 0 && img_init() != hipSuccess) { set_err("img_init failed"); st = VLOAM_ERR_HIP; }
+  if (st == VLOAM_OK) st = init_sessions(h, n_sessions, prop.multiProcessorCount);
   if (st != VLOAM_OK) { vloam_destroy(h); return st; }
   *out = h;
   return VLOAM_OK;
@@ -568,10 +553,12 @@ vloam_status vloam_reset_frame(vloam_handle* h) {
 
 // ------------------------------------------------------------------ stage enqueue helpers
 static inline int set_of(int frame) { return frame % vloam_handle::kSets; }
+// the sweep the getters show: the one in progress, or (between sweeps: finish_frame has counted it) the last finished one
+static inline int shown_frame(const vloam_handle* h) { return (h->stage == 0 && h->frame > 0) ? h->frame - 1 : h->frame; }
 static vloam_status drain_deferred(vloam_handle* h, int lag_lo, int lag_map);
 static vloam_status flush_pending(vloam_handle* h);
 static vloam_status sync_all(vloam_handle* h) {
-  { vloam_status s_ = drain_deferred(h, 0, 0); if (s_ != VLOAM_OK) return s_; }
+  TRY(drain_deferred(h, 0, 0));
   HIPCHK(hipStreamSynchronize(h->stream));
   HIPCHK(hipStreamSynchronize(h->s_lo));
   if (h->s_ds) HIPCHK(hipStreamSynchronize(h->s_ds));
@@ -580,21 +567,61 @@ static vloam_status sync_all(vloam_handle* h) {
   return VLOAM_OK;
 }
 
-static BatchIn one_sweep(const void* d_xyz_pad4, int n) {
+// ------------------------------------------------------------------ admission: what every entry point asks of its sweeps and images
+// One sweep per session (a single-sequence call passes the addresses of its two arguments).  Host sweeps are admitted by their entry point,
+// before anything is copied; device sweeps by enqueue_sr, which the deferred ring reaches a call later.  A null host sweep is a null
+// argument like any other (no message); a null device sweep says which session.
+static vloam_status check_sweeps(const vloam_handle* h, const void* const* ptrs, const int* n, bool device) {
+  for (int b = 0; b < h->se.B; b++) {
+    if (!ptrs[b]) { if (device) set_err("null sweep pointer for session %d", b); return VLOAM_ERR_INVALID; }
+    if (n[b] > h->cfg.max_points) { set_err("cloud of %d points exceeds max_points=%d", n[b], h->cfg.max_points); return VLOAM_ERR_CAPACITY; }
+    if (n[b] <= 0) { set_err("empty cloud"); return VLOAM_ERR_EMPTY; }
+  }
+  return VLOAM_OK;
+}
+static inline vloam_status check_host_sweeps(const vloam_handle* h, const float* const* xyz_pad4, const int* n) {
+  return check_sweeps(h, (const void* const*)xyz_pad4, n, false);
+}
+
+static vloam_status require_image_front_end(const vloam_handle* h) {
+  if (h->img.max_w == 0) { set_err("the handle was created without an image front-end (cfg.image_width / image_height)"); return VLOAM_ERR_ORDER; }
+  return VLOAM_OK;
+}
+// a host image, before it is uploaded
+static vloam_status check_host_image(const vloam_handle* h, int width, int height, int stride) {
+  TRY(require_image_front_end(h));
+  if (width <= 0 || height <= 0 || stride < width || width > h->img.max_w || height > h->img.max_h) {
+    set_err("bad image size (%d x %d; the handle was created for at most %d x %d)", width, height, h->img.max_w, h->img.max_h);
+    return VLOAM_ERR_INVALID;
+  }
+  return VLOAM_OK;
+}
+// what img_check / img_process refused (img_kernels.h)
+static void set_image_size_err(const vloam_handle* h, int width, int height, int stride) {
+  set_err("image front-end: bad image size (%d x %d, stride %d; capacity %d x %d, one size per sequence)", width, height, stride, h->img.max_w, h->img.max_h);
+}
+
+// the sweeps of one call, one per session, as the kernels take them
+static BatchIn batch_in(const vloam_handle* h, const void* const* ptrs, const int* n) {
   BatchIn bi;
   memset(&bi, 0, sizeof(bi));
-  bi.in[0] = (const float4*)d_xyz_pad4; bi.n[0] = n;
+  for (int b = 0; b < h->se.B; b++) { bi.in[b] = (const float4*)ptrs[b]; bi.n[b] = n[b]; }
   return bi;
 }
 
+// the mapping stage's VoxelGrid of the scan features of sweep `frame`, if it is a mapped sweep: it only needs the sweep's feature clouds, so
+// it runs on a stream of its own, off the mapping stream
+static vloam_status enqueue_scan_feature_grid(vloam_handle* h, const SRBuffers& bufs, int frame, int cur) {
+  if (!h->cfg.with_mapping || ((frame + 1) % h->cfg.mapping_skip_frame) != 0) return VLOAM_OK;
+  HIPCHK(hipStreamWaitEvent(h->s_ds, h->ev_sr[cur], 0));   // the feature clouds (ev_sr is bound to k_sr_compact); a live wait: on a queue of its own, or SR's (budget 1, or several handles alive at a small budget: stream_plan.h)
+  if (map_stack_enqueue(&h->map, h->s_ds, bufs, cur, &h->prof, h->ev_stack[cur]) != VLOAM_OK) { set_err("map_stack_enqueue failed"); return VLOAM_ERR_HIP; }
+  return VLOAM_OK;
+}
+
 static vloam_status enqueue_sr(vloam_handle* h, const BatchIn& bi) {
+  TRY(check_sweeps(h, (const void* const*)bi.in, bi.n, true));
   int n = 0;
-  for (int b = 0; b < h->se.B; b++) {
-    if (!bi.in[b]) { set_err("null sweep pointer for session %d", b); return VLOAM_ERR_INVALID; }
-    if (bi.n[b] <= 0) { set_err("empty cloud"); return VLOAM_ERR_EMPTY; }
-    if (bi.n[b] > h->cfg.max_points) { set_err("cloud of %d points exceeds max_points=%d", bi.n[b], h->cfg.max_points); return VLOAM_ERR_CAPACITY; }
-    n = bi.n[b] > n ? bi.n[b] : n;
-  }
+  for (int b = 0; b < h->se.B; b++) n = bi.n[b] > n ? bi.n[b] : n;
   if (h->frame >= h->cfg.max_frames) { set_err("trajectory log full (max_frames=%d)", h->cfg.max_frames); return VLOAM_ERR_CAPACITY; }
   const int k = h->frame, cur = set_of(k);
   // Set `cur` still holds sweep k - 3: read by odometry of sweeps k - 3 (current) and k - 2 (previous), mapping of sweep k - 3.
@@ -621,11 +648,7 @@ static vloam_status enqueue_sr(vloam_handle* h, const BatchIn& bi) {
   lo_grid_build_launch(h->stream, h->se, h->sr[cur].less_sharp, h->sr[cur].less_flat, h->sr[cur].S, h->grid[cur], &h->prof);
   HIPCHK(hipGetLastError());
   if (h->cfg.timing) HIPCHK(hipEventRecord(h->ev[1], h->stream));
-  // the mapping stage's VoxelGrid of the scan features only needs this sweep's clouds: run it here, off the mapping stream
-  if (h->cfg.with_mapping && ((k + 1) % h->cfg.mapping_skip_frame) == 0) {
-    HIPCHK(hipStreamWaitEvent(h->s_ds, h->ev_sr[cur], 0));   // the feature clouds (ev_sr is bound to k_sr_compact); a live wait: on a queue of its own, or SR's (budget 1, or several handles alive at a small budget: stream_plan.h)
-    if (map_stack_enqueue(&h->map, h->s_ds, h->sr[cur], cur, &h->prof, h->ev_stack[cur]) != VLOAM_OK) { set_err("map_stack_enqueue failed"); return VLOAM_ERR_HIP; }
-  }
+  TRY(enqueue_scan_feature_grid(h, h->sr[cur], k, cur));
   h->last_n_in = n;
   h->stage = 1;
   h->vo_frame[cur] = false;
@@ -636,8 +659,9 @@ static vloam_status enqueue_sr(vloam_handle* h, const BatchIn& bi) {
 // A cooperative solve that found its partners missing finished on one workgroup and said so in a host-mapped word: from the next enqueue on
 // this handle launches one-workgroup solves (no host synchronisation needed: a host that streams thousands of sweeps between two vloam_sync
 // calls pays the ~0.2 s wait once, not per solve).
+static inline void set_no_coop(vloam_handle* h) { h->se.no_coop = 1; h->map.se.no_coop = 1; h->vo.se.no_coop = 1; }
 static inline void poll_coop_flag(vloam_handle* h) {
-  if (!h->se.no_coop && h->coop_flag && __atomic_load_n(h->coop_flag, __ATOMIC_RELAXED)) { h->se.no_coop = 1; h->map.se.no_coop = 1; h->vo.se.no_coop = 1; }
+  if (!h->se.no_coop && h->coop_flag && __atomic_load_n(h->coop_flag, __ATOMIC_RELAXED)) set_no_coop(h);
 }
 
 static vloam_status enqueue_lo(vloam_handle* h, int frame) {
@@ -697,7 +721,7 @@ static vloam_status enqueue_map(vloam_handle* h, int frame) {
 // producing stage has normally finished, hipStreamWaitEvent on a completed event inserts nothing, and the ~11 us cross-stream
 // barrier packet disappears from the stream that bounds the throughput.  Everything that reads results drains first (sync_all).
 static vloam_status drain_deferred(vloam_handle* h, int lag_lo, int lag_map) {
-  if (lag_lo == 0 && lag_map == 0) { vloam_status s0 = flush_pending(h); if (s0 != VLOAM_OK) return s0; }   // a full drain: the host sweep still in flight first
+  if (lag_lo == 0 && lag_map == 0) TRY(flush_pending(h));   // a full drain: the host sweep still in flight first
   while (h->lo_done < h->frame - lag_lo) {
     const double t0 = g_host_prof ? now_s() : 0.0;
     vloam_status s = enqueue_lo(h, h->lo_done);
@@ -719,8 +743,7 @@ static vloam_status drain_deferred(vloam_handle* h, int lag_lo, int lag_map) {
 
 static vloam_status finish_frame(vloam_handle* h) {
   if (h->cfg.timing) {  // per-stage times need the sweep drained: timing mode gives up the overlap between sweeps
-    vloam_status s = sync_all(h);
-    if (s != VLOAM_OK) return s;
+    TRY(sync_all(h));
     float ms = 0;
     HIPCHK(hipEventElapsedTime(&ms, h->ev[0], h->ev[1])); h->stage_ms[0] += ms;
     HIPCHK(hipEventElapsedTime(&ms, h->ev[2], h->ev[3])); h->stage_ms[1] += ms;
@@ -747,7 +770,10 @@ static vloam_status finish_frame(vloam_handle* h) {
 //     KERNEL reading the pinned buffer (49 GB/s) slows every kernel beside it by ~45 us (profiles/r06_host_input.txt).  Both are gone.
 // Pageable source memory: hipMemcpyAsync has taken its copy when it returns (the caller may reuse the buffer at once).  Pinned source
 // memory (hipHostMalloc / hipHostRegister) is read by DMA later: it must stay unchanged until the next vloam_sync() (c_api.h).
-static vloam_status stage_sweep(vloam_handle* h, int b, const float* xyz_pad4, int n, const float4** d_out) {
+
+// The inline form, session b of a call.  Whatever host sweep is still pending goes first, once per call: it is older than this call's sweep.
+static vloam_status stage_inline(vloam_handle* h, int b, const float* xyz_pad4, int n, const void** d_out) {
+  if (b == 0) TRY(flush_pending(h));
   float4* dst = (float4*)((char*)(h->d_in + (size_t)vloam_handle::kInRing * (size_t)h->cfg.max_points) + (size_t)b * h->se.ss);
   HIPCHK(hipMemcpyAsync(dst, xyz_pad4, (size_t)n * sizeof(float4), hipMemcpyHostToDevice, h->stream));
   *d_out = dst;
@@ -775,50 +801,42 @@ static vloam_status host_scan_deferred(vloam_handle* h, const float* const* xyz_
   // host side.  The slot's reader was enqueued kInRing - 1 calls ago; it can still be running while the host sprints ahead at the start of a
   // burst (measured: without this wait the last pose of a 300-sweep run changes from run to run)
   if (h->in_reader[slot]) HIPCHK(hipEventSynchronize(h->in_reader[slot]));
-  BatchIn bi;
-  memset(&bi, 0, sizeof(bi));
+  const void* d[kMaxBatch];
   for (int b = 0; b < h->se.B; b++) {
     float4* dst = (float4*)((char*)(h->d_in + (size_t)slot * (size_t)h->cfg.max_points) + (size_t)b * h->se.ss);
     HIPCHK(hipMemcpyAsync(dst, xyz_pad4[b], (size_t)n[b] * sizeof(float4), hipMemcpyHostToDevice, h->s_copy));
-    bi.in[b] = dst; bi.n[b] = n[b];
+    d[b] = dst;
   }
   HIPCHK(hipEventRecord(h->ev_in_copied[slot], h->s_copy));
   const vloam_status st = flush_pending(h);   // the sweep before this one
-  h->pend.bi = bi; h->pend.slot = slot; h->pend.valid = true;
+  h->pend.bi = batch_in(h, d, n); h->pend.slot = slot; h->pend.valid = true;
   return st;
 }
 static_assert(vloam_handle::kInRing < vloam_handle::kSets, "a slot's reader event (per buffer set) must not be re-recorded before the slot is reused");
-// the inline form's brackets around a call's copies: whatever host sweep is still pending goes first (it is older than this call's sweep)
-static inline vloam_status stage_begin(vloam_handle* h) { return flush_pending(h); }
-static inline vloam_status stage_end(vloam_handle*) { return VLOAM_OK; }
-static inline vloam_status stage_release(vloam_handle*, vloam_status call_status) { return call_status; }
-#define STAGE_ONE(h, xyz, n, dptr)                                                                              \
-  const float4* dptr = nullptr;                                                                                 \
-  { vloam_status s_ = flush_pending(h); if (s_ == VLOAM_OK) s_ = stage_sweep(h, 0, xyz, n, &dptr); if (s_ != VLOAM_OK) return s_; }
 
 // ------------------------------------------------------------------ stage-wise API (façade order)
 vloam_status vloam_scan_registration_device(vloam_handle* h, const void* d_xyz_pad4, int n) {
   if (!h || !d_xyz_pad4) return VLOAM_ERR_INVALID;
   SINGLE_SESSION_ONLY(h);
   HIPCHK(hipSetDevice(h->device));
-  if (h->stage == 2) { vloam_status s = finish_frame(h); if (s != VLOAM_OK) return s; }  // previous sweep ended after LO (no mapping call)
-  { vloam_status s = drain_deferred(h, 0, 0); if (s != VLOAM_OK) return s; }               // stages owed by earlier vloam_process_scan calls
-  return enqueue_sr(h, one_sweep(d_xyz_pad4, n));
+  if (h->stage == 2) TRY(finish_frame(h));  // previous sweep ended after LO (no mapping call)
+  TRY(drain_deferred(h, 0, 0));               // stages owed by earlier vloam_process_scan calls
+  return enqueue_sr(h, batch_in(h, &d_xyz_pad4, &n));
 }
 
 vloam_status vloam_scan_registration(vloam_handle* h, const float* xyz_pad4, int n) {
   if (!h || !xyz_pad4) return VLOAM_ERR_INVALID;
-  if (n > h->cfg.max_points) { set_err("cloud of %d points exceeds max_points=%d", n, h->cfg.max_points); return VLOAM_ERR_CAPACITY; }
-  if (n <= 0) { set_err("empty cloud"); return VLOAM_ERR_EMPTY; }
   SINGLE_SESSION_ONLY(h);
+  TRY(check_host_sweeps(h, &xyz_pad4, &n));
   HIPCHK(hipSetDevice(h->device));
-  STAGE_ONE(h, xyz_pad4, n, d);
-  return stage_release(h, vloam_scan_registration_device(h, d, n));
+  const void* d = nullptr;
+  TRY(stage_inline(h, 0, xyz_pad4, n, &d));
+  return vloam_scan_registration_device(h, d, n);
 }
 
 static vloam_status read_sr_error(vloam_handle* h, int cur) {
   int err = 0;
-  { vloam_status s_ = sync_all(h); if (s_ != VLOAM_OK) return s_; }
+  TRY(sync_all(h));
   HIPCHK(hipMemcpy(&err, &SEL(h, h->sr[cur].S)->error, sizeof(int), hipMemcpyDeviceToHost));
   if (err & kErrEmpty) { set_err("no point survived NaN / minimum_range removal"); return VLOAM_ERR_EMPTY; }
   if (err & kErrRingTooLong) { set_err("a ring holds more than %d points", h->cfg.max_ring_points); return VLOAM_ERR_CAPACITY; }
@@ -828,9 +846,8 @@ static vloam_status read_sr_error(vloam_handle* h, int cur) {
 vloam_status vloam_get_features(vloam_handle* h, int which, float* xyzi4, int cap, int* n) {
   if (!h || !n) return VLOAM_ERR_INVALID;
   HIPCHK(hipSetDevice(h->device));
-  { vloam_status s_ = sync_all(h); if (s_ != VLOAM_OK) return s_; }   // (first: a host sweep still in flight is enqueued by this and counts)
-  // after finish_frame() the sweep just processed is frame-1
-  const int f = (h->stage == 0 && h->frame > 0) ? h->frame - 1 : h->frame;
+  TRY(sync_all(h));   // (first: a host sweep still in flight is enqueued by this and counts)
+  const int f = shown_frame(h);
   const int cur = set_of(f);
   SRBuffers bsel = h->sr[cur];
   if (which == 11 && h->sub_cloud_frame == f) { bsel.cloud = h->sub.cloud; bsel.S = h->sub.S; }   // laserCloudFullRes as handed to LaserMapping::input
@@ -858,7 +875,7 @@ vloam_status vloam_get_map(vloam_handle* h, float* xyzi4, long long cap, long lo
   if (!h || !n) return VLOAM_ERR_INVALID;
   if (!h->cfg.with_mapping) { *n = 0; return VLOAM_OK; }
   HIPCHK(hipSetDevice(h->device));
-  { vloam_status s_ = sync_all(h); if (s_ != VLOAM_OK) return s_; }
+  TRY(sync_all(h));
   return map_export(&h->map, h->s_map, xyzi4, cap, n);
 }
 
@@ -866,7 +883,7 @@ vloam_status vloam_set_lo_prior(vloam_handle* h, const double q[4], const double
   if (!h || !q || !t) return VLOAM_ERR_INVALID;
   SINGLE_SESSION_ONLY(h);
   HIPCHK(hipSetDevice(h->device));
-  { vloam_status s_ = drain_deferred(h, 0, 0); if (s_ != VLOAM_OK) return s_; }  // the prior belongs to the NEXT sweep's odometry
+  TRY(drain_deferred(h, 0, 0));  // the prior belongs to the NEXT sweep's odometry
   double buf[7] = {q[0], q[1], q[2], q[3], t[0], t[1], t[2]};
   HIPCHK(hipMemcpyAsync(h->lo->prior_q, buf, sizeof(buf), hipMemcpyHostToDevice, h->s_lo));
   HIPCHK(hipStreamSynchronize(h->s_lo));
@@ -896,10 +913,9 @@ vloam_status vloam_set_odometry_input(vloam_handle* h, const float* laserCloud, 
     static const char* const names[5] = {"laserCloud (cloud 0)", "cornerPointsSharp (cloud 1)", "cornerPointsLessSharp (cloud 2)", "surfPointsFlat (cloud 3)",
                                          "surfPointsLessFlat (cloud 4)"};
     static const bool walked[5] = {false, false, true, false, true};
-    vloam_status s_ = check_stage_clouds("vloam_set_odometry_input", 5, names, src, n, walked);
-    if (s_ != VLOAM_OK) return s_;
+    TRY(check_stage_clouds("vloam_set_odometry_input", 5, names, src, n, walked));
   }
-  { vloam_status s_ = sync_all(h); if (s_ != VLOAM_OK) return s_; }
+  TRY(sync_all(h));
   const int cur = set_of(h->frame);
   const SRBuffers& b = h->sr[cur];
   float4* dst[5] = {b.cloud, b.sharp, b.less_sharp, b.flat, b.less_flat};
@@ -908,10 +924,7 @@ vloam_status vloam_set_odometry_input(vloam_handle* h, const float* laserCloud, 
   if (src[2] || src[4]) {
     lo_grid_build_launch(h->stream, h->se, b.less_sharp, b.less_flat, b.S, h->grid[cur], &h->prof);
     HIPCHK(hipEventRecord(h->ev_sr[cur], h->stream));
-    if (h->cfg.with_mapping && ((h->frame + 1) % h->cfg.mapping_skip_frame) == 0) {
-      HIPCHK(hipStreamWaitEvent(h->s_ds, h->ev_sr[cur], 0));
-      if (map_stack_enqueue(&h->map, h->s_ds, b, cur, &h->prof, h->ev_stack[cur]) != VLOAM_OK) { set_err("map_stack_enqueue failed"); return VLOAM_ERR_HIP; }
-    }
+    TRY(enqueue_scan_feature_grid(h, b, h->frame, cur));
   } else HIPCHK(hipEventRecord(h->ev_sr[cur], h->stream));
   HIPCHK(hipGetLastError());
   return VLOAM_OK;
@@ -922,8 +935,8 @@ vloam_status vloam_set_odometry_input(vloam_handle* h, const float* laserCloud, 
 vloam_status vloam_get_odometry_pose(vloam_handle* h, double q_w[4], double t_w[3]) {
   if (!h) return VLOAM_ERR_INVALID;
   HIPCHK(hipSetDevice(h->device));
-  { vloam_status s_ = sync_all(h); if (s_ != VLOAM_OK) return s_; }
-  const int f = (h->stage == 0 && h->frame > 0) ? h->frame - 1 : h->frame;
+  TRY(sync_all(h));
+  const int f = shown_frame(h);
   double row[7] = {0, 0, 0, 1, 0, 0, 0};
   if (f < h->cfg.max_frames && (h->stage == 2 || h->frame > 0)) HIPCHK(hipMemcpy(row, SEL(h, h->traj) + (size_t)f * 14, sizeof(row), hipMemcpyDeviceToHost));
   if (q_w) memcpy(q_w, row, sizeof(double) * 4);
@@ -948,10 +961,9 @@ vloam_status vloam_set_mapping_input(vloam_handle* h, const float* laserCloudCor
     static const bool walked[3] = {false, false, false};
     const float* src[3] = {laserCloudCornerLast, laserCloudSurfLast, laserCloudFullRes};
     const int n[3] = {n_corner, n_surf, n_full};
-    vloam_status s_ = check_stage_clouds("vloam_set_mapping_input", 3, names, src, n, walked);
-    if (s_ != VLOAM_OK) return s_;
+    TRY(check_stage_clouds("vloam_set_mapping_input", 3, names, src, n, walked));
   }
-  { vloam_status s_ = sync_all(h); if (s_ != VLOAM_OK) return s_; }
+  TRY(sync_all(h));
   const int frame = h->frame, cur = set_of(frame);
   const bool skip = ((frame + 1) % h->cfg.mapping_skip_frame) != 0;
   if (q_wodom_curr) {
@@ -1028,22 +1040,17 @@ vloam_status vloam_laser_mapping(vloam_handle* h, double q_map[4], double t_map[
 // waits of enqueue_sr (odometry of sweep k - 3, mapping of sweep k - 4) stay behind what is enqueued here
 static constexpr int kLagLO = 1, kLagMap = 2;
 static_assert(kLagLO <= vloam_handle::kSets - 2 && kLagMap <= vloam_handle::kSets - 1, "deferred stages must be enqueued before enqueue_sr waits for them");
-static vloam_status process_scan_batch(vloam_handle* h, const BatchIn& bi) {
+// what opens and closes a whole sweep, of either kind (process_scan_batch, process_frame_common)
+static vloam_status begin_sweep(vloam_handle* h) {
   HIPCHK(hipSetDevice(h->device));
-  { vloam_status s0 = flush_pending(h); if (s0 != VLOAM_OK) return s0; }   // (a device-pointer sweep behind a host sweep: the older one first)
-  if (h->stage == 2) { vloam_status s0 = finish_frame(h); if (s0 != VLOAM_OK) return s0; }
-  if (g_enqueue_order == 1 && !h->cfg.timing) {   // A/B: the deferred odometry / mapping of earlier sweeps first, then this sweep's scan registration
-    vloam_status s0 = drain_deferred(h, kLagLO - 1, kLagMap - 1);
-    if (s0 != VLOAM_OK) return s0;
-  }
-  const double ts0 = g_host_prof ? now_s() : 0.0;
-  vloam_status s = enqueue_sr(h, bi);
-  if (g_host_prof) { h->host_s[1] += now_s() - ts0; h->host_calls++; }
-  if (s != VLOAM_OK) return s;
+  TRY(flush_pending(h));   // a host sweep of vloam_process_scan still in flight: the older one first
+  if (h->stage == 2) TRY(finish_frame(h));
+  return VLOAM_OK;
+}
+static vloam_status end_sweep(vloam_handle* h) {
   if (h->cfg.timing) {  // per-stage times: nothing deferred, the sweep is drained in finish_frame
-    s = enqueue_lo(h, h->frame);
-    if (s != VLOAM_OK) return s;
-    if (h->cfg.with_mapping) { s = enqueue_map(h, h->frame); if (s != VLOAM_OK) return s; }
+    TRY(enqueue_lo(h, h->frame));
+    if (h->cfg.with_mapping) TRY(enqueue_map(h, h->frame));
     return finish_frame(h);
   }
   h->frame++;
@@ -1051,10 +1058,19 @@ static vloam_status process_scan_batch(vloam_handle* h, const BatchIn& bi) {
   return drain_deferred(h, kLagLO, kLagMap);
 }
 
+static vloam_status process_scan_batch(vloam_handle* h, const BatchIn& bi) {
+  TRY(begin_sweep(h));
+  const double ts0 = g_host_prof ? now_s() : 0.0;
+  const vloam_status s = enqueue_sr(h, bi);
+  if (g_host_prof) { h->host_s[1] += now_s() - ts0; h->host_calls++; }
+  if (s != VLOAM_OK) return s;
+  return end_sweep(h);
+}
+
 vloam_status vloam_process_scan_device(vloam_handle* h, const void* d_xyz_pad4, int n) {
   if (!h || !d_xyz_pad4) return VLOAM_ERR_INVALID;
   SINGLE_SESSION_ONLY(h);
-  return process_scan_batch(h, one_sweep(d_xyz_pad4, n));
+  return process_scan_batch(h, batch_in(h, &d_xyz_pad4, &n));
 }
 
 // Batched execution: one call advances ALL sessions of the handle by one sweep (session b gets d_xyz_pad4[b], n[b] points); every kernel
@@ -1062,42 +1078,23 @@ vloam_status vloam_process_scan_device(vloam_handle* h, const void* d_xyz_pad4, 
 // but the launch chain; results per session through vloam_select_session + the getters.
 vloam_status vloam_batch_process_scan_device(vloam_handle* h, const void* const* d_xyz_pad4, const int* n) {
   if (!h || !d_xyz_pad4 || !n) return VLOAM_ERR_INVALID;
-  BatchIn bi;
-  memset(&bi, 0, sizeof(bi));
-  for (int b = 0; b < h->se.B; b++) { bi.in[b] = (const float4*)d_xyz_pad4[b]; bi.n[b] = n[b]; }
-  return process_scan_batch(h, bi);
+  return process_scan_batch(h, batch_in(h, d_xyz_pad4, n));
 }
 
 vloam_status vloam_batch_process_scan(vloam_handle* h, const float* const* xyz_pad4, const int* n) {
   if (!h || !xyz_pad4 || !n) return VLOAM_ERR_INVALID;
+  TRY(check_host_sweeps(h, xyz_pad4, n));
   HIPCHK(hipSetDevice(h->device));
-  BatchIn bi;
-  memset(&bi, 0, sizeof(bi));
-  for (int b = 0; b < h->se.B; b++) {
-    if (!xyz_pad4[b]) return VLOAM_ERR_INVALID;
-    if (n[b] > h->cfg.max_points) { set_err("cloud of %d points exceeds max_points=%d", n[b], h->cfg.max_points); return VLOAM_ERR_CAPACITY; }
-    if (n[b] <= 0) { set_err("empty cloud"); return VLOAM_ERR_EMPTY; }
-  }
   if (!g_stage_inline && !h->cfg.timing) return host_scan_deferred(h, xyz_pad4, n);
-  { vloam_status s_ = stage_begin(h); if (s_ != VLOAM_OK) return s_; }
-  for (int b = 0; b < h->se.B; b++) {
-    vloam_status s_ = stage_sweep(h, b, xyz_pad4[b], n[b], &bi.in[b]);
-    if (s_ != VLOAM_OK) return stage_release(h, s_);
-    bi.n[b] = n[b];
-  }
-  { vloam_status s_ = stage_end(h); if (s_ != VLOAM_OK) return stage_release(h, s_); }
-  return stage_release(h, process_scan_batch(h, bi));
+  const void* d[kMaxBatch];
+  for (int b = 0; b < h->se.B; b++) TRY(stage_inline(h, b, xyz_pad4[b], n[b], &d[b]));
+  return vloam_batch_process_scan_device(h, d, n);
 }
 
 vloam_status vloam_process_scan(vloam_handle* h, const float* xyz_pad4, int n) {
   if (!h || !xyz_pad4) return VLOAM_ERR_INVALID;
-  if (n > h->cfg.max_points) { set_err("cloud of %d points exceeds max_points=%d", n, h->cfg.max_points); return VLOAM_ERR_CAPACITY; }
-  if (n <= 0) { set_err("empty cloud"); return VLOAM_ERR_EMPTY; }
   SINGLE_SESSION_ONLY(h);
-  HIPCHK(hipSetDevice(h->device));
-  if (!g_stage_inline && !h->cfg.timing) return host_scan_deferred(h, &xyz_pad4, &n);
-  STAGE_ONE(h, xyz_pad4, n, d);
-  return vloam_process_scan_device(h, d, n);
+  return vloam_batch_process_scan(h, &xyz_pad4, &n);
 }
 
 // ------------------------------------------------------------------ coupled VLOAM frame (configs[3])
@@ -1105,7 +1102,7 @@ vloam_status vloam_process_scan(vloam_handle* h, const float* xyz_pad4, int n) {
 vloam_status vloam_set_extrinsics(vloam_handle* h, const double base_T_cam0[16], const double velo_T_cam0[16]) {
   if (!h || !base_T_cam0 || !velo_T_cam0) return VLOAM_ERR_INVALID;
   HIPCHK(hipSetDevice(h->device));
-  { vloam_status s_ = sync_all(h); if (s_ != VLOAM_OK) return s_; }
+  TRY(sync_all(h));
   for (int b = 0; b < h->se.B; b++) {   // one sensor rig for all sessions of a batched handle
     LOState* lo = (LOState*)((char*)h->lo + (size_t)b * h->se.ss);
     VloamTfState tf;
@@ -1140,27 +1137,29 @@ static vloam_status upload_image(vloam_handle* h, const unsigned char* gray, int
   return VLOAM_OK;
 }
 
-static vloam_status process_frame_common(vloam_handle* h, const BatchIn& bi, const int* const* prev_uv, const int* const* curr_uv, const int* n_match,
-                                         const unsigned char* const* d_gray /* one image per session, or null */, int width, int height, int stride) {
+// One coupled frame of every session.  n_match == null: an image frame (d_gray: one device image per session), whose matches come from the
+// image front-end; otherwise n_match[b] pixel pairs prev_uv[b] -> curr_uv[b] in host memory.
+static vloam_status process_frame_common(vloam_handle* h, const void* const* d_xyz_pad4, const int* n, const int* const* prev_uv, const int* const* curr_uv,
+                                         const int* n_match, const void* const* d_gray, int width, int height, int stride) {
   if (!h->vo.have_calib || !h->have_extrinsics) { set_err("vloam_process_frame needs vloam_vo_set_calib and vloam_set_extrinsics first"); return VLOAM_ERR_ORDER; }
+  const int* const no_uv[kMaxBatch] = {};
+  const int no_match[kMaxBatch] = {};
+  if (!n_match) { prev_uv = curr_uv = no_uv; n_match = no_match; }
   for (int b = 0; b < h->se.B; b++) {
     if (n_match[b] < 0 || (n_match[b] > 0 && (!prev_uv[b] || !curr_uv[b]))) { set_err("bad match arrays for session %d", b); return VLOAM_ERR_INVALID; }
     if (n_match[b] > kVoMaxMatches) { set_err("%d matches exceed the capacity of %d", n_match[b], kVoMaxMatches); return VLOAM_ERR_CAPACITY; }
   }
-  if (d_gray) for (int b = 0; b < h->se.B; b++) if (!d_gray[b]) { set_err("null image pointer for session %d", b); return VLOAM_ERR_INVALID; }
-  if (d_gray && h->img.max_w == 0) { set_err("the handle was created without an image front-end (cfg.image_width / image_height)"); return VLOAM_ERR_ORDER; }
-  if (d_gray && img_check(&h->img, width, height, stride) != VLOAM_OK) {   // before anything of this frame is enqueued
-    set_err("image front-end: bad image size (%d x %d, stride %d; capacity %d x %d, one size per sequence)", width, height, stride, h->img.max_w, h->img.max_h);
-    return VLOAM_ERR_INVALID;
+  if (d_gray) {   // before anything of this frame is enqueued
+    for (int b = 0; b < h->se.B; b++) if (!d_gray[b]) { set_err("null image pointer for session %d", b); return VLOAM_ERR_INVALID; }
+    TRY(require_image_front_end(h));
+    if (img_check(&h->img, width, height, stride) != VLOAM_OK) { set_image_size_err(h, width, height, stride); return VLOAM_ERR_INVALID; }
   }
-  HIPCHK(hipSetDevice(h->device));
-  { vloam_status s0 = flush_pending(h); if (s0 != VLOAM_OK) return s0; }   // a host sweep of vloam_process_scan still in flight: the older one first
-  if (h->stage == 2) { vloam_status s0 = finish_frame(h); if (s0 != VLOAM_OK) return s0; }
+  TRY(begin_sweep(h));
+  const BatchIn bi = batch_in(h, d_xyz_pad4, n);
   vloam_status s = enqueue_sr(h, bi);
   if (s != VLOAM_OK) return s;
   const int k = h->frame, cur = set_of(k);
   // depth map + matches ride on the scan-registration stream (they only need the sweep); the solve itself belongs to the odometry stream
-  int no_match[kMaxBatch] = {0};
   s = vo_depth_enqueue(&h->vo, h->stream, bi, k, prev_uv, curr_uv, d_gray ? no_match : n_match, &h->prof);
   if (s != VLOAM_OK) { set_err("vo_depth_enqueue failed"); return s; }
   HIPCHK(hipEventRecord(h->ev_vo[cur], h->stream));
@@ -1174,8 +1173,8 @@ static vloam_status process_frame_common(vloam_handle* h, const BatchIn& bi, con
     for (int b = 0; b < h->se.B; b++) {
       const size_t so = (size_t)b * h->se.ss;
       ImgContext cb = h->img.rebased(so);
-      s = img_process(&cb, h->s_img, d_gray[b], width, height, stride, (int*)((char*)h->vo.d_prev_set[vset] + so), (int*)((char*)h->vo.d_curr_set[vset] + so), &h->prof);
-      if (s != VLOAM_OK) { set_err("image front-end: bad image size (%d x %d, stride %d; capacity %d x %d, one size per sequence)", width, height, stride, h->img.max_w, h->img.max_h); return s; }
+      s = img_process(&cb, h->s_img, (const unsigned char*)d_gray[b], width, height, stride, (int*)((char*)h->vo.d_prev_set[vset] + so), (int*)((char*)h->vo.d_curr_set[vset] + so), &h->prof);
+      if (s != VLOAM_OK) { set_image_size_err(h, width, height, stride); return s; }
       h->vo.n_match_set[vset].n[b] = k > 0 ? kImgMaxCorners : 0;
       after = cb;
     }
@@ -1183,21 +1182,13 @@ static vloam_status process_frame_common(vloam_handle* h, const BatchIn& bi, con
     HIPCHK(hipEventRecord(h->ev_img[cur], h->s_img));
     h->img_frame[cur] = true;
   }
-  if (h->cfg.timing) {
-    s = enqueue_lo(h, h->frame);
-    if (s != VLOAM_OK) return s;
-    if (h->cfg.with_mapping) { s = enqueue_map(h, h->frame); if (s != VLOAM_OK) return s; }
-    return finish_frame(h);
-  }
-  h->frame++;
-  h->stage = 0;
-  return drain_deferred(h, kLagLO, kLagMap);
+  return end_sweep(h);
 }
 
 vloam_status vloam_process_frame_device(vloam_handle* h, const void* d_xyz_pad4, int n, const int* prev_uv, const int* curr_uv, int n_match) {
   if (!h || !d_xyz_pad4 || n_match < 0 || (n_match > 0 && (!prev_uv || !curr_uv))) return VLOAM_ERR_INVALID;
   SINGLE_SESSION_ONLY(h);
-  return process_frame_common(h, one_sweep(d_xyz_pad4, n), &prev_uv, &curr_uv, &n_match, nullptr, 0, 0, 0);
+  return process_frame_common(h, &d_xyz_pad4, &n, &prev_uv, &curr_uv, &n_match, nullptr, 0, 0, 0);
 }
 
 // Batched coupled frames: one call advances ALL sessions of the handle by one VLOAM frame (session b: sweep d_xyz_pad4[b] with n[b] points,
@@ -1206,122 +1197,78 @@ vloam_status vloam_process_frame_device(vloam_handle* h, const void* d_xyz_pad4,
 vloam_status vloam_batch_process_frame_device(vloam_handle* h, const void* const* d_xyz_pad4, const int* n, const int* const* prev_uv,
                                               const int* const* curr_uv, const int* n_match) {
   if (!h || !d_xyz_pad4 || !n || !prev_uv || !curr_uv || !n_match) return VLOAM_ERR_INVALID;
-  BatchIn bi;
-  memset(&bi, 0, sizeof(bi));
-  for (int b = 0; b < h->se.B; b++) { bi.in[b] = (const float4*)d_xyz_pad4[b]; bi.n[b] = n[b]; }
-  return process_frame_common(h, bi, prev_uv, curr_uv, n_match, nullptr, 0, 0, 0);
+  return process_frame_common(h, d_xyz_pad4, n, prev_uv, curr_uv, n_match, nullptr, 0, 0, 0);
 }
 
 vloam_status vloam_batch_process_frame(vloam_handle* h, const float* const* xyz_pad4, const int* n, const int* const* prev_uv,
                                        const int* const* curr_uv, const int* n_match) {
   if (!h || !xyz_pad4 || !n || !prev_uv || !curr_uv || !n_match) return VLOAM_ERR_INVALID;
+  TRY(check_host_sweeps(h, xyz_pad4, n));
   HIPCHK(hipSetDevice(h->device));
-  BatchIn bi;
-  memset(&bi, 0, sizeof(bi));
-  for (int b = 0; b < h->se.B; b++) {
-    if (!xyz_pad4[b]) return VLOAM_ERR_INVALID;
-    if (n[b] > h->cfg.max_points) { set_err("cloud of %d points exceeds max_points=%d", n[b], h->cfg.max_points); return VLOAM_ERR_CAPACITY; }
-    if (n[b] <= 0) { set_err("empty cloud"); return VLOAM_ERR_EMPTY; }
-  }
-  { vloam_status s_ = stage_begin(h); if (s_ != VLOAM_OK) return s_; }
-  for (int b = 0; b < h->se.B; b++) {
-    vloam_status s_ = stage_sweep(h, b, xyz_pad4[b], n[b], &bi.in[b]);
-    if (s_ != VLOAM_OK) return stage_release(h, s_);
-    bi.n[b] = n[b];
-  }
-  { vloam_status s_ = stage_end(h); if (s_ != VLOAM_OK) return stage_release(h, s_); }
-  return stage_release(h, process_frame_common(h, bi, prev_uv, curr_uv, n_match, nullptr, 0, 0, 0));
+  const void* d[kMaxBatch];
+  for (int b = 0; b < h->se.B; b++) TRY(stage_inline(h, b, xyz_pad4[b], n[b], &d[b]));
+  return vloam_batch_process_frame_device(h, d, n, prev_uv, curr_uv, n_match);
 }
 
 vloam_status vloam_process_frame(vloam_handle* h, const float* xyz_pad4, int n, const int* prev_uv, const int* curr_uv, int n_match) {
-  if (!h || !xyz_pad4) return VLOAM_ERR_INVALID;
-  if (n > h->cfg.max_points) { set_err("cloud of %d points exceeds max_points=%d", n, h->cfg.max_points); return VLOAM_ERR_CAPACITY; }
-  if (n <= 0) { set_err("empty cloud"); return VLOAM_ERR_EMPTY; }
+  if (!h || !xyz_pad4 || n_match < 0 || (n_match > 0 && (!prev_uv || !curr_uv))) return VLOAM_ERR_INVALID;
   SINGLE_SESSION_ONLY(h);
-  if (n_match < 0 || (n_match > 0 && (!prev_uv || !curr_uv))) return VLOAM_ERR_INVALID;
-  HIPCHK(hipSetDevice(h->device));
-  STAGE_ONE(h, xyz_pad4, n, d);
-  return stage_release(h, vloam_process_frame_device(h, d, n, prev_uv, curr_uv, n_match));
+  return vloam_batch_process_frame(h, &xyz_pad4, &n, &prev_uv, &curr_uv, &n_match);
 }
 
 vloam_status vloam_process_frame_image_device(vloam_handle* h, const void* d_xyz_pad4, int n, const void* d_gray, int width, int height, int stride) {
   if (!h || !d_xyz_pad4 || !d_gray) return VLOAM_ERR_INVALID;
   SINGLE_SESSION_ONLY(h);
-  { const int* none = nullptr; const int zero = 0;
-    const unsigned char* g = (const unsigned char*)d_gray;
-    return process_frame_common(h, one_sweep(d_xyz_pad4, n), &none, &none, &zero, &g, width, height, stride); }
-}
-
-vloam_status vloam_process_frame_image(vloam_handle* h, const float* xyz_pad4, int n, const unsigned char* gray, int width, int height, int stride) {
-  if (!h || !xyz_pad4 || !gray) return VLOAM_ERR_INVALID;
-  SINGLE_SESSION_ONLY(h);   // before anything is enqueued: VLOAM_ERR_INVALID has no side effects (c_api.h)
-  if (n > h->cfg.max_points) { set_err("cloud of %d points exceeds max_points=%d", n, h->cfg.max_points); return VLOAM_ERR_CAPACITY; }
-  if (n <= 0) { set_err("empty cloud"); return VLOAM_ERR_EMPTY; }
-  if (h->img.max_w == 0) { set_err("the handle was created without an image front-end (cfg.image_width / image_height)"); return VLOAM_ERR_ORDER; }
-  if (width <= 0 || height <= 0 || stride < width || width > h->img.max_w || height > h->img.max_h) { set_err("bad image size (%d x %d; the handle was created for at most %d x %d)", width, height, h->img.max_w, h->img.max_h); return VLOAM_ERR_INVALID; }
-  HIPCHK(hipSetDevice(h->device));
-  STAGE_ONE(h, xyz_pad4, n, d);
-  { vloam_status s_ = upload_image(h, gray, width, height, stride); if (s_ != VLOAM_OK) return stage_release(h, s_); }
-  { const int* none = nullptr; const int zero = 0;
-    const unsigned char* g = h->img.staging;
-    return stage_release(h, process_frame_common(h, one_sweep(d, n), &none, &none, &zero, &g, width, height, width)); }
+  return process_frame_common(h, &d_xyz_pad4, &n, nullptr, nullptr, nullptr, &d_gray, width, height, stride);
 }
 
 // Batched coupled frames from raw inputs: session b gets sweep d_xyz_pad4[b] and the 8-bit grey image d_gray[b] (all images of one size).
 vloam_status vloam_batch_process_frame_image_device(vloam_handle* h, const void* const* d_xyz_pad4, const int* n, const void* const* d_gray, int width, int height,
                                                     int stride) {
   if (!h || !d_xyz_pad4 || !n || !d_gray) return VLOAM_ERR_INVALID;
-  BatchIn bi;
-  memset(&bi, 0, sizeof(bi));
-  const int* none[kMaxBatch];
-  int zero[kMaxBatch];
-  const unsigned char* g[kMaxBatch];
-  for (int b = 0; b < h->se.B; b++) { bi.in[b] = (const float4*)d_xyz_pad4[b]; bi.n[b] = n[b]; none[b] = nullptr; zero[b] = 0; g[b] = (const unsigned char*)d_gray[b]; }
-  return process_frame_common(h, bi, none, none, zero, g, width, height, stride);
+  return process_frame_common(h, d_xyz_pad4, n, nullptr, nullptr, nullptr, d_gray, width, height, stride);
 }
 
 vloam_status vloam_batch_process_frame_image(vloam_handle* h, const float* const* xyz_pad4, const int* n, const unsigned char* const* gray, int width, int height,
                                              int stride) {
   if (!h || !xyz_pad4 || !n || !gray) return VLOAM_ERR_INVALID;
-  if (h->img.max_w == 0) { set_err("the handle was created without an image front-end (cfg.image_width / image_height)"); return VLOAM_ERR_ORDER; }
-  if (width <= 0 || height <= 0 || stride < width || width > h->img.max_w || height > h->img.max_h) { set_err("bad image size (%d x %d; the handle was created for at most %d x %d)", width, height, h->img.max_w, h->img.max_h); return VLOAM_ERR_INVALID; }
+  for (int b = 0; b < h->se.B; b++) if (!gray[b]) return VLOAM_ERR_INVALID;
+  TRY(check_host_sweeps(h, xyz_pad4, n));   // before anything is enqueued: a refusal has no side effects (c_api.h)
+  TRY(check_host_image(h, width, height, stride));
   HIPCHK(hipSetDevice(h->device));
-  const void* d_in[kMaxBatch];
+  const void* d[kMaxBatch];
   const void* d_img[kMaxBatch];
   for (int b = 0; b < h->se.B; b++) {
-    if (!xyz_pad4[b] || !gray[b]) return VLOAM_ERR_INVALID;
-    if (n[b] > h->cfg.max_points) { set_err("cloud of %d points exceeds max_points=%d", n[b], h->cfg.max_points); return VLOAM_ERR_CAPACITY; }
-    if (n[b] <= 0) { set_err("empty cloud"); return VLOAM_ERR_EMPTY; }
+    TRY(stage_inline(h, b, xyz_pad4[b], n[b], &d[b]));
+    TRY(upload_image(h, gray[b], width, height, stride, b));
+    d_img[b] = h->img.staging + (size_t)b * h->se.ss;
   }
-  { vloam_status s_ = stage_begin(h); if (s_ != VLOAM_OK) return s_; }
-  for (int b = 0; b < h->se.B; b++) {
-    const float4* dst = nullptr;
-    { vloam_status s_ = stage_sweep(h, b, xyz_pad4[b], n[b], &dst); if (s_ != VLOAM_OK) return stage_release(h, s_); }
-    { vloam_status s_ = upload_image(h, gray[b], width, height, stride, b); if (s_ != VLOAM_OK) return stage_release(h, s_); }
-    d_in[b] = dst; d_img[b] = h->img.staging + (size_t)b * h->se.ss;
-  }
-  { vloam_status s_ = stage_end(h); if (s_ != VLOAM_OK) return stage_release(h, s_); }
-  return stage_release(h, vloam_batch_process_frame_image_device(h, d_in, n, d_img, width, height, width));
+  return vloam_batch_process_frame_image_device(h, d, n, d_img, width, height, width);
+}
+
+vloam_status vloam_process_frame_image(vloam_handle* h, const float* xyz_pad4, int n, const unsigned char* gray, int width, int height, int stride) {
+  if (!h || !xyz_pad4 || !gray) return VLOAM_ERR_INVALID;
+  SINGLE_SESSION_ONLY(h);
+  return vloam_batch_process_frame_image(h, &xyz_pad4, &n, &gray, width, height, stride);
 }
 
 // ---- the image front-end on its own (VisualOdometry::processImage, optical_flow_match = true)
 vloam_status vloam_vo_process_image_device(vloam_handle* h, const void* d_gray, int width, int height, int stride) {
   if (!h || !d_gray) return VLOAM_ERR_INVALID;
   SINGLE_SESSION_ONLY(h);
-  if (h->img.max_w == 0) { set_err("the handle was created without an image front-end (cfg.image_width / image_height)"); return VLOAM_ERR_ORDER; }
+  TRY(require_image_front_end(h));
   HIPCHK(hipSetDevice(h->device));
   // (no match outputs here: vloam_vo_solve uploads host matches into d_prev / d_curr on another stream; nothing consumes device-side matches in standalone mode)
-  vloam_status s = img_process(&h->img, h->s_img, (const unsigned char*)d_gray, width, height, stride, nullptr, nullptr, &h->prof);
-  if (s != VLOAM_OK) set_err("image front-end: bad image size (%d x %d, stride %d; capacity %d x %d, one size per sequence)", width, height, stride, h->img.max_w, h->img.max_h);
+  const vloam_status s = img_process(&h->img, h->s_img, (const unsigned char*)d_gray, width, height, stride, nullptr, nullptr, &h->prof);
+  if (s != VLOAM_OK) set_image_size_err(h, width, height, stride);
   return s;
 }
 
 vloam_status vloam_vo_process_image(vloam_handle* h, const unsigned char* gray, int width, int height, int stride) {
   if (!h || !gray) return VLOAM_ERR_INVALID;
-  if (h->img.max_w == 0) { set_err("the handle was created without an image front-end (cfg.image_width / image_height)"); return VLOAM_ERR_ORDER; }
-  if (width <= 0 || height <= 0 || stride < width || width > h->img.max_w || height > h->img.max_h) { set_err("bad image size (%d x %d; the handle was created for at most %d x %d)", width, height, h->img.max_w, h->img.max_h); return VLOAM_ERR_INVALID; }
+  TRY(check_host_image(h, width, height, stride));
   HIPCHK(hipSetDevice(h->device));
-  { vloam_status s_ = upload_image(h, gray, width, height, stride); if (s_ != VLOAM_OK) return s_; }
+  TRY(upload_image(h, gray, width, height, stride));
   return vloam_vo_process_image_device(h, h->img.staging, width, height, width);
 }
 
@@ -1331,7 +1278,7 @@ vloam_status vloam_vo_match_descriptors(vloam_handle* h, const unsigned char* de
                                         int select_knn, int* query_idx, int* train_idx, int cap, int* n_matches) {
   if (!h || !n_matches || cap < 0 || (n_prev > 0 && !desc_prev) || (n_curr > 0 && !desc_curr) || (cap > 0 && (!query_idx || !train_idx))) return VLOAM_ERR_INVALID;
   SINGLE_SESSION_ONLY(h);
-  if (h->img.max_w == 0) { set_err("the handle was created without an image front-end (cfg.image_width / image_height)"); return VLOAM_ERR_ORDER; }
+  TRY(require_image_front_end(h));
   HIPCHK(hipSetDevice(h->device));
   vloam_status s = img_match_descriptors(&h->img, h->s_img, desc_prev, n_prev, desc_curr, n_curr, bytes_per_desc, select_knn != 0, query_idx, train_idx, cap, n_matches);
   if (s == VLOAM_ERR_CAPACITY) set_err("more than %d descriptors", kImgMaxDesc);
@@ -1343,7 +1290,7 @@ static vloam_status img_results(vloam_handle* h, std::vector<float2>* corners, s
                                 bool* have_flow) {
   if (h->img.max_w == 0 || h->img.count < 0) { set_err("no image processed yet"); return VLOAM_ERR_ORDER; }
   HIPCHK(hipSetDevice(h->device));
-  { vloam_status s_ = sync_all(h); if (s_ != VLOAM_OK) return s_; }
+  TRY(sync_all(h));
   const ImgContext img = h->img.rebased((size_t)h->sel * h->se.ss);   // the session vloam_select_session chose
   int ierr = 0;
   HIPCHK(hipMemcpy(&ierr, img.error, sizeof(int), hipMemcpyDeviceToHost));
@@ -1366,8 +1313,7 @@ vloam_status vloam_vo_get_keypoints(vloam_handle* h, float* xy, int cap, int* n)
   std::vector<float2> c;
   int nc = 0;
   bool flow = false;
-  vloam_status s = img_results(h, &c, nullptr, nullptr, &nc, &flow);
-  if (s != VLOAM_OK) return s;
+  TRY(img_results(h, &c, nullptr, nullptr, &nc, &flow));
   *n = nc;
   for (int k = 0; k < nc && k < cap; k++) { xy[2 * k] = c[(size_t)k].x; xy[2 * k + 1] = c[(size_t)k].y; }
   return VLOAM_OK;
@@ -1379,8 +1325,7 @@ vloam_status vloam_vo_get_flow(vloam_handle* h, float* prev_xy, float* curr_xy, 
   std::vector<unsigned char> st;
   int nc = 0;
   bool flow = false;
-  vloam_status s = img_results(h, &c, &t, &st, &nc, &flow);
-  if (s != VLOAM_OK) return s;
+  TRY(img_results(h, &c, &t, &st, &nc, &flow));
   *n = flow ? nc : 0;
   for (int k = 0; k < *n && k < cap; k++) {
     prev_xy[2 * k] = c[(size_t)k].x; prev_xy[2 * k + 1] = c[(size_t)k].y;
@@ -1395,7 +1340,7 @@ static vloam_status orb_results(vloam_handle* h, int which /* 0: the latest imag
   if (h->img.max_w == 0 || h->img.count < 0) { set_err("no image processed yet"); return VLOAM_ERR_ORDER; }
   if (!h->img.orb) { set_err("the handle runs the optical-flow configuration (no ORB pattern set: vloam_vo_set_orb_pattern)"); return VLOAM_ERR_ORDER; }
   HIPCHK(hipSetDevice(h->device));
-  { vloam_status s_ = sync_all(h); if (s_ != VLOAM_OK) return s_; }
+  TRY(sync_all(h));
   const ImgContext img = h->img.rebased((size_t)h->sel * h->se.ss);
   const int slot = (h->img.count + (which ? 1 : 0)) % 2;
   int n = 0;
@@ -1413,9 +1358,9 @@ static vloam_status orb_results(vloam_handle* h, int which /* 0: the latest imag
 
 vloam_status vloam_vo_set_orb_pattern(vloam_handle* h, const signed char* pattern_256x4) {
   if (!h) return VLOAM_ERR_INVALID;
-  if (h->img.max_w == 0) { set_err("the handle was created without an image front-end (cfg.image_width / image_height)"); return VLOAM_ERR_ORDER; }
+  TRY(require_image_front_end(h));
   HIPCHK(hipSetDevice(h->device));
-  { vloam_status s_ = sync_all(h); if (s_ != VLOAM_OK) return s_; }
+  TRY(sync_all(h));
   if (h->img.count >= 0 && (pattern_256x4 != nullptr) != h->img.orb) { set_err("the image configuration cannot change in the middle of a sequence"); return VLOAM_ERR_ORDER; }
   const vloam_status s = img_set_orb_pattern(&h->img, h->stream, pattern_256x4, h->se.B, h->se.ss);
   if (s == VLOAM_ERR_INVALID) set_err("ORB pattern: a steered offset leaves the 31-pixel border the keypoints keep (|x|, |y| <= 30)");
@@ -1426,8 +1371,7 @@ vloam_status vloam_vo_get_descriptors(vloam_handle* h, float* xy, unsigned char*
   if (!h || !n || cap < 0) return VLOAM_ERR_INVALID;
   std::vector<float2> kp;
   std::vector<unsigned char> d;
-  vloam_status s = orb_results(h, 0, &kp, &d);
-  if (s != VLOAM_OK) return s;
+  TRY(orb_results(h, 0, &kp, &d));
   *n = (int)kp.size();
   const int m = *n < cap ? *n : cap;
   for (int k = 0; xy && k < m; k++) { xy[2 * k] = kp[(size_t)k].x; xy[2 * k + 1] = kp[(size_t)k].y; }
@@ -1463,8 +1407,7 @@ vloam_status vloam_vo_get_flow_matches(vloam_handle* h, int* prev_uv, int* curr_
   std::vector<unsigned char> st;
   int nc = 0, m = 0;
   bool flow = false;
-  vloam_status s = img_results(h, &c, &t, &st, &nc, &flow);
-  if (s != VLOAM_OK) return s;
+  TRY(img_results(h, &c, &t, &st, &nc, &flow));
   for (int k = 0; flow && k < nc; k++) {
     if (st[(size_t)k] != 1) continue;   // visual_odometry.cpp:298-308
     if (m < cap) {
@@ -1481,7 +1424,7 @@ vloam_status vloam_vo_get_flow_matches(vloam_handle* h, int* prev_uv, int* curr_
 vloam_status vloam_get_vo_trajectory(vloam_handle* h, int first, int count, double* poses7) {
   if (!h || !poses7 || first < 0 || count < 0 || first + count > h->frame + (h->pend.valid ? 1 : 0)) return VLOAM_ERR_INVALID;   // (a host sweep in flight is enqueued by the sync below)
   HIPCHK(hipSetDevice(h->device));
-  { vloam_status s_ = sync_all(h); if (s_ != VLOAM_OK) return s_; }
+  TRY(sync_all(h));
   if (count) HIPCHK(hipMemcpy(poses7, SEL(h, h->vo_traj) + (size_t)first * 7, sizeof(double) * 7 * (size_t)count, hipMemcpyDeviceToHost));
   return VLOAM_OK;
 }
@@ -1490,7 +1433,7 @@ vloam_status vloam_get_vo_trajectory(vloam_handle* h, int first, int count, doub
 vloam_status vloam_get_vo_result(vloam_handle* h, double angle_axis[3], double t[3], int counters32_22[2], double prior_q[4], double prior_t[3]) {
   if (!h) return VLOAM_ERR_INVALID;
   HIPCHK(hipSetDevice(h->device));
-  { vloam_status s_ = sync_all(h); if (s_ != VLOAM_OK) return s_; }
+  TRY(sync_all(h));
   double x[6];
   int cnt[2];
   LOState lo;
@@ -1506,7 +1449,7 @@ vloam_status vloam_get_vo_result(vloam_handle* h, double angle_axis[3], double t
 vloam_status vloam_sync(vloam_handle* h) {
   if (!h) return VLOAM_ERR_INVALID;
   HIPCHK(hipSetDevice(h->device));
-  { vloam_status s_ = sync_all(h); if (s_ != VLOAM_OK) return s_; }
+  TRY(sync_all(h));
   if (h->frame > 0) {
     // surface sticky device-side errors: scan-registration bits of ANY sweep since the last vloam_sync (k_sr_compact folds every
     // sweep's word into the handle's sticky word; reported once, then cleared), map / solver bits for good
@@ -1518,7 +1461,7 @@ vloam_status vloam_sync(vloam_handle* h) {
       // a cooperative solve found its partner workgroups missing and finished on one workgroup (lm_solve.hip): same answer, ~0.5 s late.
       // Whatever kept them apart (a CU-masked or partitioned device, another process' solves holding the compute units) is likely to last:
       // this handle launches one-workgroup solves from now on.
-      h->se.no_coop = 1; h->map.se.no_coop = 1; h->vo.se.no_coop = 1;
+      set_no_coop(h);
     }
     h->fallback_solves = fb;
     if (merr & kErrEmpty) { set_err("no point survived NaN / minimum_range removal in at least one sweep since the last vloam_sync"); return VLOAM_ERR_EMPTY; }
@@ -1547,7 +1490,7 @@ vloam_status vloam_sync(vloam_handle* h) {
 vloam_status vloam_get_trajectory(vloam_handle* h, int first, int count, double* poses14) {
   if (!h || !poses14 || first < 0 || count < 0 || first + count > h->frame + (h->pend.valid ? 1 : 0)) return VLOAM_ERR_INVALID;   // (a host sweep in flight is enqueued by the sync below)
   HIPCHK(hipSetDevice(h->device));
-  { vloam_status s_ = sync_all(h); if (s_ != VLOAM_OK) return s_; }
+  TRY(sync_all(h));
   if (count) HIPCHK(hipMemcpy(poses14, SEL(h, h->traj) + (size_t)first * 14, sizeof(double) * 14 * (size_t)count, hipMemcpyDeviceToHost));
   return VLOAM_OK;
 }
@@ -1574,8 +1517,9 @@ vloam_status vloam_vo_process_point_cloud(vloam_handle* h, const float* xyz_pad4
   SINGLE_SESSION_ONLY(h);
   if (n > h->cfg.max_points) return VLOAM_ERR_CAPACITY;
   HIPCHK(hipSetDevice(h->device));
-  STAGE_ONE(h, xyz_pad4, n, d);
-  return stage_release(h, vo_process_point_cloud(&h->vo, h->stream, d, n) == VLOAM_OK ? VLOAM_OK : VLOAM_ERR_HIP);
+  const void* d = nullptr;
+  TRY(stage_inline(h, 0, xyz_pad4, n, &d));
+  return vo_process_point_cloud(&h->vo, h->stream, (const float4*)d, n) == VLOAM_OK ? VLOAM_OK : VLOAM_ERR_HIP;
 }
 vloam_status vloam_vo_solve(vloam_handle* h, const int* prev_uv, const int* curr_uv, int n_match, double aa[3], double t[3], int counters[2]) {
   if (!h || !prev_uv || !curr_uv || !aa || !t || n_match < 0) return VLOAM_ERR_INVALID;
@@ -1597,8 +1541,8 @@ static vloam_status copy_out(const void* d_src, size_t bytes, void* buf, long lo
 vloam_status vloam_debug_get(vloam_handle* h, int stage, int item, void* buf, long long cap, long long* n) {
   if (!h) return VLOAM_ERR_INVALID;
   HIPCHK(hipSetDevice(h->device));
-  { vloam_status s_ = sync_all(h); if (s_ != VLOAM_OK) return s_; }
-  const int f = (h->stage == 0 && h->frame > 0) ? h->frame - 1 : h->frame;
+  TRY(sync_all(h));
+  const int f = shown_frame(h);
   const int cur = set_of(f);
   if (stage == 0) {
     SRBuffers b = h->sr[cur];
@@ -1656,7 +1600,7 @@ vloam_status vloam_debug_get(vloam_handle* h, int stage, int item, void* buf, lo
 vloam_status vloam_profile_kernel(vloam_handle* h, const char* name, int max_launches) {
   if (!h || !name) return VLOAM_ERR_INVALID;
   HIPCHK(hipSetDevice(h->device));
-  { vloam_status s_ = sync_all(h); if (s_ != VLOAM_OK) return s_; }
+  TRY(sync_all(h));
   int id = kKNone;
   for (int k = 1; k < kKCount; k++) if (strcmp(name, kKernelNames[k]) == 0) id = k;
   if (strcmp(name, "*") == 0) id = kKAll;  // every launch of every kernel (vloam_profile_read_table)
@@ -1677,7 +1621,7 @@ vloam_status vloam_profile_kernel(vloam_handle* h, const char* name, int max_lau
 vloam_status vloam_profile_read(vloam_handle* h, double* total_ms, int* launches) {
   if (!h || !total_ms || !launches) return VLOAM_ERR_INVALID;
   HIPCHK(hipSetDevice(h->device));
-  { vloam_status s_ = sync_all(h); if (s_ != VLOAM_OK) return s_; }
+  TRY(sync_all(h));
   double tot = 0;
   for (int k = 0; k < h->prof.used; k++) {
     float ms = 0;
@@ -1695,7 +1639,7 @@ vloam_status vloam_profile_read(vloam_handle* h, double* total_ms, int* launches
 vloam_status vloam_profile_read_table(vloam_handle* h, int n_kernels, double* ms, int* launches) {
   if (!h || !ms || !launches || n_kernels < 0) return VLOAM_ERR_INVALID;
   HIPCHK(hipSetDevice(h->device));
-  { vloam_status s_ = sync_all(h); if (s_ != VLOAM_OK) return s_; }
+  TRY(sync_all(h));
   for (int k = 0; k < n_kernels; k++) { ms[k] = 0; launches[k] = 0; }
   for (int k = 0; k < h->prof.used; k++) {
     float t = 0;
@@ -1714,11 +1658,11 @@ const char* vloam_profile_kernel_name(int k) { return (k >= 0 && k < kKCount) ? 
 vloam_status vloam_get_health(vloam_handle* h, long long out8[8]) {
   if (!h || !out8) return VLOAM_ERR_INVALID;
   HIPCHK(hipSetDevice(h->device));
-  { vloam_status s_ = sync_all(h); if (s_ != VLOAM_OK) return s_; }
+  TRY(sync_all(h));
   for (int k = 0; k < 8; k++) out8[k] = 0;
   int merr = 0;
   long long fb = 0;
-  if (h->frame > 0) { vloam_status s = map_error(&h->map, &merr, 0, &fb); if (s != VLOAM_OK) return s; }
+  if (h->frame > 0) TRY(map_error(&h->map, &merr, 0, &fb));
   out8[0] = fb; out8[1] = h->se.no_coop; out8[2] = h->map.rebuilds;
   return VLOAM_OK;
 }
@@ -1733,10 +1677,10 @@ vloam_status vloam_get_stage_ms(vloam_handle* h, double ms4[4], int* scans) {
 vloam_status vloam_get_counts(vloam_handle* h, long long c[16]) {
   if (!h || !c) return VLOAM_ERR_INVALID;
   HIPCHK(hipSetDevice(h->device));
-  { vloam_status s_ = sync_all(h); if (s_ != VLOAM_OK) return s_; }
+  TRY(sync_all(h));
   memset(c, 0, sizeof(long long) * 16);
   if (h->frame == 0) return VLOAM_OK;
-  const int f = (h->stage == 0) ? h->frame - 1 : h->frame;
+  const int f = shown_frame(h);
   const int cur = set_of(f), prev = set_of(f + vloam_handle::kSets - 1);
   FrameScalars S, Sp;
   HIPCHK(hipMemcpy(&S, SEL(h, h->sr[cur].S), sizeof(S), hipMemcpyDeviceToHost));
