@@ -85,11 +85,22 @@ vloam_status vloam_destroy(vloam_handle* h);
 typedef struct vloam_limits {
   int struct_size;             /* sizeof(vloam_limits) as the caller compiled it */
   int max_surf_stack_points;   /* capacity of laserCloudSurfStack: 24576 (0 = 24576); multiples of 8192 up to 131072 add the large stack tier */
+  /* The clouds of LaserMapping::publish (laser_mapping.cpp:778-805), written by the mapping stream itself behind the sweep that publishes
+   * them (vloam_get_published_map / _cloud / vloam_published_device_ptr below).  All three 0 (or a struct_size of 8): none, as before. */
+  int map_pub_number;          /* 0: off.  >= 1: /laser_cloud_map after every MAPPED sweep with (frameCount * mapping_skip_frame) % map_pub_number == 0,
+                                  frameCount = mapped sweeps so far, this one included (laser_mapping.cpp:778; the KITTI launch file sets 20).  On a
+                                  sweep skipped by mapping_skip_frame the reference republishes the unchanged map; here the last publication
+                                  simply stays current */
+  int max_published_map_points;/* capacity of one map publication: 256 .. 16777216 (0 = 2097152); ignored when map_pub_number == 0 */
+  int publish_registered_cloud;/* 0 | 1: the full-resolution cloud registered in the map frame (laser_mapping.cpp:795-805) after every sweep's mapping */
 } vloam_limits;
 void vloam_default_limits(vloam_limits* lim);
 /* vloam_create_batch with limits.  lim == NULL or the defaults: the same handle as vloam_create_batch(cfg, device, n_sessions, out).
  * VLOAM_ERR_INVALID (before any device call): max_surf_stack_points other than 0, 24576 or a multiple of 8192 in (24576, 131072], or such a
- * multiple above cfg->max_points; a struct_size that is neither 0 nor >= sizeof(vloam_limits).  VLOAM_ERR_HIP: the arenas do not fit the device's memory. */
+ * multiple above cfg->max_points; a struct_size that is neither 0, nor 8 (the first version of the struct: the fields behind
+ * max_surf_stack_points read as 0), nor >= sizeof(vloam_limits); a negative map_pub_number; a max_published_map_points outside 256 .. 16777216
+ * (with map_pub_number >= 1); a publish_registered_cloud other than 0 or 1; either product with cfg->with_mapping == 0.
+ * VLOAM_ERR_HIP: the arenas (the publication buffers are part of them) do not fit the device's memory. */
 vloam_status vloam_create_with_limits(const vloam_config* cfg, const vloam_limits* lim, int device, int n_sessions, vloam_handle** out);
 
 /* ---- Batched execution: one handle, n_sessions independent sequences advanced in lock step.  Every kernel of the sweep chain is
@@ -144,8 +155,29 @@ vloam_status vloam_get_features(vloam_handle* h, int which, float* xyzi4, int ca
 
 /* == the /laser_cloud_map product of LaserMapping::publish (laser_mapping.cpp:778-793): the corner cloud then the surf cloud of every
  * cube of the 21 x 21 x 11 window, cube index ascending, each cube cloud in its VoxelGrid order.  The reference publishes it every
- * map_pub_number frames; here the caller decides when to ask.  Copies min(*n, cap) points to the HOST buffer, true count in *n. */
+ * map_pub_number frames.  Two ways to it: vloam_get_map, whenever the caller asks (synchronises the whole pipeline, orders the cloud on the
+ * host), or vloam_limits::map_pub_number and vloam_get_published_map below (the mapping stream writes the ordered cloud behind the publishing
+ * sweep).  Copies min(*n, cap) points to the HOST buffer, true count in *n. */
 vloam_status vloam_get_map(vloam_handle* h, float* xyzi4, long long cap, long long* n);
+
+/* == the clouds of LaserMapping::publish as products of the sweep pipeline (vloam_limits::map_pub_number / publish_registered_cloud).  The
+ * mapping stream writes them into device buffers of the handle, in order behind the mapping of the sweep that publishes: a publication is a
+ * snapshot as of that sweep, whatever has been enqueued since.  Two buffers per product and session, used alternately.
+ * vloam_get_published_map / _cloud: the latest publication ENQUEUED so far.  First enqueues what the handle still owes (no wait), then waits
+ *   for the event behind that publication only — not for the pipeline — and copies min(*n, cap) points to the HOST buffer (which may be NULL
+ *   with cap 0); *n = the true count, *frame = the 0-based index of the publishing sweep.  Before the first publication: *n = 0, *frame = -1,
+ *   VLOAM_OK.  Reads the session chosen with vloam_select_session.  The registered cloud is the one vloam_get_features(h, 11) returns for
+ *   that sweep (laserCloudFullRes as handed to vloam_set_mapping_input included); on a sweep skipped by mapping_skip_frame it is registered
+ *   with the last mapped pose, as there.
+ * VLOAM_ERR_ORDER: the product is not enabled on this handle.  VLOAM_ERR_CAPACITY (map only): the map held more points than
+ *   max_published_map_points at that sweep — nothing was written, *n is the true count (also in vloam_last_error()), no partial cloud comes
+ *   back; the pipeline itself is unaffected (vloam_sync stays VLOAM_OK, vloam_get_map still works).
+ * vloam_published_device_ptr: which = 0 map, 1 registered cloud.  The device address of the same publication (packed float4), its count and
+ *   frame, for a consumer on the GPU; waits for the publication's event like the getters.  The address stays valid until the next call that
+ *   enqueues a sweep (the product's second buffer takes the next publication, the one after that overwrites this one). */
+vloam_status vloam_get_published_map(vloam_handle* h, float* xyzi4, long long cap, long long* n, int* frame);
+vloam_status vloam_get_published_cloud(vloam_handle* h, float* xyzi4, int cap, int* n, int* frame);
+vloam_status vloam_published_device_ptr(vloam_handle* h, int which, void** d_xyzi4, long long* n, int* frame);
 
 /* == vloam_tf->velo_last_VOT_velo_curr, read by solveLO when detach_VO_LO == 0 (laser_odometry.cpp:223-236) */
 vloam_status vloam_set_lo_prior(vloam_handle* h, const double q_xyzw[4], const double t[3]);

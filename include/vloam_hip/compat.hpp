@@ -122,8 +122,17 @@ class Session {  // one vloam_handle == one sequence on one GPU; shared by the t
     vloam_default_limits(&lim);
     lim.max_surf_stack_points = max_surf_stack_points;
     check(vloam_create_with_limits(&config, &lim, device, 1, &h_));
+    limits = lim;
+  }
+  // every capacity and the published clouds of the mapping stream (map_pub_number, max_published_map_points, publish_registered_cloud):
+  // LaserMapping::publishedMap() / registeredCloud() of such a session read what the mapping stream published
+  Session(int device, const vloam_config* cfg, const vloam_limits& lim) {
+    if (cfg) config = *cfg; else vloam_default_config(&config);
+    check(vloam_create_with_limits(&config, &lim, device, 1, &h_));
+    limits = lim;
   }
   vloam_config config;
+  vloam_limits limits = vloam_limits();   // all zero: the defaults, nothing published
   int frames_done = 0;   // sweeps whose laser odometry has run == LaserOdometry::frameCount
   ~Session() { vloam_destroy(h_); }
   Session(const Session&) = delete;
@@ -300,7 +309,29 @@ class LaserMapping {
     if (n) check(vloam_get_map(s_->get(), &c[0].x, n, &n));
     return c;
   }
-  Cloud registeredCloud() { return s_->features(11); }  // /velodyne_cloud_registered (laser_mapping.cpp:795-805)
+  // /laser_cloud_map as publish() emits it every map_pub_number frames: on a session created with vloam_limits::map_pub_number the latest
+  // publication of the mapping stream (a snapshot of its sweep; no pipeline synchronisation), otherwise map().  frame (may be null): the
+  // 0-based sweep that published it, -1 before the first publication / without the product
+  Cloud publishedMap(int* frame = nullptr) {
+    if (frame) *frame = -1;
+    if (s_->limits.map_pub_number <= 0) return map();
+    long long n = 0;
+    int f = -1;
+    check(vloam_get_published_map(s_->get(), nullptr, 0, &n, &f));
+    Cloud c(static_cast<size_t>(n));
+    if (n) check(vloam_get_published_map(s_->get(), &c[0].x, n, &n, &f));
+    if (frame) *frame = f;
+    return c;
+  }
+  // /velodyne_cloud_registered (laser_mapping.cpp:795-805); with vloam_limits::publish_registered_cloud the mapping stream's own product
+  Cloud registeredCloud() {
+    if (s_->limits.publish_registered_cloud != 1) return s_->features(11);
+    int n = 0, f = -1;
+    check(vloam_get_published_cloud(s_->get(), nullptr, 0, &n, &f));
+    Cloud c(static_cast<size_t>(n));
+    if (n) check(vloam_get_published_cloud(s_->get(), &c[0].x, n, &n, &f));
+    return c;
+  }
   Quaterniond q_w_curr{{0, 0, 0, 1}}, q_w_curr_highfreq{{0, 0, 0, 1}};   // laser_mapping.h:141-155: a skipped sweep only moves the high-frequency pose
   Vector3d t_w_curr{{0, 0, 0}}, t_w_curr_highfreq{{0, 0, 0}};
 

@@ -84,6 +84,10 @@ def main():
     ap.add_argument("--calib-cam-to-cam", help="KITTI calib_cam_to_cam.txt (R_rect_00, P_rect_00)")
     ap.add_argument("--calib-velo-to-cam", help="KITTI calib_velo_to_cam.txt (R, T)")
     ap.add_argument("--metrics", help="write per-frame metrics as JSON lines to this file")
+    ap.add_argument("--map-pub-number", type=int, default=0,
+                    help="publish /laser_cloud_map from the mapping stream every N frames (vloam_limits::map_pub_number; the KITTI launch file: 20) "
+                         "and write each publication as OUT/map_<frame>.npy (float32 [n, 4]); read through vloam_get_published_map, which waits "
+                         "for the publication only, never for the pipeline")
     ap.add_argument("--imu-T-velo", help="16 numbers, row major (default: KITTI 2011_09_26 extrinsics, approx.)")
     ap.add_argument("--imu-T-cam0", help="16 numbers, row major")
     a = ap.parse_args()
@@ -126,7 +130,8 @@ def main():
         img_cfg = dict(image_width=int(iw), image_height=int(ih), CLAHE=int(a.clahe))
     loam = vl.LidarOdometryMapping(device=a.device, mapping_skip_frame=a.mapping_skip_frame, detach_VO_LO=0 if a.vloam else 1,
                                    timing=1 if (a.metrics and not a.vloam) else 0, **img_cfg,
-                                   **({"max_ring_points": a.max_ring_points} if a.max_ring_points else {}))
+                                   **({"max_ring_points": a.max_ring_points} if a.max_ring_points else {}),
+                                   **({"map_pub_number": a.map_pub_number} if a.map_pub_number else {}))
     hd = loam.hd
     if a.vloam:
         if real_images:   # PointCloudUtil::loadTransformations (point_cloud_util.cpp:5-116)
@@ -138,6 +143,7 @@ def main():
     lo_rows, mo_rows, vo_rows = [], [], []
     mf = open(a.metrics, "w") if a.metrics else None
     ms_prev = np.zeros(4)
+    last_pub, n_pub = -1, 0
     for count, cloud in enumerate(clouds):
         if a.vloam:
             if a.images:
@@ -160,11 +166,26 @@ def main():
             q_lo, t_lo, q_mo, t_mo = lo.q_w_curr, lo.t_w_curr, lm.q_w_curr, lm.t_w_curr
         lo_rows.append(tf.LO2Cam0StartFrame(q_lo, t_lo, count))
         mo_rows.append(tf.MO2Cam0StartFrame(q_mo, t_mo, count))
+        pub_points, pub_overflow = None, False
+        if a.map_pub_number:
+            try:
+                _, _, pub_frame = hd.published_device_ptr(0)   # which sweep published last: no cloud crosses the link for an old publication
+                if pub_frame != last_pub:   # a new publication (a sweep skipped by mapping_skip_frame leaves the last one current)
+                    cloud_map, pub_frame = hd.published_map()
+                    np.save(os.path.join(a.out, "map_%06d.npy" % pub_frame), cloud_map)
+                    last_pub, n_pub, pub_points = pub_frame, n_pub + 1, int(cloud_map.shape[0])
+            except vl.VloamError as e:      # a map beyond max_published_map_points is not published; the run goes on
+                if e.status != vl.ERR_CAPACITY:
+                    raise
+                pub_overflow = True
+                print("frame %d: %s" % (count, e), file=sys.stderr)
         if mf:
             c = hd.counts()
             rec = {"frame": count, "points_in": int(cloud.shape[0]), "counts": c, "unwrap_boundary_points": unwrap_boundary_points(cloud),
                    "lo_pose": [float(x) for x in list(q_lo) + list(t_lo)],
                    "map_pose": [float(x) for x in list(q_mo) + list(t_mo)]}
+            if a.map_pub_number:
+                rec["published_map"] = {"frame": last_pub, "points": pub_points, "overflow": pub_overflow}   # points: of a publication written by this frame, else null
             if count > 0:
                 for name, st, item in (("lo_round0", 1, 2), ("lo_round1", 1, 18), ("map_round0", 2, 3), ("map_round1", 2, 19)):
                     r = hd.debug_lm_record(st, item)
@@ -189,6 +210,8 @@ def main():
     if vo_rows:
         kio.write_trajectory(os.path.join(a.out, "VO0.txt"), vo_rows)
     print("wrote %d rows to %s/{LO0,MO0%s}.txt" % (n, a.out, ",VO0" if vo_rows else ""))
+    if a.map_pub_number:
+        print("wrote %d published maps to %s/map_<frame>.npy" % (n_pub, a.out))
 
 
 if __name__ == "__main__":

@@ -1,7 +1,9 @@
 #!/usr/bin/env python3
 """Quick steady-state throughput probe (seconds, not minutes): one sequence and B batched sequences of 64 x 2048 sweeps with mapping,
 after a short warm-up.  For A/B-ing a kernel change; bench.py remains the measurement of record.
-  python tools/throughput_probe.py [--sessions 8] [--warm 60] [--steps 120] [--table]"""
+  python tools/throughput_probe.py [--sessions 8] [--warm 60] [--steps 120] [--table]
+  python tools/throughput_probe.py --no-batch --steps 200 --map-pub-number 20 --publish-registered-cloud --publish-ab 3
+      the single sequence with the published clouds of the mapping stream (vloam_limits) off and on, alternately, in one process"""
 import argparse
 import multiprocessing as mp
 import os
@@ -24,6 +26,10 @@ ap.add_argument("--steps", type=int, default=120)
 ap.add_argument("--sweeps", type=int, default=48)
 ap.add_argument("--table", action="store_true", help="per-kernel HIP-event table of the batched run")
 ap.add_argument("--no-single", action="store_true")
+ap.add_argument("--no-batch", action="store_true")
+ap.add_argument("--map-pub-number", type=int, default=0, help="vloam_limits::map_pub_number of the handles")
+ap.add_argument("--publish-registered-cloud", action="store_true", help="vloam_limits::publish_registered_cloud of the handles")
+ap.add_argument("--publish-ab", type=int, default=0, help="that many off / on pairs of single-sequence runs, products off first; replaces the normal run")
 ap.add_argument("--map-log2", type=int, default=22, help="map_capacity_log2 of the handles (voxel table slots)")
 ap.add_argument("--procs", type=int, default=32, help="worker processes for the synthesis (1 under rocprofv3: it follows forked children)")
 ap.add_argument("--from-idle", default="", help="comma-separated sweep counts: time that many sweeps of ONE sequence from a drained pipeline (5 repeats each) "
@@ -50,8 +56,11 @@ npts = host.shape[1]
 ptr = lambda k: d.data_ptr() + (k % a.sweeps) * npts * 16   # noqa: E731  (the sequence wraps: a jump back every a.sweeps, same for every variant)
 
 
-def run(B):
-    h = vl.Handle(0, n_sessions=B, with_mapping=1, max_frames=a.warm + a.steps + 8, map_capacity_log2=a.map_log2)
+PUB = dict(map_pub_number=a.map_pub_number, publish_registered_cloud=int(a.publish_registered_cloud))
+
+
+def run(B, pub=PUB):
+    h = vl.Handle(0, n_sessions=B, with_mapping=1, max_frames=a.warm + a.steps + 8, map_capacity_log2=a.map_log2, **pub)
     step = (lambda k: h.process_scan_device(ptr(k), npts)) if B == 1 else (lambda k: h.batch_process_scan_device([ptr(k)] * B, [npts] * B))
     for k in range(a.warm):
         step(k)
@@ -63,7 +72,9 @@ def run(B):
         step(k)
     h.sync()
     dt = time.perf_counter() - t0
-    print("B = %2d: %8.0f scans/s   (%.1f us per step)" % (B, B * a.steps / dt, 1e6 * dt / a.steps), flush=True)
+    print("B = %2d: %8.0f scans/s   (%.1f us per step)%s" % (B, B * a.steps / dt, 1e6 * dt / a.steps,
+                                                             "   published: map every %d, registered cloud %d" % (pub["map_pub_number"], pub["publish_registered_cloud"])
+                                                             if any(pub.values()) else ""), flush=True)
     if a.table:
         rows = h.profile_table()
         tot = sum(ms for ms, _ in rows.values())
@@ -102,7 +113,14 @@ def from_idle(counts):
 if a.from_idle:
     from_idle([int(v) for v in a.from_idle.split(",")])
     sys.exit(0)
+if a.publish_ab:
+    for _ in range(a.publish_ab):
+        run(1, dict(map_pub_number=0, publish_registered_cloud=0))
+        run(1)
+    sys.exit(0)
 t1 = None if a.no_single else run(1)
+if a.no_batch:
+    sys.exit(0)
 tb = run(a.sessions)
 if t1 is not None:
     print("batched session 0 identical to the single sequence:", bool(np.array_equal(t1, tb)))

@@ -46,7 +46,8 @@ class Config(C.Structure):
 
 class Limits(C.Structure):
     """vloam_limits: capacities that are not in vloam_config (c_api.h)."""
-    _fields_ = [("struct_size", C.c_int), ("max_surf_stack_points", C.c_int)]
+    _fields_ = [("struct_size", C.c_int), ("max_surf_stack_points", C.c_int), ("map_pub_number", C.c_int),
+                ("max_published_map_points", C.c_int), ("publish_registered_cloud", C.c_int)]
 
 
 class Calib(C.Structure):
@@ -112,13 +113,18 @@ def _fp(a):
 class Handle:
     """One sequence on one GPU (``vloam_handle``)."""
 
-    def __init__(self, device=0, n_sessions=1, max_surf_stack_points=None, **cfg):
+    def __init__(self, device=0, n_sessions=1, max_surf_stack_points=None, map_pub_number=None, max_published_map_points=None,
+                 publish_registered_cloud=None, **cfg):
         """n_sessions > 1: a batched handle — that many independent sequences advanced in lock step by batch_process_scan*;
         select(b) chooses the session the getters read.  max_surf_stack_points: vloam_limits::max_surf_stack_points (None: the default,
-        24576; multiples of 8192 up to 131072 add the large stack tier)."""
+        24576; multiples of 8192 up to 131072 add the large stack tier).  map_pub_number / max_published_map_points /
+        publish_registered_cloud: the clouds of LaserMapping::publish as products of the mapping stream (vloam_limits; None: off),
+        read with published_map() / published_cloud() / published_device_ptr()."""
         self.L = lib()
         self.cfg = default_config(**cfg)
-        self.limits = default_limits() if max_surf_stack_points is None else default_limits(max_surf_stack_points=int(max_surf_stack_points))
+        lim = dict(max_surf_stack_points=max_surf_stack_points, map_pub_number=map_pub_number, max_published_map_points=max_published_map_points,
+                   publish_registered_cloud=publish_registered_cloud)
+        self.limits = default_limits(**{k: int(v) for k, v in lim.items() if v is not None})
         self.surf_stack_cap = self.limits.max_surf_stack_points or K_STACK_CAP_SURF
         self.h = C.c_void_p()
         self.n_sessions = int(n_sessions)
@@ -541,6 +547,30 @@ class Handle:
         buf = np.zeros((max(n.value, 1), 4), dtype=np.float32)
         self._chk(self.L.vloam_get_map(self.h, _fp(buf), C.c_longlong(n.value), C.byref(n)))
         return buf[:n.value]
+
+    def published_map(self):
+        """The latest /laser_cloud_map the mapping stream published (vloam_limits::map_pub_number): (float32 [n, 4], 0-based sweep index),
+        ([0, 4], -1) before the first publication.  Waits for that publication only, not for the pipeline."""
+        n, f = C.c_longlong(0), C.c_int(-1)
+        self._chk(self.L.vloam_get_published_map(self.h, None, C.c_longlong(0), C.byref(n), C.byref(f)))
+        buf = np.zeros((max(n.value, 1), 4), dtype=np.float32)
+        self._chk(self.L.vloam_get_published_map(self.h, _fp(buf), C.c_longlong(n.value), C.byref(n), C.byref(f)))
+        return buf[:n.value], f.value
+
+    def published_cloud(self):
+        """The latest registered full-resolution cloud the mapping stream published (vloam_limits::publish_registered_cloud), like published_map()."""
+        n, f = C.c_int(0), C.c_int(-1)
+        self._chk(self.L.vloam_get_published_cloud(self.h, None, 0, C.byref(n), C.byref(f)))
+        buf = np.zeros((max(n.value, 1), 4), dtype=np.float32)
+        self._chk(self.L.vloam_get_published_cloud(self.h, _fp(buf), n.value, C.byref(n), C.byref(f)))
+        return buf[:n.value], f.value
+
+    def published_device_ptr(self, which):
+        """(device address, points, sweep index) of the latest published map (which = 0) / registered cloud (1): packed float4, valid until
+        the next call that enqueues a sweep."""
+        p, n, f = C.c_void_p(), C.c_longlong(0), C.c_int(-1)
+        self._chk(self.L.vloam_published_device_ptr(self.h, int(which), C.byref(p), C.byref(n), C.byref(f)))
+        return p.value, n.value, f.value
 
     def map_health(self):
         v = self.debug_raw(2, 69, np.int32)

@@ -271,19 +271,38 @@ template <class T>
 static inline T* SEL(const vloam_handle* h, T* p) { return p ? (T*)((char*)p + (size_t)h->sel * h->se.ss) : p; }
 
 // ------------------------------------------------------------------ vloam_create, in three parts
-// 1. What a configuration must satisfy, checked before any HIP call (so without a device too).  *surf_cap: the surf stack capacity to build with.
-static vloam_status validate_create(const vloam_config* cfg, const vloam_limits* lim, int n_sessions, int* surf_cap) {
-  *surf_cap = kStackCapSurf;
+// 1. What a configuration must satisfy, checked before any HIP call (so without a device too).  *lim_out: the limits to build with, every
+// field resolved (defaults for 0, fields the caller's struct_size does not reach read as 0).
+constexpr int kLimitsSizeV1 = 8;   // sizeof(vloam_limits) when it ended behind max_surf_stack_points
+static vloam_status validate_create(const vloam_config* cfg, const vloam_limits* lim, int n_sessions, vloam_limits* lim_out) {
+  memset(lim_out, 0, sizeof(*lim_out));
+  lim_out->struct_size = (int)sizeof(vloam_limits);
+  lim_out->max_surf_stack_points = kStackCapSurf;
   if (lim) {
     const int S = lim->max_surf_stack_points;
-    const bool size_ok = lim->struct_size == 0 || lim->struct_size >= (int)sizeof(vloam_limits);
+    const bool size_ok = lim->struct_size == 0 || lim->struct_size == kLimitsSizeV1 || lim->struct_size >= (int)sizeof(vloam_limits);
     const bool value_ok = S == 0 || S == kStackCapSurf || (S > kStackCapSurf && S <= kStackCapSurfMax && S % kStackCapSurfStep == 0);
     if (!size_ok || !value_ok || (S > kStackCapSurf && S > cfg->max_points)) {   // (the default holds whatever max_points is, as it always has)
-      set_err("vloam_limits: max_surf_stack_points must be 0 or %d (default), or a multiple of %d up to %d, and at most max_points; struct_size 0 or >= %d",
+      set_err("vloam_limits: max_surf_stack_points must be 0 or %d (default), or a multiple of %d up to %d, and at most max_points; struct_size 0, 8 or >= %d",
               kStackCapSurf, kStackCapSurfStep, kStackCapSurfMax, (int)sizeof(vloam_limits));
       return VLOAM_ERR_INVALID;
     }
-    if (S != 0) *surf_cap = S;
+    if (S != 0) lim_out->max_surf_stack_points = S;
+    if (lim->struct_size != kLimitsSizeV1) {   // the published clouds (a first-version caller has no such fields: whatever lies behind its struct is not read)
+      const int N = lim->map_pub_number, C = lim->max_published_map_points, R = lim->publish_registered_cloud;
+      if (N < 0) { set_err("vloam_limits: map_pub_number must be 0 (off) or 1 .. %d", INT_MAX); return VLOAM_ERR_INVALID; }
+      if (N > 0 && C != 0 && (C < kPubMapCapMin || C > kPubMapCapMax)) {
+        set_err("vloam_limits: max_published_map_points must be 0 (= %lld) or %lld .. %lld", kPubMapCapDefault, kPubMapCapMin, kPubMapCapMax); return VLOAM_ERR_INVALID;
+      }
+      if (R != 0 && R != 1) { set_err("vloam_limits: publish_registered_cloud must be 0 or 1"); return VLOAM_ERR_INVALID; }
+      if ((N > 0 || R) && !cfg->with_mapping) {
+        set_err("vloam_limits: map_pub_number (0 or 1 .. %d) and publish_registered_cloud (0 or 1) must be 0 on a handle with with_mapping == 0: the mapping stage publishes", INT_MAX);
+        return VLOAM_ERR_INVALID;
+      }
+      lim_out->map_pub_number = N;
+      lim_out->max_published_map_points = N > 0 ? (C != 0 ? C : (int)kPubMapCapDefault) : 0;
+      lim_out->publish_registered_cloud = R;
+    }
   }
   if (n_sessions < 1 || n_sessions > kMaxBatch) { set_err("n_sessions must be 1..%d", kMaxBatch); return VLOAM_ERR_INVALID; }
   if (cfg->scan_line != 16 && cfg->scan_line != 32 && cfg->scan_line != 64) {
@@ -454,6 +473,9 @@ const char* vloam_version(void) { return "vloam_hip 0.1 (gfx950)"; }
 void vloam_default_limits(vloam_limits* lim) {
   lim->struct_size = (int)sizeof(vloam_limits);
   lim->max_surf_stack_points = kStackCapSurf;
+  lim->map_pub_number = 0;
+  lim->max_published_map_points = (int)kPubMapCapDefault;
+  lim->publish_registered_cloud = 0;
 }
 
 vloam_status vloam_create_batch(const vloam_config* cfg, int device, int n_sessions, vloam_handle** out) {
@@ -462,8 +484,8 @@ vloam_status vloam_create_batch(const vloam_config* cfg, int device, int n_sessi
 
 vloam_status vloam_create_with_limits(const vloam_config* cfg, const vloam_limits* lim, int device, int n_sessions, vloam_handle** out) {
   if (!cfg || !out) { set_err("null argument"); return VLOAM_ERR_INVALID; }
-  int surf_cap = 0;
-  TRY(validate_create(cfg, lim, n_sessions, &surf_cap));
+  vloam_limits lims;
+  TRY(validate_create(cfg, lim, n_sessions, &lims));
   // A handle drives two to six HIP streams that must run side by side (scan registration | odometry [| mapping | scan-feature VoxelGrid]
   // [| images] [| host-sweep copies]).  GPU_MAX_HW_QUEUES (read by the runtime when it initialises: it belongs to the HOST's environment, and a
   // library must not setenv() behind a multi-threaded host) caps each of the runtime's three priority pools of hardware queues; the handle
@@ -495,7 +517,11 @@ vloam_status vloam_create_with_limits(const vloam_config* cfg, const vloam_limit
   vloam_handle* h = new vloam_handle;
   h->cfg = *cfg;
   if (h->cfg.max_ring_points == 0) h->cfg.max_ring_points = kMaxRingLen;   // zero-initialised configs: the default
-  h->map.surf_cap = surf_cap;   // before the layout: the mapping stage's arrays are sized by it (map_layout)
+  h->map.surf_cap = lims.max_surf_stack_points;   // before the layout: the mapping stage's arrays are sized by it (map_layout)
+  h->map.pub.pub_number = lims.map_pub_number;    // ... and so are the publication buffers
+  h->map.pub.skip_n = cfg->mapping_skip_frame;
+  h->map.pub.cap = lims.max_published_map_points;
+  h->map.pub.cloud_on = lims.publish_registered_cloud;
   h->device = device;
   *out = nullptr;
   vloam_status st = create_streams(h, plan, cfg);
@@ -710,9 +736,19 @@ static vloam_status enqueue_map(vloam_handle* h, int frame) {
   // LaserOdometry::output: skip_frame = (frameCount % mapping_skip_frame != 0), frameCount already incremented (laser_odometry.cpp:535,618)
   const bool skip = ((frame + 1) % h->cfg.mapping_skip_frame) != 0;
   const bool sub_pose = h->sub_pose_frame == frame;   // LaserMapping::input was handed another odometry pose (vloam_set_mapping_input)
-  vloam_status s = map_enqueue(&h->map, h->cfg, h->s_map, h->sr[cur], h->lo, sub_pose ? h->sub_row : h->traj + (size_t)frame * 14, skip, cur, &h->prof, h->ev_map[cur]);
+  // the registered cloud (vloam_limits::publish_registered_cloud) still reads the sweep's buffer set behind the mapping: such a sweep releases the
+  // set behind k_map_register.  The published map reads the voxel tables only, so it leaves the event where it is.
+  const bool publishes = map_publishes(&h->map, skip), reads_set = h->map.pub.cloud_on != 0;
+  vloam_status s = map_enqueue(&h->map, h->cfg, h->s_map, h->sr[cur], h->lo, sub_pose ? h->sub_row : h->traj + (size_t)frame * 14, skip, cur, &h->prof,
+                               reads_set ? nullptr : h->ev_map[cur]);
   if (s != VLOAM_OK) { set_err("map_enqueue failed: %s", hipGetErrorString(hipGetLastError())); return VLOAM_ERR_HIP; }
   if (sub_pose) HIPCHK(hipMemcpyAsync(h->traj + (size_t)frame * 14 + 7, h->sub_row + 7, 7 * sizeof(double), hipMemcpyDeviceToDevice, h->s_map));   // the map half of the log
+  if (publishes) {
+    const bool sub_cloud = h->sub_cloud_frame == frame;   // laserCloudFullRes as handed to LaserMapping::input (what vloam_get_features(h, 11) shows)
+    s = map_publish_enqueue(&h->map, h->s_map, sub_cloud ? h->sub.cloud : h->sr[cur].cloud, sub_cloud ? h->sub.S : h->sr[cur].S, frame, skip, &h->prof,
+                            reads_set ? h->ev_map[cur] : nullptr);
+    if (s != VLOAM_OK) { set_err("map_publish_enqueue failed: %s", hipGetErrorString(hipGetLastError())); return VLOAM_ERR_HIP; }
+  }
   if (h->cfg.timing) HIPCHK(hipEventRecord(h->ev[5], h->s_map));
   return VLOAM_OK;
 }
@@ -877,6 +913,40 @@ vloam_status vloam_get_map(vloam_handle* h, float* xyzi4, long long cap, long lo
   HIPCHK(hipSetDevice(h->device));
   TRY(sync_all(h));
   return map_export(&h->map, h->s_map, xyzi4, cap, n);
+}
+
+// == the same cloud, and the registered full-resolution cloud, as the mapping stream published them (vloam_limits)
+static vloam_status published_get(vloam_handle* h, int which, float* xyzi4, long long cap, long long* n, int* frame, void** d_ptr) {
+  const MapPub& P = h->map.pub;
+  if (which == 0 ? P.pub_number == 0 : !P.cloud_on) {
+    set_err(which == 0 ? "the handle was created without vloam_limits::map_pub_number: no map is published (vloam_get_map exports it on request)"
+                       : "the handle was created without vloam_limits::publish_registered_cloud (vloam_get_features(h, 11) registers the cloud on request)");
+    return VLOAM_ERR_ORDER;
+  }
+  HIPCHK(hipSetDevice(h->device));
+  TRY(drain_deferred(h, 0, 0));   // enqueue only: the publication of every sweep handed over so far is then on the mapping stream
+  const vloam_status s = map_published_get(&h->map, which, xyzi4, cap, n, frame, d_ptr);
+  if (s == VLOAM_ERR_CAPACITY) set_err("the map published after sweep %d holds %lld points, more than max_published_map_points = %lld", *frame, *n, P.cap);
+  else if (s != VLOAM_OK) set_err("reading the published cloud failed: %s", hipGetErrorString(hipGetLastError()));
+  return s;
+}
+
+vloam_status vloam_get_published_map(vloam_handle* h, float* xyzi4, long long cap, long long* n, int* frame) {
+  if (!h || !n || !frame || cap < 0) return VLOAM_ERR_INVALID;
+  return published_get(h, 0, xyzi4, cap, n, frame, nullptr);
+}
+
+vloam_status vloam_get_published_cloud(vloam_handle* h, float* xyzi4, int cap, int* n, int* frame) {
+  if (!h || !n || !frame || cap < 0) return VLOAM_ERR_INVALID;
+  long long nn = 0;
+  const vloam_status s = published_get(h, 1, xyzi4, cap, &nn, frame, nullptr);
+  *n = (int)nn;
+  return s;
+}
+
+vloam_status vloam_published_device_ptr(vloam_handle* h, int which, void** d_xyzi4, long long* n, int* frame) {
+  if (!h || !d_xyzi4 || !n || !frame || (which != 0 && which != 1)) return VLOAM_ERR_INVALID;
+  return published_get(h, which, nullptr, 0, n, frame, d_xyzi4);
 }
 
 vloam_status vloam_set_lo_prior(vloam_handle* h, const double q[4], const double t[3]) {

@@ -95,6 +95,41 @@ struct MapFrame {         // per-sweep device counters
   int fallback_solves;    // cooperative Levenberg-Marquardt solves of this session that degraded to one workgroup (lm_solve.hip)
 };
 
+// The clouds of LaserMapping::publish as products of the mapping stream (vloam_limits::map_pub_number / publish_registered_cloud; LM:778-805).
+// Everything here lives in the session arena and only on a handle that asked for it.  /laser_cloud_map is ordered on the device: the live
+// records are counted per (cube, kind) bucket, an exclusive scan turns the counts into segment offsets, the records are scattered into their
+// segments, and every segment is ordered by its key — in LDS when it fits (kPubLdsKeys), by counting smaller keys otherwise.  A point's
+// place is a function of the keys alone.
+constexpr int kPubBuckets = 2 * kCubeNum;   // (cube, kind): the leading bits of the order key
+constexpr int kPubLdsKeys = 4096;           // segments of up to this many records are sorted in LDS by one workgroup (k_map_pub_sort)
+constexpr long long kPubMapCapDefault = 2097152, kPubMapCapMin = 256, kPubMapCapMax = 16777216;
+struct PubHeader { long long n; int overflow; int pad; };   // next to each publication buffer: true count | 1 = more than the capacity, nothing written
+struct MapPub {
+  int pub_number = 0;          // vloam_limits::map_pub_number
+  int skip_n = 1;              // vloam_config::mapping_skip_frame
+  bool due(int frame_count) const { return ((long long)frame_count * skip_n) % pub_number == 0; }   // LM:778, frameCount = mapped sweeps so far
+  long long cap = 0;           // vloam_limits::max_published_map_points
+  int cloud_on = 0;            // vloam_limits::publish_registered_cloud
+  int* cnt = nullptr;          // [kPubBuckets] records per bucket (zero between publications: k_map_pub_sort clears what it has read)
+  int* off = nullptr;          // [kPubBuckets + 1] exclusive scan of cnt
+  int* cur = nullptr;          // [kPubBuckets] scatter cursors
+  unsigned long long* keys = nullptr;   // [cap] order keys by segment, arrival order inside a segment
+  float4* vals = nullptr;      // [cap] their points
+  float4* out[2] = {nullptr, nullptr};       // [cap] the ordered cloud, two publications
+  PubHeader* hdr[2] = {nullptr, nullptr};
+  float4* cloud[2] = {nullptr, nullptr};     // [max_points] registered full-resolution cloud, two publications
+  int* cloud_n[2] = {nullptr, nullptr};      // its count (the sweep's FrameScalars::N2)
+  // host side
+  hipEvent_t ev_map[2] = {nullptr, nullptr}, ev_cloud[2] = {nullptr, nullptr};   // recorded behind each publication
+  int map_seq = 0, cloud_seq = 0;            // publications enqueued so far (the latest sits in buffer (seq - 1) & 1)
+  int map_frame[2] = {-1, -1}, cloud_frame[2] = {-1, -1};
+  int mapped = 0;              // mapped sweeps enqueued (map_enqueue counts them) == MapState::sweep_no once they have run
+  void rebase(size_t o) {
+    rbp(cnt, o); rbp(off, o); rbp(cur, o); rbp(keys, o); rbp(vals, o);
+    for (int k = 0; k < 2; k++) { rbp(out[k], o); rbp(hdr[k], o); rbp(cloud[k], o); rbp(cloud_n[k], o); }
+  }
+};
+
 struct MapContext {
   MapState* state = nullptr;
   MapFrame* frame = nullptr;
@@ -135,9 +170,11 @@ struct MapContext {
     for (int k = 0; k < 2; k++) { rbp(m.stack[k], off); rbp(m.stack_map[k], off); rbp(m.touched[k], off); rbp(m.deferred[k], off); rbp(m.newraw[k], off); m.F[k].rebase(off); }
     rbp(m.rec, off); rbp(m.nbr, off); rbp(m.cbox, off); rbp(m.ccand, off); rbp(m.registered, off); rbp(m.assoc_cyc, off); rbp(m.ts_log, off); rbp(m.rebuild_tmp, off); rbp(m.rebuild_n, off);
     if (m.host_flags) m.host_flags += 2 * b;
+    m.pub.rebase(off);
     m.se.B = 1; m.sel = 0;
     return m;
   }
+  MapPub pub;              // published clouds (off on a default handle)
   float4* registered = nullptr;  // full-resolution cloud in the map frame, on request
   long long* assoc_cyc = nullptr;  // [2][8] debug: phase cycle sums of k_map_assoc per outer round
   long long* ts_log = nullptr;     // [1024][2] VLOAM_TS_LOG=1: constant-rate (100 MHz) clock at the start of k_map_prepare / end of k_map_finalize of sweep k % 1024
@@ -156,6 +193,16 @@ vloam_status map_error(MapContext* m, int* err_bits, int clear_mask = 0, long lo
 vloam_status map_debug_get(MapContext* m, int item, void* buf, long long cap, long long* n);
 // == /laser_cloud_map (laser_mapping.cpp:778-793): every cube's corner cloud then surf cloud, cube index ascending
 vloam_status map_export(MapContext* m, hipStream_t st, float* xyzi4, long long cap, long long* n);
+// Publications of sweep `frame`, enqueued on the mapping stream behind map_enqueue of that sweep: the registered cloud first, then `done`
+// (non-null on a handle with the registered cloud, whose map_enqueue was given done == nullptr: k_map_register still reads the sweep's buffer
+// set), then the map, which reads the voxel tables only.  cloud / S: the sweep's laserCloudFullRes and its scalars, session 0's addresses.
+// No allocation, host copy or synchronisation.
+bool map_publishes(const MapContext* m, bool skip_frame);   // asked BEFORE map_enqueue of the sweep: will it publish anything?
+vloam_status map_publish_enqueue(MapContext* m, hipStream_t st, const float4* cloud, const FrameScalars* S, int frame, bool skip_frame, ProfHook* ph,
+                                 hipEvent_t done);
+// which: 0 map, 1 registered cloud; the latest publication of the selected session.  Waits for that publication's event only.
+// d_ptr (may be NULL): its device address.  xyzi4 (may be NULL): host buffer of cap points.  VLOAM_ERR_CAPACITY: the map overflowed (*n = true count).
+vloam_status map_published_get(MapContext* m, int which, float* xyzi4, long long cap, long long* n, int* frame, void** d_ptr);
 vloam_status map_force_rebuild(MapContext* m, hipStream_t st);  // every session
 void map_destroy(MapContext* m);
 vloam_status map_counts(MapContext* m, long long c[16]);
