@@ -81,7 +81,9 @@ vloam_status vloam_destroy(vloam_handle* h);
  * larger max_surf_stack_points adds the large stack tier: everything the mapping stage indexes by a stack point is sized by it (~2.8 KB of
  * device memory per point and session), the scan-to-map kernels run their run-time-capacity forms and the solve
  * compacts its factors in a launch of its own.  The corner stack (8192 >= the 7680 lessSharp points a sweep can have) has no such limit.
- * struct_size: sizeof(vloam_limits) as the caller compiled it (0: this header's), so that fields can be added behind the ones it knows. */
+ * struct_size: sizeof(vloam_limits) as the caller compiled it (0: this header's), so that fields can be added behind the ones it knows: 8 ends
+ * behind max_surf_stack_points, 20 == sizeof(vloam_limits) behind publish_registered_cloud, 24 == sizeof(vloam_limits_ext) behind sweep_log (below);
+ * the fields a caller's size does not reach read as 0. */
 typedef struct vloam_limits {
   int struct_size;             /* sizeof(vloam_limits) as the caller compiled it */
   int max_surf_stack_points;   /* capacity of laserCloudSurfStack: 24576 (0 = 24576); multiples of 8192 up to 131072 add the large stack tier */
@@ -94,12 +96,22 @@ typedef struct vloam_limits {
   int max_published_map_points;/* capacity of one map publication: 256 .. 16777216 (0 = 2097152); ignored when map_pub_number == 0 */
   int publish_registered_cloud;/* 0 | 1: the full-resolution cloud registered in the map frame (laser_mapping.cpp:795-805) after every sweep's mapping */
 } vloam_limits;
+/* The limits with the field that came after vloam_limits (which keeps its 20 bytes for the callers compiled against it): sweep_log lies right
+ * behind publish_registered_cloud, at byte 20.  Hand &ext.limits to vloam_create_with_limits with limits.struct_size == sizeof(vloam_limits_ext)
+ * (vloam_default_limits_ext sets it): exactly that struct_size tells the library that the field is there; with any other accepted size (0, 8, 20,
+ * or a larger one: a later header's struct, of which the fields of vloam_limits are read) nothing behind vloam_limits is read and sweep_log is 0. */
+typedef struct vloam_limits_ext {
+  vloam_limits limits;
+  int sweep_log;               /* 0 | 1: one vloam_sweep_record per sweep and session, written by the stage streams themselves (vloam_get_sweep_log below);
+                                  works with with_mapping 0 or 1 */
+} vloam_limits_ext;
+void vloam_default_limits_ext(vloam_limits_ext* lim);
 void vloam_default_limits(vloam_limits* lim);
 /* vloam_create_batch with limits.  lim == NULL or the defaults: the same handle as vloam_create_batch(cfg, device, n_sessions, out).
  * VLOAM_ERR_INVALID (before any device call): max_surf_stack_points other than 0, 24576 or a multiple of 8192 in (24576, 131072], or such a
  * multiple above cfg->max_points; a struct_size that is neither 0, nor 8 (the first version of the struct: the fields behind
- * max_surf_stack_points read as 0), nor >= sizeof(vloam_limits); a negative map_pub_number; a max_published_map_points outside 256 .. 16777216
- * (with map_pub_number >= 1); a publish_registered_cloud other than 0 or 1; either product with cfg->with_mapping == 0.
+ * max_surf_stack_points read as 0), nor >= sizeof(vloam_limits) (only sizeof(vloam_limits_ext) itself carries sweep_log); a negative map_pub_number; a max_published_map_points outside 256 .. 16777216 (with map_pub_number >= 1); a publish_registered_cloud
+ * other than 0 or 1; either product with cfg->with_mapping == 0; a sweep_log other than 0 or 1 (struct_size == sizeof(vloam_limits_ext)).
  * VLOAM_ERR_HIP: the arenas (the publication buffers are part of them) do not fit the device's memory. */
 vloam_status vloam_create_with_limits(const vloam_config* cfg, const vloam_limits* lim, int device, int n_sessions, vloam_handle** out);
 
@@ -257,6 +269,74 @@ vloam_status vloam_frame_count(vloam_handle* h, int* frames);
 /* device address + byte size of the trajectory log (for an RCCL gather across GPUs); rows are only complete
  * after vloam_sync() */
 vloam_status vloam_trajectory_device_ptr(vloam_handle* h, void** d_ptr, long long* bytes);
+
+/* == Per-sweep diagnostics log (vloam_limits_ext::sweep_log = 1): what the reference says about a frame while it runs -- "less correspondence!"
+ * (laser_odometry.cpp:452-455), "Map corner and surf num are not enough" (laser_mapping.cpp:448,631-635), the solver summaries -- and what
+ * vloam_sync can only report for "at least one sweep since the last vloam_sync", as one fixed-size record per sweep and session.  The rows live
+ * beside the trajectory log in the session arena (max_frames rows of 192 bytes: 1.5 MB per session at the default 8192) and are written by
+ * the stage streams themselves: scan registration writes its counts and error bits behind the sweep's scan registration, the odometry its
+ * factor counts and two solves behind the sweep's odometry, the mapping the rest behind the sweep's mapping; the last of them (the odometry
+ * when with_mapping == 0) stamps `frame`.  No stream waits for another and nothing synchronises.  A handle without sweep_log allocates and
+ * launches nothing of this.  vloam_sync, the sticky error words and vloam_get_health are what they were, log or no log.
+ * sizeof(vloam_sweep_record) == 192: 32 ints, then 8 doubles; ints without a name here are 0. */
+enum {   /* vloam_sweep_record::error_bits: raised BY THIS SWEEP; the condition is the one vloam_sync words for the handle */
+  VLOAM_SWEEP_EMPTY = 1,            /* no point of the sweep survived NaN / minimum_range removal (vloam_sync: VLOAM_ERR_EMPTY) */
+  VLOAM_SWEEP_RING_TOO_LONG = 2,    /* a ring held more than max_ring_points points and was dropped (VLOAM_ERR_CAPACITY) */
+  VLOAM_SWEEP_MAP_FULL = 4,         /* voxel hash full (map_capacity_log2); the handle keeps this bit for good: the row is the sweep that raised it first */
+  VLOAM_SWEEP_MAP_RAW_CAPACITY = 8, /* raw-point capacity of the map exceeded (more than 255 un-merged points in a voxel of a cube outside the valid
+                                       block, or more than 64 raw voxels around one query); first sweep to raise it, like MAP_FULL */
+  VLOAM_SWEEP_STACK_FULL = 16,      /* mapping factor table full: more surf points after VoxelGrid than max_surf_stack_points */
+  VLOAM_SWEEP_DS_TIMEOUT = 32,      /* a workgroup of the scan-feature VoxelGrid gave up waiting for the bins in front of it: the sweep was not mapped */
+  VLOAM_SWEEP_VO_DEGENERATE = 64    /* this frame's VO solve returned a zero rotation angle: poses are NaN from here on (visual_odometry.cpp:427-430) */
+};
+enum {   /* vloam_sweep_record::flags */
+  VLOAM_SWEEP_FLAG_FIRST = 1,              /* first sweep of the sequence: no odometry solve (laser_odometry.cpp:196-204) */
+  VLOAM_SWEEP_FLAG_MAP_SKIPPED = 2,        /* mapping skipped by mapping_skip_frame: only the high-frequency pose (laser_mapping.cpp:186-190) */
+  VLOAM_SWEEP_FLAG_MAP_NOT_OPTIMIZED = 4,  /* mapped, but "Map corner and surf num are not enough": no solve (laser_mapping.cpp:448,631-635) */
+  VLOAM_SWEEP_FLAG_LO_LESS_CORR_0 = 8,     /* "less correspondence!": fewer than 10 factors in odometry round 0 (laser_odometry.cpp:452-455) */
+  VLOAM_SWEEP_FLAG_LO_LESS_CORR_1 = 16,    /* ... in round 1 */
+  VLOAM_SWEEP_FLAG_SOLVE_DEGRADED = 32     /* a cooperative solve degraded to one workgroup (vloam_get_health) and this sweep's odometry or mapping was
+                                              the first to see the handle's counter rise: the odometry and the mapping of neighbouring sweeps run side
+                                              by side and share that counter, so the solve may be the neighbour's */
+};
+typedef struct vloam_sweep_record {
+  int frame;                   /* 0-based sweep index; -1 while the row has not been completed */
+  int error_bits;              /* VLOAM_SWEEP_* */
+  int flags;                   /* VLOAM_SWEEP_FLAG_* */
+  /* scan registration */
+  int n_in;                    /* points handed in */
+  int n_cloud;                 /* laserCloud->size() after NaN / minimum_range / ring removal */
+  int n_sharp, n_less_sharp, n_flat, n_less_flat;
+  /* laser odometry, per outer round; all 0 on the first sweep */
+  int lo_corner_factors[2];    /* corner_correspondence (laser_odometry.cpp:326-341) */
+  int lo_plane_factors[2];     /* plane_correspondence (laser_odometry.cpp:430-446) */
+  int lo_iterations[2];        /* trust-region iterations run, accepted or not (the rows of the solver's iteration trace) */
+  int lo_termination[2];       /* 0 iteration cap, 1 convergence, 2 failure */
+  /* laser mapping; all 0 on a sweep skipped by mapping_skip_frame and on a handle without mapping */
+  int n_corner_stack, n_surf_stack;   /* laserCloudCornerStackNum / laserCloudSurfStackNum (laser_mapping.cpp:432-440) */
+  int n_map_corner, n_map_surf;       /* laserCloudCornerFromMapNum / laserCloudSurfFromMapNum: points gathered from the valid block (:404-430) */
+  int map_corner_factors[2];   /* per outer round; the four solve fields are 0 when the optimisation did not run */
+  int map_surf_factors[2];
+  int map_iterations[2];
+  int map_termination[2];
+  int reserved[3];
+  /* initial / final cost of the four solves (0 where a solve did not run) */
+  double lo_initial_cost[2], lo_final_cost[2];
+  double map_initial_cost[2], map_final_cost[2];
+} vloam_sweep_record;
+#if defined(__cplusplus)
+static_assert(sizeof(vloam_sweep_record) == 192, "vloam_sweep_record is 32 ints and 8 doubles");
+#elif defined(__STDC_VERSION__) && __STDC_VERSION__ >= 201112L
+_Static_assert(sizeof(vloam_sweep_record) == 192, "vloam_sweep_record is 32 ints and 8 doubles");
+#endif
+/* vloam_get_sweep_log: the rows of sweeps first .. first + count - 1 of the session chosen with vloam_select_session -> HOST buffer.  Like
+ *   vloam_get_published_map it first enqueues what the handle still owes (no wait) and then waits for the work behind sweep first + count - 1
+ *   only, not for sweeps enqueued after it.  VLOAM_ERR_ORDER: the handle was created without vloam_limits_ext::sweep_log.  VLOAM_ERR_INVALID: a
+ *   range beyond vloam_frame_count.  A sweep whose odometry or mapping the caller left out (stage-wise driving) keeps frame == -1.
+ * vloam_sweep_log_device_ptr: device address + byte size of the selected session's rows, like vloam_trajectory_device_ptr; rows are only complete
+ *   after vloam_sync(). */
+vloam_status vloam_get_sweep_log(vloam_handle* h, int first, int count, vloam_sweep_record* out);
+vloam_status vloam_sweep_log_device_ptr(vloam_handle* h, void** d_rows, long long* bytes);
 
 /* == VisualOdometry::processPointCloud + solveNlsAll (visual_odometry.cpp:157-186,254-450).
  * prev_uv/curr_uv: n_match integer pixel pairs (the reference truncates keypoints to int, :283-294).

@@ -131,6 +131,14 @@ class Session {  // one vloam_handle == one sequence on one GPU; shared by the t
     check(vloam_create_with_limits(&config, &lim, device, 1, &h_));
     limits = lim;
   }
+  // ... and the per-sweep diagnostics log (vloam_limits_ext::sweep_log): LidarOdometryMapping::sweepRecord reads it
+  Session(int device, const vloam_config* cfg, const vloam_limits_ext& ext) {
+    if (cfg) config = *cfg; else vloam_default_config(&config);
+    vloam_limits_ext e = ext;
+    e.limits.struct_size = (int)sizeof(vloam_limits_ext);
+    check(vloam_create_with_limits(&config, &e.limits, device, 1, &h_));
+    limits = e.limits;
+  }
   vloam_config config;
   vloam_limits limits = vloam_limits();   // all zero: the defaults, nothing published
   int frames_done = 0;   // sweeps whose laser odometry has run == LaserOdometry::frameCount
@@ -350,8 +358,21 @@ class LidarOdometryMapping {
  public:
   explicit LidarOdometryMapping(int device = 0, const vloam_config* cfg = nullptr)
       : session(std::make_shared<Session>(device, cfg)), scan_registration(session), laser_odometry(session), laser_mapping(session) {}
+  // with vloam_limits (capacities, the published clouds) or vloam_limits_ext (also the per-sweep diagnostics log, sweep_log = 1: sweepRecord below)
+  LidarOdometryMapping(int device, const vloam_config* cfg, const vloam_limits_ext& lim)
+      : session(std::make_shared<Session>(device, cfg, lim)), scan_registration(session), laser_odometry(session), laser_mapping(session) {}
+  LidarOdometryMapping(int device, const vloam_config* cfg, const vloam_limits& lim)
+      : session(std::make_shared<Session>(device, cfg, lim)), scan_registration(session), laser_odometry(session), laser_mapping(session) {}
   void init() {}
   template <class TF> void init(std::shared_ptr<TF>&) {}   // lidar_odometry_mapping.h: init(std::shared_ptr<VloamTF>&)
+  // What the reference prints about a frame while it runs ("less correspondence!", laser_odometry.cpp:452-455; "Map corner and surf num are
+  // not enough", laser_mapping.cpp:448,631-635; the solver summaries) and the error bits of that sweep: the record of sweep `frame` (0-based,
+  // a sweep counts once its last stage has run) as the stage streams wrote it.  Needs vloam_limits_ext::sweep_log = 1 (VLOAM_ERR_ORDER otherwise).
+  vloam_sweep_record sweepRecord(int frame) {
+    vloam_sweep_record r;
+    check(vloam_get_sweep_log(session->get(), frame, 1, &r));
+    return r;
+  }
   void reset() { scan_registration.reset(); laser_mapping.reset(); }
   void scanRegistrationIO(const Cloud& laserCloudIn) { scan_registration.input(laserCloudIn); }
   template <class XyzCloud, detail::XyzCloudLike<XyzCloud> = 0>

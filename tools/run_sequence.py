@@ -66,6 +66,22 @@ def unwrap_boundary_points(cloud, band=4e-6):
     return int(near.sum())
 
 
+def write_sweep_log(vl, hd, path):
+    """One JSON line per sweep from vloam_get_sweep_log: every field of vloam_sweep_record, error_bits and flags also by name."""
+    bits = [(n[len("SWEEP_"):].lower(), getattr(vl, n)) for n in ("SWEEP_EMPTY", "SWEEP_RING_TOO_LONG", "SWEEP_MAP_FULL", "SWEEP_MAP_RAW_CAPACITY",
+                                                                    "SWEEP_STACK_FULL", "SWEEP_DS_TIMEOUT", "SWEEP_VO_DEGENERATE")]
+    flags = [(n[len("SWEEP_FLAG_"):].lower(), getattr(vl, n)) for n in ("SWEEP_FLAG_FIRST", "SWEEP_FLAG_MAP_SKIPPED", "SWEEP_FLAG_MAP_NOT_OPTIMIZED",
+                                                                        "SWEEP_FLAG_LO_LESS_CORR_0", "SWEEP_FLAG_LO_LESS_CORR_1", "SWEEP_FLAG_SOLVE_DEGRADED")]
+    rows = hd.sweep_log()
+    with open(path, "w") as f:
+        for r in rows:
+            rec = {name: (r[name].tolist() if r[name].ndim else r[name].item()) for name in rows.dtype.names if name != "reserved"}
+            rec["errors"] = [n for n, b in bits if rec["error_bits"] & b]
+            rec["flag_names"] = [n for n, b in flags if rec["flags"] & b]
+            f.write(json.dumps(rec) + "\n")
+    print("wrote %d sweep records to %s" % (rows.shape[0], path))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--velodyne", help="directory of KITTI raw velodyne .bin sweeps")
@@ -88,6 +104,8 @@ def main():
                     help="publish /laser_cloud_map from the mapping stream every N frames (vloam_limits::map_pub_number; the KITTI launch file: 20) "
                          "and write each publication as OUT/map_<frame>.npy (float32 [n, 4]); read through vloam_get_published_map, which waits "
                          "for the publication only, never for the pipeline")
+    ap.add_argument("--sweep-log", help="write the per-sweep diagnostics log (vloam_limits_ext::sweep_log) as JSON lines to this file: one line per sweep, read "
+                                        "once after the run from the rows the stage streams wrote, with no per-frame synchronisation")
     ap.add_argument("--imu-T-velo", help="16 numbers, row major (default: KITTI 2011_09_26 extrinsics, approx.)")
     ap.add_argument("--imu-T-cam0", help="16 numbers, row major")
     a = ap.parse_args()
@@ -131,7 +149,8 @@ def main():
     loam = vl.LidarOdometryMapping(device=a.device, mapping_skip_frame=a.mapping_skip_frame, detach_VO_LO=0 if a.vloam else 1,
                                    timing=1 if (a.metrics and not a.vloam) else 0, **img_cfg,
                                    **({"max_ring_points": a.max_ring_points} if a.max_ring_points else {}),
-                                   **({"map_pub_number": a.map_pub_number} if a.map_pub_number else {}))
+                                   **({"map_pub_number": a.map_pub_number} if a.map_pub_number else {}),
+                                   **({"sweep_log": 1} if a.sweep_log else {}))
     hd = loam.hd
     if a.vloam:
         if real_images:   # PointCloudUtil::loadTransformations (point_cloud_util.cpp:5-116)
@@ -205,6 +224,8 @@ def main():
             mf.write(json.dumps(rec) + "\n")
     if mf:
         mf.close()
+    if a.sweep_log:
+        write_sweep_log(vl, hd, a.sweep_log)
     kio.write_trajectory(os.path.join(a.out, "LO0.txt"), lo_rows)
     kio.write_trajectory(os.path.join(a.out, "MO0.txt"), mo_rows)
     if vo_rows:

@@ -30,6 +30,8 @@ ap.add_argument("--no-batch", action="store_true")
 ap.add_argument("--map-pub-number", type=int, default=0, help="vloam_limits::map_pub_number of the handles")
 ap.add_argument("--publish-registered-cloud", action="store_true", help="vloam_limits::publish_registered_cloud of the handles")
 ap.add_argument("--publish-ab", type=int, default=0, help="that many off / on pairs of single-sequence runs, products off first; replaces the normal run")
+ap.add_argument("--sweep-log-ab", type=int, default=0, help="that many off / on pairs of single-sequence runs (then of --sessions batches unless --no-batch), "
+                                                         "vloam_limits_ext::sweep_log off first; replaces the normal run")
 ap.add_argument("--map-log2", type=int, default=22, help="map_capacity_log2 of the handles (voxel table slots)")
 ap.add_argument("--procs", type=int, default=32, help="worker processes for the synthesis (1 under rocprofv3: it follows forked children)")
 ap.add_argument("--from-idle", default="", help="comma-separated sweep counts: time that many sweeps of ONE sequence from a drained pipeline (5 repeats each) "
@@ -72,9 +74,10 @@ def run(B, pub=PUB):
         step(k)
     h.sync()
     dt = time.perf_counter() - t0
-    print("B = %2d: %8.0f scans/s   (%.1f us per step)%s" % (B, B * a.steps / dt, 1e6 * dt / a.steps,
-                                                             "   published: map every %d, registered cloud %d" % (pub["map_pub_number"], pub["publish_registered_cloud"])
-                                                             if any(pub.values()) else ""), flush=True)
+    note = "   sweep_log 1" if pub.get("sweep_log") else ""
+    if pub.get("map_pub_number") or pub.get("publish_registered_cloud"):
+        note += "   published: map every %d, registered cloud %d" % (pub["map_pub_number"], pub["publish_registered_cloud"])
+    print("B = %2d: %8.0f scans/s   (%.1f us per step)%s" % (B, B * a.steps / dt, 1e6 * dt / a.steps, note), flush=True)
     if a.table:
         rows = h.profile_table()
         tot = sum(ms for ms, _ in rows.values())
@@ -117,6 +120,12 @@ if a.publish_ab:
     for _ in range(a.publish_ab):
         run(1, dict(map_pub_number=0, publish_registered_cloud=0))
         run(1)
+    sys.exit(0)
+if a.sweep_log_ab:
+    for B in [1] + ([] if a.no_batch else [a.sessions]):
+        for _ in range(a.sweep_log_ab):
+            run(B, dict(sweep_log=0))
+            run(B, dict(sweep_log=1))
     sys.exit(0)
 t1 = None if a.no_single else run(1)
 if a.no_batch:

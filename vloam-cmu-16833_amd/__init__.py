@@ -50,6 +50,23 @@ class Limits(C.Structure):
                 ("max_published_map_points", C.c_int), ("publish_registered_cloud", C.c_int)]
 
 
+class LimitsExt(C.Structure):
+    """vloam_limits_ext: vloam_limits (which keeps its size) and, right behind it, the field that came later (c_api.h)."""
+    _fields_ = [("limits", Limits), ("sweep_log", C.c_int)]
+
+
+# vloam_sweep_record (c_api.h): 32 ints then 8 doubles, 192 bytes
+SWEEP_RECORD_DTYPE = np.dtype([
+    ("frame", "<i4"), ("error_bits", "<i4"), ("flags", "<i4"), ("n_in", "<i4"), ("n_cloud", "<i4"), ("n_sharp", "<i4"), ("n_less_sharp", "<i4"),
+    ("n_flat", "<i4"), ("n_less_flat", "<i4"), ("lo_corner_factors", "<i4", (2,)), ("lo_plane_factors", "<i4", (2,)), ("lo_iterations", "<i4", (2,)),
+    ("lo_termination", "<i4", (2,)), ("n_corner_stack", "<i4"), ("n_surf_stack", "<i4"), ("n_map_corner", "<i4"), ("n_map_surf", "<i4"),
+    ("map_corner_factors", "<i4", (2,)), ("map_surf_factors", "<i4", (2,)), ("map_iterations", "<i4", (2,)), ("map_termination", "<i4", (2,)),
+    ("reserved", "<i4", (3,)), ("lo_initial_cost", "<f8", (2,)), ("lo_final_cost", "<f8", (2,)), ("map_initial_cost", "<f8", (2,)),
+    ("map_final_cost", "<f8", (2,))])
+SWEEP_EMPTY, SWEEP_RING_TOO_LONG, SWEEP_MAP_FULL, SWEEP_MAP_RAW_CAPACITY, SWEEP_STACK_FULL, SWEEP_DS_TIMEOUT, SWEEP_VO_DEGENERATE = 1, 2, 4, 8, 16, 32, 64
+SWEEP_FLAG_FIRST, SWEEP_FLAG_MAP_SKIPPED, SWEEP_FLAG_MAP_NOT_OPTIMIZED, SWEEP_FLAG_LO_LESS_CORR_0, SWEEP_FLAG_LO_LESS_CORR_1, SWEEP_FLAG_SOLVE_DEGRADED = 1, 2, 4, 8, 16, 32
+
+
 class Calib(C.Structure):
     _fields_ = [("cam_T_velo", C.c_float * 16), ("rect0_T_cam", C.c_float * 16), ("P_rect0", C.c_float * 12)]
 
@@ -106,6 +123,17 @@ def default_limits(**kw):
     return lim
 
 
+def default_limits_ext(sweep_log=0, **kw):
+    ext = LimitsExt()
+    lib().vloam_default_limits_ext(C.byref(ext))
+    for k, v in kw.items():
+        if not hasattr(ext.limits, k):
+            raise AttributeError("vloam_limits has no field %r" % k)
+        setattr(ext.limits, k, v)
+    ext.sweep_log = int(sweep_log)
+    return ext
+
+
 def _fp(a):
     return a.ctypes.data_as(C.c_void_p)
 
@@ -114,21 +142,26 @@ class Handle:
     """One sequence on one GPU (``vloam_handle``)."""
 
     def __init__(self, device=0, n_sessions=1, max_surf_stack_points=None, map_pub_number=None, max_published_map_points=None,
-                 publish_registered_cloud=None, **cfg):
+                 publish_registered_cloud=None, sweep_log=None, **cfg):
         """n_sessions > 1: a batched handle — that many independent sequences advanced in lock step by batch_process_scan*;
         select(b) chooses the session the getters read.  max_surf_stack_points: vloam_limits::max_surf_stack_points (None: the default,
         24576; multiples of 8192 up to 131072 add the large stack tier).  map_pub_number / max_published_map_points /
         publish_registered_cloud: the clouds of LaserMapping::publish as products of the mapping stream (vloam_limits; None: off),
-        read with published_map() / published_cloud() / published_device_ptr()."""
+        read with published_map() / published_cloud() / published_device_ptr().  sweep_log: vloam_limits_ext::sweep_log (None / 0: off): one
+        diagnostics record per sweep, written by the stage streams, read with sweep_log()."""
         self.L = lib()
         self.cfg = default_config(**cfg)
         lim = dict(max_surf_stack_points=max_surf_stack_points, map_pub_number=map_pub_number, max_published_map_points=max_published_map_points,
                    publish_registered_cloud=publish_registered_cloud)
         self.limits = default_limits(**{k: int(v) for k, v in lim.items() if v is not None})
+        self.limits_ext = None
+        if sweep_log is not None:   # the library is told by struct_size that sweep_log lies behind the limits
+            self.limits_ext = LimitsExt(self.limits, int(sweep_log))
+            self.limits_ext.limits.struct_size = C.sizeof(LimitsExt)
         self.surf_stack_cap = self.limits.max_surf_stack_points or K_STACK_CAP_SURF
         self.h = C.c_void_p()
         self.n_sessions = int(n_sessions)
-        self._chk(self.L.vloam_create_with_limits(C.byref(self.cfg), C.byref(self.limits), int(device), self.n_sessions, C.byref(self.h)))
+        self._chk(self.L.vloam_create_with_limits(C.byref(self.cfg), C.byref(self.limits_ext or self.limits), int(device), self.n_sessions, C.byref(self.h)))
 
     def _chk(self, st):
         if st != VLOAM_OK:
@@ -255,6 +288,20 @@ class Handle:
     def trajectory_device_ptr(self):
         p, b = C.c_void_p(), C.c_longlong(0)
         self._chk(self.L.vloam_trajectory_device_ptr(self.h, C.byref(p), C.byref(b)))
+        return p.value, b.value
+
+    def sweep_log(self, first=0, count=None):
+        """vloam_get_sweep_log: the diagnostics rows of sweeps first .. first + count - 1 of the selected session as a structured array
+        (SWEEP_RECORD_DTYPE).  Waits for the work behind the last row asked for only, not for the pipeline."""
+        if count is None:
+            count = self.frame_count() - first
+        out = np.zeros(max(count, 1), dtype=SWEEP_RECORD_DTYPE)
+        self._chk(self.L.vloam_get_sweep_log(self.h, int(first), int(count), _fp(out)))
+        return out[:count]
+
+    def sweep_log_device_ptr(self):
+        p, b = C.c_void_p(), C.c_longlong(0)
+        self._chk(self.L.vloam_sweep_log_device_ptr(self.h, C.byref(p), C.byref(b)))
         return p.value, b.value
 
     def profile_kernel(self, name, max_launches=4096):

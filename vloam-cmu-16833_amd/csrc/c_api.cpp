@@ -10,6 +10,7 @@
 #include <atomic>
 #include <limits.h>
 #include <stdarg.h>
+#include <stddef.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -24,6 +25,7 @@
 #include "sr_kernels.h"
 #include "stage_input_check.h"
 #include "stream_plan.h"
+#include "sweep_log.h"
 #include "vloam_device.h"
 #include "vo_kernels.h"
 #include "img_kernels.h"
@@ -142,6 +144,16 @@ struct vloam_handle {
   double* lo_resid[2] = {nullptr, nullptr};
   double* traj = nullptr;      // [max_frames][14]
   double* vo_traj = nullptr;   // [max_frames][7] world_VOT_base_last per frame (coupled frame loop)
+  // per-sweep diagnostics log (vloam_limits_ext::sweep_log; everything below stays null / unused on a handle without it).  ev_log: the event behind
+  // each stage's row write, a ring of kLogEvents sweeps per stage; a slot that a later sweep has taken over belongs to a sweep whose writes
+  // the host has long seen finished (enqueue_sr waits for the odometry of sweep k - kSets + 1 and the mapping of sweep k - kSets before it
+  // enqueues sweep k, and every stream is in order), so the reader only ever waits for an event that still carries its sweep's number
+  bool sweep_log = false;
+  vloam_sweep_record* log_rows = nullptr;   // [max_frames]
+  SweepLogScratch* log_scratch = nullptr;
+  static constexpr int kLogEvents = 2 * kSets, kLogStages = 3;   // scan registration, odometry, mapping
+  hipEvent_t ev_log[kLogStages][kLogEvents] = {};
+  int ev_log_frame[kLogStages][kLogEvents];
   hipEvent_t ev_vo[kSets] = {};     // depth map + matches of the frame in set c are in HBM
   bool vo_frame[kSets] = {};        // the sweep in set c came through vloam_process_frame (its odometry is preceded by the VO solve)
   bool have_extrinsics = false;
@@ -253,6 +265,7 @@ static vloam_status handle_layout(vloam_handle* h, Arena& A) {
   TAKE(h->lo_queue_n, 2);
   TAKE(h->traj, (size_t)cfg->max_frames * 14);
   TAKE(h->vo_traj, (size_t)cfg->max_frames * 7);
+  if (h->sweep_log) { TAKE(h->log_rows, (size_t)cfg->max_frames); TAKE(h->log_scratch, 1); }
   if (map_layout(&h->map, h->cfg, A) != VLOAM_OK) { set_err("map_layout failed"); return VLOAM_ERR_HIP; }
   TAKE(h->sync_pool, kSyncCand * kSyncStride / sizeof(double));
   if (vo_layout(&h->vo, h->cfg, A) != VLOAM_OK) { set_err("vo_layout failed"); return VLOAM_ERR_HIP; }
@@ -274,8 +287,11 @@ static inline T* SEL(const vloam_handle* h, T* p) { return p ? (T*)((char*)p + (
 // 1. What a configuration must satisfy, checked before any HIP call (so without a device too).  *lim_out: the limits to build with, every
 // field resolved (defaults for 0, fields the caller's struct_size does not reach read as 0).
 constexpr int kLimitsSizeV1 = 8;   // sizeof(vloam_limits) when it ended behind max_surf_stack_points
-static vloam_status validate_create(const vloam_config* cfg, const vloam_limits* lim, int n_sessions, vloam_limits* lim_out) {
+static_assert(sizeof(vloam_limits) == 20 && sizeof(vloam_limits_ext) == 24 && offsetof(vloam_limits_ext, sweep_log) == sizeof(vloam_limits),
+              "vloam_limits keeps its size; sweep_log lies right behind it");
+static vloam_status validate_create(const vloam_config* cfg, const vloam_limits* lim, int n_sessions, vloam_limits* lim_out, int* sweep_log_out) {
   memset(lim_out, 0, sizeof(*lim_out));
+  *sweep_log_out = 0;
   lim_out->struct_size = (int)sizeof(vloam_limits);
   lim_out->max_surf_stack_points = kStackCapSurf;
   if (lim) {
@@ -302,6 +318,13 @@ static vloam_status validate_create(const vloam_config* cfg, const vloam_limits*
       lim_out->map_pub_number = N;
       lim_out->max_published_map_points = N > 0 ? (C != 0 ? C : (int)kPubMapCapDefault) : 0;
       lim_out->publish_registered_cloud = R;
+    }
+    // exactly vloam_limits_ext's size: the caller's struct IS one.  Any other accepted size says nothing about what lies behind vloam_limits
+    // (0 = sizeof(vloam_limits); a larger size is a later header's struct, of which the fields of vloam_limits are read): nothing there is read
+    if (lim->struct_size == (int)sizeof(vloam_limits_ext)) {
+      const int L = reinterpret_cast<const vloam_limits_ext*>(lim)->sweep_log;
+      if (L != 0 && L != 1) { set_err("vloam_limits_ext: sweep_log must be 0 or 1"); return VLOAM_ERR_INVALID; }
+      *sweep_log_out = L;
     }
   }
   if (n_sessions < 1 || n_sessions > kMaxBatch) { set_err("n_sessions must be 1..%d", kMaxBatch); return VLOAM_ERR_INVALID; }
@@ -435,6 +458,11 @@ static vloam_status init_sessions(vloam_handle* h, int n_sessions, int n_cus) {
     HIPCHK(hipEventCreateWithFlags(&h->ev_vo[k], hipEventDisableTiming));
     HIPCHK(hipEventCreateWithFlags(&h->ev_img[k], hipEventDisableTiming));
   }
+  if (h->sweep_log) {
+    HIPCHK(sweep_log_init(h->stream, h->log_rows, h->cfg.max_frames));
+    for (int s = 0; s < vloam_handle::kLogStages; s++)
+      for (int k = 0; k < vloam_handle::kLogEvents; k++) HIPCHK(hipEventCreateWithFlags(&h->ev_log[s][k], hipEventDisableTiming | hipEventBlockingSync));
+  }
   HIPCHK(hipStreamSynchronize(h->stream));
   // ---- the other sessions start as byte-for-byte copies of session 0
   for (int b = 1; b < n_sessions; b++)
@@ -478,6 +506,12 @@ void vloam_default_limits(vloam_limits* lim) {
   lim->publish_registered_cloud = 0;
 }
 
+void vloam_default_limits_ext(vloam_limits_ext* lim) {
+  vloam_default_limits(&lim->limits);
+  lim->limits.struct_size = (int)sizeof(vloam_limits_ext);
+  lim->sweep_log = 0;
+}
+
 vloam_status vloam_create_batch(const vloam_config* cfg, int device, int n_sessions, vloam_handle** out) {
   return vloam_create_with_limits(cfg, nullptr, device, n_sessions, out);
 }
@@ -485,7 +519,8 @@ vloam_status vloam_create_batch(const vloam_config* cfg, int device, int n_sessi
 vloam_status vloam_create_with_limits(const vloam_config* cfg, const vloam_limits* lim, int device, int n_sessions, vloam_handle** out) {
   if (!cfg || !out) { set_err("null argument"); return VLOAM_ERR_INVALID; }
   vloam_limits lims;
-  TRY(validate_create(cfg, lim, n_sessions, &lims));
+  int sweep_log = 0;
+  TRY(validate_create(cfg, lim, n_sessions, &lims, &sweep_log));
   // A handle drives two to six HIP streams that must run side by side (scan registration | odometry [| mapping | scan-feature VoxelGrid]
   // [| images] [| host-sweep copies]).  GPU_MAX_HW_QUEUES (read by the runtime when it initialises: it belongs to the HOST's environment, and a
   // library must not setenv() behind a multi-threaded host) caps each of the runtime's three priority pools of hardware queues; the handle
@@ -522,6 +557,8 @@ vloam_status vloam_create_with_limits(const vloam_config* cfg, const vloam_limit
   h->map.pub.skip_n = cfg->mapping_skip_frame;
   h->map.pub.cap = lims.max_published_map_points;
   h->map.pub.cloud_on = lims.publish_registered_cloud;
+  h->sweep_log = sweep_log != 0;
+  for (int s = 0; s < vloam_handle::kLogStages; s++) for (int k = 0; k < vloam_handle::kLogEvents; k++) h->ev_log_frame[s][k] = -1;
   h->device = device;
   *out = nullptr;
   vloam_status st = create_streams(h, plan, cfg);
@@ -562,6 +599,7 @@ vloam_status vloam_destroy(vloam_handle* h) {
   for (int k = 0; k < 6; k++) if (h->ev[k]) (void)hipEventDestroy(h->ev[k]);
   for (int k = 0; k < vloam_handle::kSets; k++)
     for (hipEvent_t e : {h->ev_sr[k], h->ev_lo[k], h->ev_map[k], h->ev_stack[k], h->ev_vo[k], h->ev_img[k]}) if (e) (void)hipEventDestroy(e);
+  for (int s = 0; s < vloam_handle::kLogStages; s++) for (hipEvent_t e : h->ev_log[s]) if (e) (void)hipEventDestroy(e);
   for (hipEvent_t e : h->prof_events) (void)hipEventDestroy(e);
   for (hipStream_t st : {h->s_copy, h->stream, h->s_lo, h->s_map, h->s_ds, h->s_img}) if (st) (void)hipStreamDestroy(st);
   map_destroy(&h->map);
@@ -644,6 +682,13 @@ static vloam_status enqueue_scan_feature_grid(vloam_handle* h, const SRBuffers& 
   return VLOAM_OK;
 }
 
+// the event a stage's row write of sweep `frame` is bound to (sweep log)
+static inline hipEvent_t log_event(vloam_handle* h, int stage, int frame) {
+  const int slot = frame % vloam_handle::kLogEvents;
+  h->ev_log_frame[stage][slot] = frame;
+  return h->ev_log[stage][slot];
+}
+
 static vloam_status enqueue_sr(vloam_handle* h, const BatchIn& bi) {
   TRY(check_sweeps(h, (const void* const*)bi.in, bi.n, true));
   int n = 0;
@@ -672,6 +717,7 @@ static vloam_status enqueue_sr(vloam_handle* h, const BatchIn& bi) {
   // == kdtreeCornerLast / kdtreeSurfLast->setInputCloud (laser_odometry.cpp:525-526): index this sweep's clouds for the next one
   // (the next sweep's ev_sr is recorded behind this on the same stream, so its odometry sees the finished grids)
   lo_grid_build_launch(h->stream, h->se, h->sr[cur].less_sharp, h->sr[cur].less_flat, h->sr[cur].S, h->grid[cur], &h->prof);
+  if (h->sweep_log) sweep_log_sr_launch(h->stream, h->se, h->log_rows, k, h->sr[cur].S, bi, &h->prof, log_event(h, 0, k));
   HIPCHK(hipGetLastError());
   if (h->cfg.timing) HIPCHK(hipEventRecord(h->ev[1], h->stream));
   TRY(enqueue_scan_feature_grid(h, h->sr[cur], k, cur));
@@ -722,6 +768,9 @@ static vloam_status enqueue_lo(vloam_handle* h, int frame) {
     lo_finish_launch(h->s_lo, h->se, h->lo, h->traj + (size_t)frame * 14, false, &h->prof);
     HIPCHK(hipEventRecord(h->ev_lo[cur], h->s_lo));
   }
+  if (h->sweep_log)
+    sweep_log_lo_launch(h->s_lo, h->se, h->log_rows, frame, h->log_scratch, h->lo, h->lo_corr[0], h->lo_corr[1], h->lo_rec, &h->map.frame->fallback_solves,
+                        !h->cfg.with_mapping, &h->prof, log_event(h, 1, frame));
   HIPCHK(hipGetLastError());
   if (h->cfg.timing) HIPCHK(hipEventRecord(h->ev[3], h->s_lo));
   return VLOAM_OK;
@@ -739,9 +788,14 @@ static vloam_status enqueue_map(vloam_handle* h, int frame) {
   // the registered cloud (vloam_limits::publish_registered_cloud) still reads the sweep's buffer set behind the mapping: such a sweep releases the
   // set behind k_map_register.  The published map reads the voxel tables only, so it leaves the event where it is.
   const bool publishes = map_publishes(&h->map, skip), reads_set = h->map.pub.cloud_on != 0;
+  if (h->sweep_log) sweep_log_map_begin_launch(h->s_map, h->se, h->log_scratch, h->map.frame, h->map.stack_info[cur], skip, &h->prof);
   vloam_status s = map_enqueue(&h->map, h->cfg, h->s_map, h->sr[cur], h->lo, sub_pose ? h->sub_row : h->traj + (size_t)frame * 14, skip, cur, &h->prof,
                                reads_set ? nullptr : h->ev_map[cur]);
   if (s != VLOAM_OK) { set_err("map_enqueue failed: %s", hipGetErrorString(hipGetLastError())); return VLOAM_ERR_HIP; }
+  if (h->sweep_log) {
+    sweep_log_map_launch(h->s_map, h->se, h->log_rows, frame, h->log_scratch, h->map.state, h->map.frame, h->map.rec, skip, &h->prof, log_event(h, 2, frame));
+    HIPCHK(hipGetLastError());
+  }
   if (sub_pose) HIPCHK(hipMemcpyAsync(h->traj + (size_t)frame * 14 + 7, h->sub_row + 7, 7 * sizeof(double), hipMemcpyDeviceToDevice, h->s_map));   // the map half of the log
   if (publishes) {
     const bool sub_cloud = h->sub_cloud_frame == frame;   // laserCloudFullRes as handed to LaserMapping::input (what vloam_get_features(h, 11) shows)
@@ -1573,6 +1627,35 @@ vloam_status vloam_trajectory_device_ptr(vloam_handle* h, void** d_ptr, long lon
   if (!h || !d_ptr || !bytes) return VLOAM_ERR_INVALID;
   *d_ptr = SEL(h, h->traj);
   *bytes = (long long)h->cfg.max_frames * 14 * (long long)sizeof(double);
+  return VLOAM_OK;
+}
+
+// ------------------------------------------------------------------ per-sweep diagnostics log (vloam_limits_ext::sweep_log)
+static vloam_status require_sweep_log(const vloam_handle* h) {
+  if (!h->sweep_log) { set_err("the handle was created without vloam_limits_ext::sweep_log: no per-sweep log is kept"); return VLOAM_ERR_ORDER; }
+  return VLOAM_OK;
+}
+vloam_status vloam_get_sweep_log(vloam_handle* h, int first, int count, vloam_sweep_record* out) {
+  if (!h) return VLOAM_ERR_INVALID;
+  TRY(require_sweep_log(h));
+  if (!out || first < 0 || count < 0 || first + count > h->frame + (h->pend.valid ? 1 : 0)) {   // (a host sweep in flight is enqueued by the drain below)
+    set_err("vloam_get_sweep_log: sweeps %d .. %d are not all handed over (vloam_frame_count)", first, first + count - 1); return VLOAM_ERR_INVALID;
+  }
+  HIPCHK(hipSetDevice(h->device));
+  TRY(drain_deferred(h, 0, 0));   // enqueue only: every stage of every sweep handed over so far is then on its stream
+  if (count == 0) return VLOAM_OK;
+  // rows complete in sweep order on every stream: wait for the three writers of the LAST row asked for, nothing younger
+  const int last = first + count - 1, slot = last % vloam_handle::kLogEvents;
+  for (int s = 0; s < vloam_handle::kLogStages; s++)
+    if (h->ev_log_frame[s][slot] == last) HIPCHK(hipEventSynchronize(h->ev_log[s][slot]));
+  HIPCHK(hipMemcpy(out, SEL(h, h->log_rows) + first, sizeof(vloam_sweep_record) * (size_t)count, hipMemcpyDeviceToHost));
+  return VLOAM_OK;
+}
+vloam_status vloam_sweep_log_device_ptr(vloam_handle* h, void** d_rows, long long* bytes) {
+  if (!h || !d_rows || !bytes) return VLOAM_ERR_INVALID;
+  TRY(require_sweep_log(h));
+  *d_rows = SEL(h, h->log_rows);
+  *bytes = (long long)h->cfg.max_frames * (long long)sizeof(vloam_sweep_record);
   return VLOAM_OK;
 }
 
