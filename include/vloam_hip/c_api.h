@@ -115,6 +115,28 @@ void vloam_default_limits(vloam_limits* lim);
  * VLOAM_ERR_HIP: the arenas (the publication buffers are part of them) do not fit the device's memory. */
 vloam_status vloam_create_with_limits(const vloam_config* cfg, const vloam_limits* lim, int device, int n_sessions, vloam_handle** out);
 
+/* ---- Growable voxel map (opt-in, single-sequence handles).  The map is two open-addressing tables of 2^map_capacity_log2 slots; a fixed handle
+ * whose table passes 60 % of its slots is finished (VLOAM_ERR_CAPACITY from every vloam_sync, for good).  With grow = 1 the handle STARTS at
+ * map_capacity_log2, keeps the two tables in allocations of their own, and doubles a table between two sweeps whenever the sweeps enqueued
+ * so far could fill it (a bound, not a count: INTEGRATION.md section 5), up to 2^max_capacity_log2 slots per table.  Below that ceiling no
+ * table passes 60 % of its slots (tombstones included), the load a fixed handle reports as full; at the ceiling the fixed handle's behaviour returns.  Poses and map are what a fixed handle of any sufficient size
+ * computes: slot positions do not matter.  A failed allocation of a larger table is reported (VLOAM_ERR_HIP) by the call that tried; the old
+ * table stays in use and the handle stays usable until that table really fills.
+ * struct_size: sizeof(vloam_map_options) as the caller compiled it. */
+typedef struct vloam_map_options {
+  int struct_size;            /* sizeof(vloam_map_options) as the caller compiled it */
+  int grow;                   /* 0 | 1 */
+  int max_capacity_log2;      /* ceiling per table; 0 = 28; >= cfg->map_capacity_log2 (after its clamp to 10..28), <= 28 */
+} vloam_map_options;
+void vloam_default_map_options(vloam_map_options* opt);
+/* vloam_create_with_limits with map options.  lim: any form vloam_create_with_limits accepts, or NULL.  opt == NULL or grow == 0: the same
+ * handle as vloam_create_with_limits(cfg, lim, device, n_sessions, out) in every respect.  VLOAM_ERR_INVALID (before any device call), each
+ * with its own vloam_last_error(): a struct_size other than sizeof(vloam_map_options); a grow other than 0 or 1 or a max_capacity_log2 that
+ * is neither 0 nor in [map_capacity_log2, 28]; grow == 1 with n_sessions > 1 or cfg->with_mapping == 0 (a batch's kernels address session
+ * b's tables at the arena stride: DESIGN.md section 8). */
+vloam_status vloam_create_with_options(const vloam_config* cfg, const vloam_limits* lim, const vloam_map_options* opt, int device, int n_sessions,
+                                       vloam_handle** out);
+
 /* ---- Batched execution: one handle, n_sessions independent sequences advanced in lock step.  Every kernel of the sweep chain is
  * launched once per sweep for ALL sessions (session index in blockIdx.z), so n_sessions sequences cost one launch chain — the way to
  * fill the chip with a path whose single-sequence form is a latency chain.  Each session owns an identical arena of
@@ -282,7 +304,7 @@ vloam_status vloam_trajectory_device_ptr(vloam_handle* h, void** d_ptr, long lon
 enum {   /* vloam_sweep_record::error_bits: raised BY THIS SWEEP; the condition is the one vloam_sync words for the handle */
   VLOAM_SWEEP_EMPTY = 1,            /* no point of the sweep survived NaN / minimum_range removal (vloam_sync: VLOAM_ERR_EMPTY) */
   VLOAM_SWEEP_RING_TOO_LONG = 2,    /* a ring held more than max_ring_points points and was dropped (VLOAM_ERR_CAPACITY) */
-  VLOAM_SWEEP_MAP_FULL = 4,         /* voxel hash full (map_capacity_log2); the handle keeps this bit for good: the row is the sweep that raised it first */
+  VLOAM_SWEEP_MAP_FULL = 4,         /* voxel hash full (map_capacity_log2; on a growable handle: at vloam_map_options::max_capacity_log2); the handle keeps this bit for good: the row is the sweep that raised it first */
   VLOAM_SWEEP_MAP_RAW_CAPACITY = 8, /* raw-point capacity of the map exceeded (more than 255 un-merged points in a voxel of a cube outside the valid
                                        block, or more than 64 raw voxels around one query); first sweep to raise it, like MAP_FULL */
   VLOAM_SWEEP_STACK_FULL = 16,      /* mapping factor table full: more surf points after VoxelGrid than max_surf_stack_points */
@@ -444,7 +466,9 @@ const char* vloam_profile_kernel_name(int k);
 /* Health counters (synchronises): out8[0] cooperative Levenberg-Marquardt solves that found their partner workgroups missing and finished on ONE
  * workgroup instead (same factors, same trust-region loop; the pose agrees with the cooperative form to round-off, the solve is ~0.5 s late
  * because the workgroup first waited for its partners), summed over the sessions; out8[1] 1 once the handle has reacted to that by launching
- * one-workgroup solves only (vloam_sync does, see the co-residency note at vloam_create_batch); out8[2] voxel-table rebuilds; out8[3..7] 0. */
+ * one-workgroup solves only (vloam_sync does, see the co-residency note at vloam_create_batch); out8[2] voxel-table rebuilds; on a growable handle
+ * (vloam_map_options::grow) out8[3] growth steps enqueued so far (both tables) and out8[4], out8[5] the current log2 of the corner and the surf
+ * table, 0 on any other handle; out8[6..7] 0. */
 vloam_status vloam_get_health(vloam_handle* h, long long out8[8]);
 
 /* Timing of the last vloam_sync()ed scans: HIP-event milliseconds accumulated per stage

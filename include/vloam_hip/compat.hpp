@@ -112,6 +112,8 @@ inline Cloud from_cloud_ptr(const P& in) {
 // A Session / LidarOdometryMapping created with a vloam_config* takes the handle's capacities from it: max_points (points of a sweep),
 // map_capacity_log2, and max_ring_points (points of one scan line: 4096 by default; 4097 .. 16384 for sensors whose scan lines are longer —
 // an HDL-32E at 5 Hz, an HDL-64E with two lasers in one scan line, 4 096-column heads).
+// The growable voxel map (vloam_map_options::grow: tables that start at map_capacity_log2 and double between sweeps) is an option of the C call
+// vloam_create_with_options and has no constructor here yet; a Session always holds a fixed-size map.
 class Session {  // one vloam_handle == one sequence on one GPU; shared by the three stage objects
  public:
   // max_surf_stack_points != 0: vloam_limits::max_surf_stack_points (the constructor LaserMapping(device, cfg, max_surf_stack_points) uses it)

@@ -3,7 +3,11 @@
 after a short warm-up.  For A/B-ing a kernel change; bench.py remains the measurement of record.
   python tools/throughput_probe.py [--sessions 8] [--warm 60] [--steps 120] [--table]
   python tools/throughput_probe.py --no-batch --steps 200 --map-pub-number 20 --publish-registered-cloud --publish-ab 3
-      the single sequence with the published clouds of the mapping stream (vloam_limits) off and on, alternately, in one process"""
+      the single sequence with the published clouds of the mapping stream (vloam_limits) off and on, alternately, in one process
+  python tools/throughput_probe.py --no-batch --steps 2000 --map-log2 20 --map-grow-ab 3
+      the single sequence on a fixed handle and on a growable one (vloam_map_options::grow) of the same size, alternately
+  python tools/throughput_probe.py --grow-step 18,21
+      one forced growth step of both tables from 2^18 and from 2^21 slots with the warm-up's map in them (for a kernel trace: --procs 1)"""
 import argparse
 import multiprocessing as mp
 import os
@@ -32,6 +36,8 @@ ap.add_argument("--publish-registered-cloud", action="store_true", help="vloam_l
 ap.add_argument("--publish-ab", type=int, default=0, help="that many off / on pairs of single-sequence runs, products off first; replaces the normal run")
 ap.add_argument("--sweep-log-ab", type=int, default=0, help="that many off / on pairs of single-sequence runs (then of --sessions batches unless --no-batch), "
                                                          "vloam_limits_ext::sweep_log off first; replaces the normal run")
+ap.add_argument("--map-grow-ab", type=int, default=0, help="that many fixed / growable pairs of single-sequence runs at --map-log2, fixed first; replaces the normal run")
+ap.add_argument("--grow-step", default="", help="comma-separated log2 sizes: a growable handle of that size, --warm sweeps, one forced growth step, timed on the host; replaces the normal run")
 ap.add_argument("--map-log2", type=int, default=22, help="map_capacity_log2 of the handles (voxel table slots)")
 ap.add_argument("--procs", type=int, default=32, help="worker processes for the synthesis (1 under rocprofv3: it follows forked children)")
 ap.add_argument("--from-idle", default="", help="comma-separated sweep counts: time that many sweeps of ONE sequence from a drained pipeline (5 repeats each) "
@@ -83,9 +89,30 @@ def run(B, pub=PUB):
         tot = sum(ms for ms, _ in rows.values())
         for name, (ms, cnt) in sorted(rows.items(), key=lambda kv: -kv[1][0])[:14]:
             print("   %-20s %6.1f us x %5d  (%4.1f %%)" % (name, 1e3 * ms / max(cnt, 1), cnt, 100 * ms / tot))
+    if pub.get("map_grow"):
+        print("         growable: %s" % (h.health(),), flush=True)
     tr = h.trajectory(0, a.warm + a.steps)
     h.close()
     return tr
+
+
+def grow_step(sizes):
+    for lg in sizes:
+        h = vl.Handle(0, with_mapping=1, max_frames=a.warm + 8, map_capacity_log2=lg, map_grow=1)
+        for k in range(a.warm):
+            h.process_scan_device(ptr(k), npts)
+            if k % 4 == 3:
+                h.sync()
+        h.sync()
+        before, keys = h.health(), h.map_health()["keys"]
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        h.map_force_grow()
+        h.sync()
+        dt = time.perf_counter() - t0
+        print("start 2^%d: tables %s with %s keys -> %s: %.3f ms on the host for both steps (allocation, memsets, k_map_grow, sync); growth steps before: %d"
+              % (lg, before["map_log2"], keys, h.health()["map_log2"], 1e3 * dt, before["map_growth_steps"]), flush=True)
+        h.close()
 
 
 def from_idle(counts):
@@ -115,6 +142,14 @@ def from_idle(counts):
 
 if a.from_idle:
     from_idle([int(v) for v in a.from_idle.split(",")])
+    sys.exit(0)
+if a.grow_step:
+    grow_step([int(v) for v in a.grow_step.split(",")])
+    sys.exit(0)
+if a.map_grow_ab:
+    for _ in range(a.map_grow_ab):
+        run(1, dict())
+        run(1, dict(map_grow=1))
     sys.exit(0)
 if a.publish_ab:
     for _ in range(a.publish_ab):

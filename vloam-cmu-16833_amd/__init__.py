@@ -55,6 +55,11 @@ class LimitsExt(C.Structure):
     _fields_ = [("limits", Limits), ("sweep_log", C.c_int)]
 
 
+class MapOptions(C.Structure):
+    """vloam_map_options: the growable voxel map (c_api.h; vloam_create_with_options)."""
+    _fields_ = [("struct_size", C.c_int), ("grow", C.c_int), ("max_capacity_log2", C.c_int)]
+
+
 # vloam_sweep_record (c_api.h): 32 ints then 8 doubles, 192 bytes
 SWEEP_RECORD_DTYPE = np.dtype([
     ("frame", "<i4"), ("error_bits", "<i4"), ("flags", "<i4"), ("n_in", "<i4"), ("n_cloud", "<i4"), ("n_sharp", "<i4"), ("n_less_sharp", "<i4"),
@@ -134,6 +139,16 @@ def default_limits_ext(sweep_log=0, **kw):
     return ext
 
 
+def default_map_options(**kw):
+    opt = MapOptions()
+    lib().vloam_default_map_options(C.byref(opt))
+    for k, v in kw.items():
+        if not hasattr(opt, k):
+            raise AttributeError("vloam_map_options has no field %r" % k)
+        setattr(opt, k, v)
+    return opt
+
+
 def _fp(a):
     return a.ctypes.data_as(C.c_void_p)
 
@@ -142,13 +157,15 @@ class Handle:
     """One sequence on one GPU (``vloam_handle``)."""
 
     def __init__(self, device=0, n_sessions=1, max_surf_stack_points=None, map_pub_number=None, max_published_map_points=None,
-                 publish_registered_cloud=None, sweep_log=None, **cfg):
+                 publish_registered_cloud=None, sweep_log=None, map_grow=None, map_max_capacity_log2=None, **cfg):
         """n_sessions > 1: a batched handle — that many independent sequences advanced in lock step by batch_process_scan*;
         select(b) chooses the session the getters read.  max_surf_stack_points: vloam_limits::max_surf_stack_points (None: the default,
         24576; multiples of 8192 up to 131072 add the large stack tier).  map_pub_number / max_published_map_points /
         publish_registered_cloud: the clouds of LaserMapping::publish as products of the mapping stream (vloam_limits; None: off),
         read with published_map() / published_cloud() / published_device_ptr().  sweep_log: vloam_limits_ext::sweep_log (None / 0: off): one
-        diagnostics record per sweep, written by the stage streams, read with sweep_log()."""
+        diagnostics record per sweep, written by the stage streams, read with sweep_log().  map_grow / map_max_capacity_log2:
+        vloam_map_options (None: no options struct is passed): a single-sequence handle whose voxel tables start at map_capacity_log2 and
+        double whenever they could fill, up to the ceiling; health() then reports the growth steps and the tables' sizes."""
         self.L = lib()
         self.cfg = default_config(**cfg)
         lim = dict(max_surf_stack_points=max_surf_stack_points, map_pub_number=map_pub_number, max_published_map_points=max_published_map_points,
@@ -161,7 +178,13 @@ class Handle:
         self.surf_stack_cap = self.limits.max_surf_stack_points or K_STACK_CAP_SURF
         self.h = C.c_void_p()
         self.n_sessions = int(n_sessions)
-        self._chk(self.L.vloam_create_with_limits(C.byref(self.cfg), C.byref(self.limits_ext or self.limits), int(device), self.n_sessions, C.byref(self.h)))
+        self.map_options = None
+        if map_grow is not None or map_max_capacity_log2 is not None:
+            self.map_options = default_map_options(grow=int(map_grow or 0), max_capacity_log2=int(map_max_capacity_log2 or 0))
+            self._chk(self.L.vloam_create_with_options(C.byref(self.cfg), C.byref(self.limits_ext or self.limits), C.byref(self.map_options), int(device),
+                                                       self.n_sessions, C.byref(self.h)))
+        else:
+            self._chk(self.L.vloam_create_with_limits(C.byref(self.cfg), C.byref(self.limits_ext or self.limits), int(device), self.n_sessions, C.byref(self.h)))
 
     def _chk(self, st):
         if st != VLOAM_OK:
@@ -336,10 +359,12 @@ class Handle:
         return dict(zip(names, [int(v) for v in c]))
 
     def health(self):
-        """vloam_get_health: cooperative solves that degraded to one workgroup, whether the handle switched to one-workgroup solves, table rebuilds."""
+        """vloam_get_health: cooperative solves that degraded to one workgroup, whether the handle switched to one-workgroup solves, table rebuilds;
+        on a growable handle (map_grow=1) the growth steps enqueued so far and the log2 of the corner / surf table (0 on any other handle)."""
         v = np.zeros(8, dtype=np.int64)
         self._chk(self.L.vloam_get_health(self.h, _fp(v)))
-        return dict(fallback_solves=int(v[0]), one_workgroup_solves=bool(v[1]), rebuilds=int(v[2]))
+        return dict(fallback_solves=int(v[0]), one_workgroup_solves=bool(v[1]), rebuilds=int(v[2]), map_growth_steps=int(v[3]),
+                    map_log2=(int(v[4]), int(v[5])))
 
     # ---- VO
     def vo_set_calib(self, cam_T_velo, rect0_T_cam, P_rect0):
@@ -627,6 +652,11 @@ class Handle:
     def map_force_rebuild(self):
         n = C.c_longlong(0)
         self._chk(self.L.vloam_debug_get(self.h, 2, 70, None, C.c_longlong(0), C.byref(n)))
+
+    def map_force_grow(self):
+        """Test hook: one growth step of both tables of a growable handle (map_grow=1) now, between two sweeps."""
+        n = C.c_longlong(0)
+        self._chk(self.L.vloam_debug_get(self.h, 2, 74, None, C.c_longlong(0), C.byref(n)))
 
     def map_dump(self, kind):
         """Live voxels of the corner (0) / surf (1) map as (count int32[n], xyzi float32[n, 4])."""

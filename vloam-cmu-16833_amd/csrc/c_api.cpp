@@ -7,6 +7,7 @@
 #include "../../include/vloam_hip/c_api.h"
 
 #include <hip/hip_runtime.h>
+#include <algorithm>
 #include <atomic>
 #include <limits.h>
 #include <stdarg.h>
@@ -516,11 +517,34 @@ vloam_status vloam_create_batch(const vloam_config* cfg, int device, int n_sessi
   return vloam_create_with_limits(cfg, nullptr, device, n_sessions, out);
 }
 
+void vloam_default_map_options(vloam_map_options* opt) {
+  opt->struct_size = (int)sizeof(vloam_map_options);
+  opt->grow = 0;
+  opt->max_capacity_log2 = 28;
+}
+
 vloam_status vloam_create_with_limits(const vloam_config* cfg, const vloam_limits* lim, int device, int n_sessions, vloam_handle** out) {
+  return vloam_create_with_options(cfg, lim, nullptr, device, n_sessions, out);
+}
+
+vloam_status vloam_create_with_options(const vloam_config* cfg, const vloam_limits* lim, const vloam_map_options* opt, int device, int n_sessions,
+                                       vloam_handle** out) {
   if (!cfg || !out) { set_err("null argument"); return VLOAM_ERR_INVALID; }
   vloam_limits lims;
   int sweep_log = 0;
   TRY(validate_create(cfg, lim, n_sessions, &lims, &sweep_log));
+  int grow_max_log2 = 0;   // > 0: a growable map with this ceiling
+  if (opt) {
+    const int lg0 = cfg->map_capacity_log2 < 10 ? 10 : (cfg->map_capacity_log2 > 28 ? 28 : cfg->map_capacity_log2);   // map_layout's clamp
+    if (opt->struct_size != (int)sizeof(vloam_map_options)) { set_err("vloam_map_options: struct_size must be %d", (int)sizeof(vloam_map_options)); return VLOAM_ERR_INVALID; }
+    if ((opt->grow != 0 && opt->grow != 1) || (opt->max_capacity_log2 != 0 && (opt->max_capacity_log2 < lg0 || opt->max_capacity_log2 > 28))) {
+      set_err("vloam_map_options: grow must be 0 or 1 and max_capacity_log2 0 (= 28) or map_capacity_log2 (%d) .. 28", lg0); return VLOAM_ERR_INVALID;
+    }
+    if (opt->grow == 1 && (n_sessions > 1 || !cfg->with_mapping)) {
+      set_err("vloam_map_options: grow = 1 needs a single-sequence handle (n_sessions == 1) with with_mapping == 1"); return VLOAM_ERR_INVALID;
+    }
+    if (opt->grow == 1) grow_max_log2 = opt->max_capacity_log2 ? opt->max_capacity_log2 : 28;
+  }
   // A handle drives two to six HIP streams that must run side by side (scan registration | odometry [| mapping | scan-feature VoxelGrid]
   // [| images] [| host-sweep copies]).  GPU_MAX_HW_QUEUES (read by the runtime when it initialises: it belongs to the HOST's environment, and a
   // library must not setenv() behind a multi-threaded host) caps each of the runtime's three priority pools of hardware queues; the handle
@@ -557,6 +581,17 @@ vloam_status vloam_create_with_limits(const vloam_config* cfg, const vloam_limit
   h->map.pub.skip_n = cfg->mapping_skip_frame;
   h->map.pub.cap = lims.max_published_map_points;
   h->map.pub.cloud_on = lims.publish_registered_cloud;
+  if (grow_max_log2 > 0) {   // before the layout: the tables then stay out of the arena (map_layout)
+    MapGrow* G = new MapGrow;
+    G->max_log2 = grow_max_log2;
+    // What one mapped sweep can add to a table at most.  Stack points: no more than the sweep's lessSharp cloud (kMaxLessSharp; a caller's
+    // own clouds, vloam_set_mapping_input, included) / the surf stack's capacity, and than the sweep has points.  Records: TWO per stack point
+    // — a point of a cube outside the valid block costs its voxel's record and a raw-point record of its own (k_map_finalize).  Block keys: one.
+    const long long pts[2] = {std::min<long long>(kMaxLessSharp, cfg->max_points), std::min<long long>(lims.max_surf_stack_points, cfg->max_points)};
+    for (int k = 0; k < 2; k++) { G->inc_rec[k] = 2 * pts[k]; G->inc_blk[k] = pts[k]; }
+    for (int k = 0; k < 2; k++) { h->map.tab[k].rec = nullptr; h->map.tab[k].pend = nullptr; h->map.tab[k].blk = nullptr; }   // (map_destroy frees them, whatever creation reached)
+    h->map.grow = G;
+  }
   h->sweep_log = sweep_log != 0;
   for (int s = 0; s < vloam_handle::kLogStages; s++) for (int k = 0; k < vloam_handle::kLogEvents; k++) h->ev_log_frame[s][k] = -1;
   h->device = device;
@@ -791,6 +826,11 @@ static vloam_status enqueue_map(vloam_handle* h, int frame) {
   if (h->sweep_log) sweep_log_map_begin_launch(h->s_map, h->se, h->log_scratch, h->map.frame, h->map.stack_info[cur], skip, &h->prof);
   vloam_status s = map_enqueue(&h->map, h->cfg, h->s_map, h->sr[cur], h->lo, sub_pose ? h->sub_row : h->traj + (size_t)frame * 14, skip, cur, &h->prof,
                                reads_set ? nullptr : h->ev_map[cur]);
+  if (s != VLOAM_OK && h->map.grow && h->map.grow->failed_log2) {   // a growth step's allocation: the old table stays in use, the sweep's mapping is enqueued by a later call
+    set_err("could not allocate a voxel table of 2^%d slots (hipMalloc); the corner / surf tables stay at 2^%d / 2^%d", h->map.grow->failed_log2, h->map.grow->lg[0], h->map.grow->lg[1]);
+    h->map.grow->failed_log2 = 0;
+    return VLOAM_ERR_HIP;
+  }
   if (s != VLOAM_OK) { set_err("map_enqueue failed: %s", hipGetErrorString(hipGetLastError())); return VLOAM_ERR_HIP; }
   if (h->sweep_log) {
     sweep_log_map_launch(h->s_map, h->se, h->log_rows, frame, h->log_scratch, h->map.state, h->map.frame, h->map.rec, skip, &h->prof, log_event(h, 2, frame));
@@ -1574,6 +1614,7 @@ vloam_status vloam_sync(vloam_handle* h) {
   if (!h) return VLOAM_ERR_INVALID;
   HIPCHK(hipSetDevice(h->device));
   TRY(sync_all(h));
+  map_grow_release(&h->map);   // nothing of the handle is in flight: tables a finished growth step left behind are freed here
   if (h->frame > 0) {
     // surface sticky device-side errors: scan-registration bits of ANY sweep since the last vloam_sync (k_sr_compact folds every
     // sweep's word into the handle's sticky word; reported once, then cleared), map / solver bits for good
@@ -1590,6 +1631,10 @@ vloam_status vloam_sync(vloam_handle* h) {
     h->fallback_solves = fb;
     if (merr & kErrEmpty) { set_err("no point survived NaN / minimum_range removal in at least one sweep since the last vloam_sync"); return VLOAM_ERR_EMPTY; }
     if (merr & kErrRingTooLong) { set_err("a ring held more than %d points (dropped) in at least one sweep since the last vloam_sync", h->cfg.max_ring_points); return VLOAM_ERR_CAPACITY; }
+    if ((merr & kErrMapFull) && h->map.grow) {
+      set_err("voxel hash full at the growable map's ceiling (max_capacity_log2=%d; corner table 2^%d, surf table 2^%d slots)", h->map.grow->max_log2, h->map.grow->lg[0], h->map.grow->lg[1]);
+      return VLOAM_ERR_CAPACITY;
+    }
     if (merr & kErrMapFull) { set_err("voxel hash full (map_capacity_log2=%d)", h->cfg.map_capacity_log2); return VLOAM_ERR_CAPACITY; }
     if (merr & kErrStackFull) {
       set_err("mapping factor table full: more than %d surf points after VoxelGrid; raise vloam_limits::max_surf_stack_points", h->map.surf_cap);
@@ -1742,6 +1787,10 @@ vloam_status vloam_debug_get(vloam_handle* h, int stage, int item, void* buf, lo
     if (n) *n = 0;
     return h->cfg.with_mapping ? map_force_rebuild(&h->map, h->s_map) : VLOAM_OK;
   }
+  if (stage == 2 && item == 74) {  // test hook: one growth step of both tables of a growable handle now (the production trigger is map_enqueue's bound)
+    if (n) *n = 0;
+    return map_force_grow(&h->map, h->s_map);
+  }
   if (stage == 2) return map_debug_get(&h->map, item, buf, cap, n);
   if (stage == 3) return vo_debug_get(&h->vo, item, buf, cap, n);
   if (stage == 4) return img_debug_get(&h->img, item, buf, cap, n);
@@ -1807,7 +1856,7 @@ int vloam_profile_kernel_count(void) { return kKCount; }
 const char* vloam_profile_kernel_name(int k) { return (k >= 0 && k < kKCount) ? kKernelNames[k] : ""; }
 
 // {cooperative solves that degraded to one workgroup (all sessions), 1 if the handle has switched to one-workgroup solves, voxel-table
-// rebuilds, 0 ...}
+// rebuilds, growable handles: growth steps, log2 of the corner table, log2 of the surf table, 0 ...}
 vloam_status vloam_get_health(vloam_handle* h, long long out8[8]) {
   if (!h || !out8) return VLOAM_ERR_INVALID;
   HIPCHK(hipSetDevice(h->device));
@@ -1817,6 +1866,7 @@ vloam_status vloam_get_health(vloam_handle* h, long long out8[8]) {
   long long fb = 0;
   if (h->frame > 0) TRY(map_error(&h->map, &merr, 0, &fb));
   out8[0] = fb; out8[1] = h->se.no_coop; out8[2] = h->map.rebuilds;
+  if (h->map.grow) { out8[3] = h->map.grow->steps; out8[4] = h->map.grow->lg[0]; out8[5] = h->map.grow->lg[1]; }
   return VLOAM_OK;
 }
 

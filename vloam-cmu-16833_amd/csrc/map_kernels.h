@@ -130,6 +130,25 @@ struct MapPub {
   }
 };
 
+// Growable map (vloam_map_options::grow, single-sequence handles): the two tables' rec / pend / blk live in allocations of their own and are
+// rehashed into larger ones between two sweeps (k_map_grow); a handle without the option has no MapGrow at all.  The host decides on a BOUND,
+// not on a count (map_enqueue): last reported keys + (mapped sweeps enqueued since that report) x (what one sweep can add).
+struct MapGrow {
+  int max_log2 = 28;              // ceiling per table: there k_map_finalize's kErrMapFull returns
+  int lg[2] = {0, 0};             // current log2 of the corner / surf table
+  long long steps = 0;            // growth steps enqueued so far, both tables
+  long long inc_rec[2] = {0, 0};  // records / block keys one mapped sweep can add to a table at most (set at creation, c_api.cpp)
+  long long inc_blk[2] = {0, 0};
+  unsigned long long* progress = nullptr;   // host-mapped [2 kinds][3]: sweep << 32 | live keys, | block keys, | keys incl. tombstones (k_map_progress)
+  long long step_at[2] = {-1, -1};  // mapped sweeps enqueued when the table was last rehashed: reports up to that sweep still count its tombstones
+  static constexpr int kEvRing = 4;
+  hipEvent_t ev_prog[kEvRing] = {};   // behind k_map_progress of mapped sweep n (slot n % kEvRing): the only thing the growth decision may wait for
+  int failed_log2 = 0;            // > 0: the last step could not allocate a table of that size (the caller words the error and clears it)
+  struct Retired { void* p[3]; hipEvent_t ev; };
+  std::vector<Retired> retired;   // buffers a grow chain still reads: released once their event has fired (map_grow_release)
+  std::vector<void*> leftover;    // what a failed allocation had got already: freed by map_grow_release (hipFree synchronises the device)
+};
+
 struct MapContext {
   MapState* state = nullptr;
   MapFrame* frame = nullptr;
@@ -159,6 +178,8 @@ struct MapContext {
   int* host_flags = nullptr;        // host-mapped: [kind] 1 = the table of that kind wants a rebuild (written by k_map_finalize)
   int rebuild_cooldown[kMaxBatch][2] = {};
   long long rebuilds = 0;
+  MapGrow* grow = nullptr; // growable map: null on every handle that did not ask for it.  Such a handle has ONE session, so for_session's
+                           // rebase of tab[] is by zero and tab[] always names the current buffers for every reader
   Sess se;                 // sessions of the handle (launch geometry .z and arena stride)
   int sel = 0;             // session the host-side getters read (vloam_select_session)
   // a copy whose device pointers address session b (host-side getters, per-session rebuilds)
@@ -204,6 +225,18 @@ vloam_status map_publish_enqueue(MapContext* m, hipStream_t st, const float4* cl
 // d_ptr (may be NULL): its device address.  xyzi4 (may be NULL): host buffer of cap points.  VLOAM_ERR_CAPACITY: the map overflowed (*n = true count).
 vloam_status map_published_get(MapContext* m, int which, float* xyzi4, long long cap, long long* n, int* frame, void** d_ptr);
 vloam_status map_force_rebuild(MapContext* m, hipStream_t st);  // every session
+// growable handles (m->grow != null).  map_force_grow: test hook, one doubling of both tables now (between two sweeps, on the mapping stream).
+// map_grow_release: frees retired buffers whose grow chain has finished (hipEventQuery); call with nothing of the handle in flight — hipFree
+// synchronises the device.
+vloam_status map_force_grow(MapContext* m, hipStream_t st);
+void map_grow_release(MapContext* m);
+// the rest of map_grow.hip's interface, for map_kernels.hip: the tables' first allocation / everything the option owns; a rehash of table
+// `kind` at its size (tombstone reclamation); the growth decision in front of a mapped sweep; k_map_progress behind its k_map_finalize
+vloam_status map_grow_init(MapContext* m, hipStream_t st);
+void map_grow_destroy(MapContext* m);
+vloam_status map_grow_rehash(MapContext* m, hipStream_t st, int kind);
+vloam_status map_grow_before_sweep(MapContext* m, hipStream_t st);
+void map_grow_progress_enqueue(MapContext* m, hipStream_t st);
 void map_destroy(MapContext* m);
 vloam_status map_counts(MapContext* m, long long c[16]);
 

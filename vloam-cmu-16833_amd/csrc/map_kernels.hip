@@ -19,6 +19,7 @@
 //                             raw voxels of cubes that became valid; after a grid roll drops the voxels whose cube left the
 //                             21x21x11 window (tombstones); table health -> host-mapped rebuild flag
 //   k_map_rebuild_* grid      (rare, between sweeps) gather live records, clear, reinsert: tombstone reclamation
+//   (map_grow.hip)            growable handles: k_map_grow rehashes a table into a fresh one between sweeps, k_map_progress reports its keys
 //   k_map_export    grid      /laser_cloud_map (LM:778-793) for vloam_get_map
 //   k_map_pub_*     grid      the same cloud ordered on the device, published behind a sweep's mapping (vloam_limits::map_pub_number)
 #include <hip/hip_runtime.h>
@@ -30,19 +31,13 @@
 #include <type_traits>
 #include "lm_solve.h"
 #include "map_kernels.h"
+#include "map_table.h"
 #include "subwave.h"
 #include "bitonic.h"
 
 namespace vloam {
 
-typedef unsigned long long u64;
-
 // ---------------------------------------------------------------------------------------------- helpers
-__device__ __forceinline__ u64 mix64(u64 x) {
-  x ^= x >> 33; x *= 0xff51afd7ed558ccdull; x ^= x >> 33; x *= 0xc4ceb9fe1a85ec53ull; x ^= x >> 33;
-  return x;
-}
-
 // LM:207-216 / LM:643-652: C int() truncation plus the "< 0" correction; absolute cube coordinate (no centre offset)
 __device__ __forceinline__ int cube_abs(double v) {
   int c = int((v + 25.0) / 50.0);
@@ -53,52 +48,6 @@ __device__ __forceinline__ int cube_lo(double v) { return (int)floor((v - 1e-3 +
 __device__ __forceinline__ int cube_hi(double v) { return (int)floor((v + 1e-3 + 25.0) * 0.02); }
 // first global voxel index that can belong to cube A (minus one cell of slack so the local index is never negative)
 __device__ __forceinline__ int cube_voxel_base(int A, float inv) { return (int)floor((50.0 * (double)A - 25.0) * (double)inv) - 1; }
-
-// Voxel key: | seq 8 (56-63) | - | cube i + 512 (10: 45-54) | cube j + 512 (10: 35-44) | cube k + 128 (8: 27-34) | voxel lx (18-26), ly (9-17),
-// lz (0-8) inside the cube, 9 bits each |.  Nine bits per axis take any leaf down to 50 m / 508 (the reference's launch files use 0.2 / 0.4 and
-// 0.4 / 0.8, laser_mapping.cpp:95-101 takes any value; vloam_create's bound of 0.132 m comes from the 32-bit tie rank of k_map_assoc, not
-// from the key).  seq = 0: the voxel's record (centroid, or the running sum of a raw voxel); seq = 1..255: one RAW point of a voxel whose
-// cube lies outside the valid 5 x 5 x 3 block (see k_map_finalize) — the reference keeps such points un-merged in their cube until the
-// cube is next re-filtered, and its kd-tree sees them one by one.  Cubes are absolute (no window offset): +-25.6 km horizontally,
-// +-6.4 km vertically around the start (k_map_insert reports anything beyond).
-constexpr int kCubeOffXY = 512, kCubeOffZ = 128;
-constexpr int kVoxBits = 9, kVoxMax = (1 << kVoxBits) - 1;
-__device__ __forceinline__ u64 pack_key(int Ai, int Aj, int Ak, int lx, int ly, int lz) {
-  return ((u64)(unsigned)(Ai + kCubeOffXY) << 45) | ((u64)(unsigned)(Aj + kCubeOffXY) << 35) | ((u64)(unsigned)(Ak + kCubeOffZ) << 27) |
-         ((u64)(unsigned)lx << (2 * kVoxBits)) | ((u64)(unsigned)ly << kVoxBits) | (u64)(unsigned)lz;
-}
-__device__ __forceinline__ void unpack_cube(u64 k, int* Ai, int* Aj, int* Ak) {
-  *Ai = (int)((k >> 45) & 0x3ff) - kCubeOffXY; *Aj = (int)((k >> 35) & 0x3ff) - kCubeOffXY; *Ak = (int)((k >> 27) & 0xff) - kCubeOffZ;
-}
-__device__ __forceinline__ int key_lx(u64 k) { return (int)((k >> (2 * kVoxBits)) & kVoxMax); }
-__device__ __forceinline__ int key_ly(u64 k) { return (int)((k >> kVoxBits) & kVoxMax); }
-__device__ __forceinline__ int key_lz(u64 k) { return (int)(k & kVoxMax); }
-__device__ __forceinline__ bool cube_in_key_range(int Ai, int Aj, int Ak) {
-  return Ai >= -kCubeOffXY && Ai < kCubeOffXY && Aj >= -kCubeOffXY && Aj < kCubeOffXY && Ak >= -kCubeOffZ && Ak < kCubeOffZ;
-}
-__device__ __forceinline__ int key_seq(u64 k) { return (int)(k >> 56); }
-__device__ __forceinline__ u64 key_with_seq(u64 k, int seq) { return (k & 0x00ffffffffffffffull) | ((u64)(unsigned)seq << 56); }
-// VoxelRec::count of a seq-0 record: points in the sum (low 16 bits) | kRecRaw when the voxel holds raw points (its cube was outside the
-// valid block when they arrived): then records seq = 1..n hold the points themselves
-constexpr int kRecRaw = 1 << 30;
-__device__ __forceinline__ int rec_n(int count) { return count & 0xffff; }
-__device__ __forceinline__ bool rec_raw(int count) { return (count & kRecRaw) != 0; }
-
-// A voxel record as two 16-byte loads of one 32-byte line
-struct RecVal { u64 key; float4 sum; int count, pend_cnt; };
-__device__ __forceinline__ RecVal rec_load(const VoxelRec* r) {
-  const uint4 a = reinterpret_cast<const uint4*>(r)[0], b = reinterpret_cast<const uint4*>(r)[1];
-  RecVal v;
-  v.key = (u64)a.x | ((u64)a.y << 32);
-  v.sum = make_float4(__uint_as_float(a.z), __uint_as_float(a.w), __uint_as_float(b.x), __uint_as_float(b.y));
-  v.count = (int)b.z; v.pend_cnt = (int)b.w;
-  return v;
-}
-// everything but the key (which only find-or-insert writes)
-__device__ __forceinline__ void rec_store_value(VoxelRec* r, float4 sum, int count, int pend_cnt) {
-  reinterpret_cast<float2*>(r)[1] = make_float2(sum.x, sum.y);
-  reinterpret_cast<uint4*>(r)[1] = make_uint4(__float_as_uint(sum.z), __float_as_uint(sum.w), (unsigned)count, (unsigned)pend_cnt);
-}
 
 // Eigen q * v (see lm_solve.hip / lo_kernels.hip) followed by + t, rounded to f32: pointAssociateToMap, LM:146-155
 __device__ __forceinline__ float4 associate_to_map(float4 pi, const double* q, const double* t) {
@@ -970,21 +919,6 @@ __device__ void map_update(MapState* ms, double* traj_row14) {
   if (traj_row14) for (int k = 0; k < 7; k++) traj_row14[7 + k] = ms->parameters[k];
 }
 
-// set the voxel's bit in its 4 x 4 x 4 block's occupancy mask (find-or-insert of the block entry)
-__device__ bool map_publish_block(const VoxelTable& T, int Ai, int Aj, int Ak, int lx, int ly, int lz) {
-  const u64 bkey = pack_key(Ai, Aj, Ak, lx >> 2, ly >> 2, lz >> 2) | (1ull << 63);
-  unsigned bs = (unsigned)mix64(bkey) & T.bslots_mask;
-  for (int bp = 0; bp < kMaxProbe; bp++, bs = (bs + 1) & T.bslots_mask) {
-    const u64 bold = atomicCAS(&T.blk[bs].x, 0ull, bkey);
-    if (bold == 0ull || bold == bkey) {
-      if (bold == 0ull) atomicAdd(&T.stats[2], 1);
-      atomicOr(&T.blk[bs].y, 1ull << (((lz & 3) << 4) | ((ly & 3) << 2) | (lx & 3)));
-      return true;
-    }
-  }
-  return false;
-}
-
 // One raw point of a voxel as a record of its own: key | seq, sum = the point, count = 1, pend_cnt = arrival stamp (sweep << 14 | stack
 // index — sweep << 17 | stack index on a handle of the large stack tier, k_map_finalize; 0 for a centroid that became raw point number one).  find-or-insert: a purged record of the same key is reused.
 __device__ bool map_put_raw_point(const VoxelTable& T, u64 voxel_key, int seq, float4 p, int stamp) {
@@ -1295,10 +1229,11 @@ vloam_status map_layout(MapContext* m, const vloam_config& cfg, Arena& A) {
   const size_t slots = (size_t)1 << lg;
   for (int k = 0; k < 2 && ok; k++) {
     VoxelTable& T = m->tab[k];
-    ok = ok && A.take(&T.rec, slots) && A.take(&T.pend, slots * kPendCap) && A.take(&T.stats, 4);
+    if (m->grow) { T.rec = nullptr; T.pend = nullptr; T.blk = nullptr; ok = ok && A.take(&T.stats, 4); }   // growable: rec / pend / blk are allocations of their own (map_grow_init)
+    else ok = ok && A.take(&T.rec, slots) && A.take(&T.pend, slots * kPendCap) && A.take(&T.stats, 4);
     T.mask = (unsigned)(slots - 1);
     const size_t bslots = slots / 2;
-    ok = ok && A.take(&T.blk, bslots);
+    if (!m->grow) ok = ok && A.take(&T.blk, bslots);
     T.bslots_mask = (unsigned)(bslots - 1);
     DsScratch& D = m->ds[k];
     if (k == 0) for (int c = 0; c < MapContext::kSets; c++) ok = ok && A.take(&m->stack_info[c], 1);
@@ -1325,8 +1260,9 @@ vloam_status map_layout(MapContext* m, const vloam_config& cfg, Arena& A) {
   }
   ok = ok && A.take(&m->rec, 2) && A.take(&m->nbr, 5 * (size_t)m->factor_cap());
   ok = ok && A.take(&m->cbox, 2 * (size_t)m->factor_cap()) && A.take(&m->ccand, (size_t)m->factor_cap() * kCandCache);
-  m->rebuild_cap = (int)(slots / 2);
-  ok = ok && A.take(&m->rebuild_tmp, (size_t)m->rebuild_cap) && A.take(&m->rebuild_n, 2);
+  m->rebuild_cap = m->grow ? 0 : (int)(slots / 2);
+  if (m->grow) { m->rebuild_tmp = nullptr; m->grow->lg[0] = m->grow->lg[1] = lg; ok = ok && A.take(&m->rebuild_n, 2); }   // a growable handle reclaims through k_map_grow: no staging list
+  else ok = ok && A.take(&m->rebuild_tmp, (size_t)m->rebuild_cap) && A.take(&m->rebuild_n, 2);
   ok = ok && A.take(&m->registered, (size_t)cfg.max_points) && A.take(&m->assoc_cyc, 16) && A.take(&m->ts_log, 2048);
   MapPub& P = m->pub;   // published clouds: nothing on a handle that did not ask for them
   if (P.pub_number > 0) {
@@ -1343,6 +1279,7 @@ vloam_status map_layout(MapContext* m, const vloam_config& cfg, Arena& A) {
 }
 
 vloam_status map_init(MapContext* m, hipStream_t st) {
+  if (m->grow && map_grow_init(m, st) != VLOAM_OK) return VLOAM_ERR_HIP;
   if (!m->host_flags) {
     if (hipHostMalloc((void**)&m->host_flags, sizeof(int) * 2 * kMaxBatch, hipHostMallocMapped) != hipSuccess) { m->host_flags = nullptr; return VLOAM_ERR_HIP; }
     for (int k = 0; k < 2 * kMaxBatch; k++) m->host_flags[k] = 0;
@@ -1375,6 +1312,7 @@ vloam_status map_stack_enqueue(MapContext* m, hipStream_t st, const SRBuffers& c
 }
 
 void map_destroy(MapContext* m) {
+  if (m->grow) map_grow_destroy(m);
   if (m->host_flags) { (void)hipHostFree(m->host_flags); m->host_flags = nullptr; }
   for (int k = 0; k < 2; k++)
     for (hipEvent_t* e : {&m->pub.ev_map[k], &m->pub.ev_cloud[k]}) if (*e) { (void)hipEventDestroy(*e); *e = nullptr; }
@@ -1382,6 +1320,7 @@ void map_destroy(MapContext* m) {
 
 // gather the live records, clear the table, reinsert (see k_map_rebuild_*); between two sweeps on the mapping stream; one session
 static vloam_status map_rebuild_enqueue(MapContext* m0, hipStream_t st, int session, int kind) {
+  if (m0->grow) return map_grow_rehash(m0, st, kind);   // a fresh table of the same size (rebuild_tmp would not fit a grown one)
   MapContext ms_ = m0->for_session(session);
   MapContext* m = &ms_;
   VoxelTable& T = m->tab[kind];
@@ -1413,6 +1352,7 @@ vloam_status map_enqueue(MapContext* m, const vloam_config& cfg, hipStream_t st,
   const unsigned Z = (unsigned)m->se.B;
   const size_t ss = m->se.ss;
   m->stack[0] = m->stack_sets[set][0]; m->stack[1] = m->stack_sets[set][1];
+  if (m->grow && !skip_frame && map_grow_before_sweep(m, st) != VLOAM_OK) return VLOAM_ERR_HIP;   // (no kernel of this sweep's mapping is enqueued yet)
   if (!skip_frame) {
     // the flag is written by k_map_finalize of an EARLIER sweep (plain read of host-mapped memory, no synchronisation): a rebuild
     // a few sweeps late is as good; the cool-down covers the sweeps already in flight that still report the old state
@@ -1473,6 +1413,7 @@ vloam_status map_enqueue(MapContext* m, const vloam_config& cfg, hipStream_t st,
   else { VL_INSERT(k_map_insert, ss); VL_FINALIZE(k_map_finalize, kStackCapSurf / 256, ss); }
 #undef VL_INSERT
 #undef VL_FINALIZE
+  if (m->grow) map_grow_progress_enqueue(m, st);
   return hipGetLastError() == hipSuccess ? VLOAM_OK : VLOAM_ERR_HIP;
 }
 
