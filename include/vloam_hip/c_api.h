@@ -471,6 +471,34 @@ const char* vloam_profile_kernel_name(int k);
  * table, 0 on any other handle; out8[6..7] 0. */
 vloam_status vloam_get_health(vloam_handle* h, long long out8[8]);
 
+/* Checkpoint and restore: a sequence saved into host memory and resumed in another handle (another process, another GPU, other capacities).
+ * vloam_checkpoint_size / _save first enqueue whatever the handle still owes (a deferred host sweep, trailing odometry and mapping) and
+ *   synchronise.  _size: the exact size of a checkpoint taken now.  _save: writes it into buf; *bytes is always the true size; cap smaller than
+ *   that: VLOAM_ERR_CAPACITY, nothing written.  Neither changes the handle: the next sweeps produce byte-identical results.
+ * vloam_checkpoint_load: on a FRESH single-sequence handle (vloam_frame_count == 0, stage 0; VLOAM_ERR_ORDER otherwise).  Afterwards the handle
+ *   is the saved sequence at the saved sweep: vloam_frame_count, vloam_get_trajectory(0 .. frames - 1), vloam_get_map, vloam_get_features(5 .. 8)
+ *   and vloam_get_odometry_pose return what the saving handle returned, and every later sweep produces what the uninterrupted handle would have.
+ *   The capacities may differ from the saver's (map_capacity_log2, fixed or growable, max_frames, max_points, max_ring_points,
+ *   max_surf_stack_points, the publication options, sweep_log); the algorithmic parameters must be equal: scan_line, minimum_range,
+ *   mapping_skip_frame, mapping_line_resolution, mapping_plane_resolution, detach_VO_LO, with_mapping (VLOAM_ERR_INVALID, vloam_last_error() names
+ *   the field) — and both handles or neither must have the large stack tier (max_surf_stack_points > 24576: the arrival stamps of raw points
+ *   have another width there; VLOAM_ERR_INVALID).  VLOAM_ERR_CAPACITY, naming what is too small: more frames than max_frames, clouds larger
+ *   than max_points / the stack capacity, or — on a fixed handle — more live records or block keys than 60 % of a table's slots; a growable
+ *   handle first takes a table size under which its own growth bound holds, up to its ceiling.  The buffer is validated in full (magic, format
+ *   version, struct sizes, checksum, every section offset, length and record count) before any device call: VLOAM_ERR_INVALID; nothing outside
+ *   [buf, buf + bytes) is read.  On every refusal the handle stays fresh and usable.
+ * A checkpoint is for the SAME BUILD of the library (it stores device structs verbatim).  Its size does not depend on map_capacity_log2: the map
+ * travels as its live records, 32 bytes each.
+ * Not supported, each refused with its own message: handles with n_sessions > 1 (VLOAM_ERR_INVALID); a sequence that used a VO, frame or image
+ * entry point — the VO's previous-frame state is not saved (VLOAM_ERR_ORDER from size / save); a handle in the middle of a stage-wise sweep
+ * (VLOAM_ERR_ORDER); a handle whose vloam_sync reports a sticky error (size / save return that error).
+ * What does not travel: the publication buffers (after load it is "before the first publication": *n = 0, *frame = -1; the map_pub_number
+ * schedule continues from the restored mapped-sweep count); the health counters (out8[0..3] start at 0); vloam_get_features(0 .. 4, 11) of the
+ * last sweep; sweep-log rows 0 .. frames - 1 travel when both handles keep a log, otherwise the rows of restored sweeps read frame == -1. */
+vloam_status vloam_checkpoint_size(vloam_handle* h, long long* bytes);
+vloam_status vloam_checkpoint_save(vloam_handle* h, void* buf, long long cap, long long* bytes);
+vloam_status vloam_checkpoint_load(vloam_handle* h, const void* buf, long long bytes);
+
 /* Timing of the last vloam_sync()ed scans: HIP-event milliseconds accumulated per stage
  * {scanRegistration, laserOdometry, laserMapping, vo} and number of scans covered. */
 vloam_status vloam_get_stage_ms(vloam_handle* h, double ms4[4], int* scans);

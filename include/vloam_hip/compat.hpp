@@ -112,8 +112,9 @@ inline Cloud from_cloud_ptr(const P& in) {
 // A Session / LidarOdometryMapping created with a vloam_config* takes the handle's capacities from it: max_points (points of a sweep),
 // map_capacity_log2, and max_ring_points (points of one scan line: 4096 by default; 4097 .. 16384 for sensors whose scan lines are longer —
 // an HDL-32E at 5 Hz, an HDL-64E with two lasers in one scan line, 4 096-column heads).
-// The growable voxel map (vloam_map_options::grow: tables that start at map_capacity_log2 and double between sweeps) is an option of the C call
-// vloam_create_with_options and has no constructor here yet; a Session always holds a fixed-size map.
+// The growable voxel map (vloam_map_options::grow: tables that start at map_capacity_log2 and double between sweeps) has a constructor of its
+// own below (vloam_create_with_options).  checkpoint() / restore(): the sequence as bytes and back into a fresh Session of
+// any capacities (vloam_checkpoint_save / vloam_checkpoint_load; sequences driven by sweeps only).
 class Session {  // one vloam_handle == one sequence on one GPU; shared by the three stage objects
  public:
   // max_surf_stack_points != 0: vloam_limits::max_surf_stack_points (the constructor LaserMapping(device, cfg, max_surf_stack_points) uses it)
@@ -141,8 +142,30 @@ class Session {  // one vloam_handle == one sequence on one GPU; shared by the t
     check(vloam_create_with_limits(&config, &e.limits, device, 1, &h_));
     limits = e.limits;
   }
+  // ... and the map options (vloam_map_options::grow / max_capacity_log2); lim may be null (the default limits)
+  Session(int device, const vloam_config* cfg, const vloam_limits* lim, const vloam_map_options& opt) {
+    if (cfg) config = *cfg; else vloam_default_config(&config);
+    check(vloam_create_with_options(&config, lim, &opt, device, 1, &h_));
+    if (lim) limits = *lim;
+    map_options = opt;
+  }
+  // The sequence as bytes, for the same build of the library; the session goes on as if it had not been asked.
+  std::vector<unsigned char> checkpoint() const {
+    long long n = 0;
+    check(vloam_checkpoint_size(h_, &n));
+    std::vector<unsigned char> buf(static_cast<size_t>(n));
+    check(vloam_checkpoint_save(h_, buf.data(), n, &n));
+    buf.resize(static_cast<size_t>(n));
+    return buf;
+  }
+  // ... and resumed in this session, which must be fresh; its capacities may differ from the saver's, its algorithmic parameters may not
+  void restore(const std::vector<unsigned char>& data) {
+    check(vloam_checkpoint_load(h_, data.data(), static_cast<long long>(data.size())));
+    check(vloam_frame_count(h_, &frames_done));
+  }
   vloam_config config;
   vloam_limits limits = vloam_limits();   // all zero: the defaults, nothing published
+  vloam_map_options map_options = vloam_map_options();   // all zero: a fixed-size map
   int frames_done = 0;   // sweeps whose laser odometry has run == LaserOdometry::frameCount
   ~Session() { vloam_destroy(h_); }
   Session(const Session&) = delete;

@@ -106,6 +106,11 @@ def main():
                          "for the publication only, never for the pipeline")
     ap.add_argument("--sweep-log", help="write the per-sweep diagnostics log (vloam_limits_ext::sweep_log) as JSON lines to this file: one line per sweep, read "
                                         "once after the run from the rows the stage streams wrote, with no per-frame synchronisation")
+    ap.add_argument("--save-checkpoint", metavar="PATH", help="write the sequence's checkpoint (vloam_checkpoint_save) to this file: after the last sweep, or with --at "
+                                                              "FRAME once FRAME sweeps are done (a run resumed from it starts at sweep FRAME); the run itself goes on unchanged")
+    ap.add_argument("--at", type=int, default=None, metavar="FRAME", help="with --save-checkpoint: sweeps done when the checkpoint is taken")
+    ap.add_argument("--resume", metavar="PATH", help="load this checkpoint (vloam_checkpoint_load) into the fresh handle and go on with the sweep behind the saved ones: "
+                                                     "the same input and the same algorithmic options as the saving run; outputs start at the restored sweep")
     ap.add_argument("--imu-T-velo", help="16 numbers, row major (default: KITTI 2011_09_26 extrinsics, approx.)")
     ap.add_argument("--imu-T-cam0", help="16 numbers, row major")
     a = ap.parse_args()
@@ -115,12 +120,12 @@ def main():
 
     if a.velodyne:
         files = sorted(glob.glob(os.path.join(a.velodyne, "*.bin")))
-        clouds = (kio.load_kitti_bin(f) for f in files)
+        load_sweep = lambda k: kio.load_kitti_bin(files[k])
         n = len(files)
     else:
         synth = importlib.import_module("vloam_amd.synth")
         seq = synth.SynthSequence(n_rings=64, n_azimuth=a.azimuth, n_sweeps=max(a.synthetic, 2) + 1, sensor=a.sensor)
-        clouds = (seq.sweep(k) for k in range(a.synthetic))
+        load_sweep = seq.sweep
         n = a.synthetic
     if n == 0:
         sys.exit("no sweeps")
@@ -140,6 +145,10 @@ def main():
         real_images = sorted(glob.glob(os.path.join(a.image_dir, "*.png")))
         if len(real_images) < n:
             sys.exit("%d sweeps but only %d images in %s" % (n, len(real_images), a.image_dir))
+    if a.vloam and (a.save_checkpoint or a.resume):
+        sys.exit("--save-checkpoint / --resume are for sequences driven by sweeps only: the VO's previous-frame state is not saved")
+    if a.at is not None and not (a.save_checkpoint and 0 < a.at <= n):
+        sys.exit("--at FRAME belongs to --save-checkpoint, 1 <= FRAME <= %d" % n)
     if a.images and not a.vloam:
         sys.exit("--images belongs to the coupled loop: add --vloam")
     img_cfg = {}
@@ -163,7 +172,19 @@ def main():
     mf = open(a.metrics, "w") if a.metrics else None
     ms_prev = np.zeros(4)
     last_pub, n_pub = -1, 0
-    for count, cloud in enumerate(clouds):
+    start = 0
+    if a.resume:
+        with open(a.resume, "rb") as f:
+            hd.restore(f.read())
+        start = hd.frame_count()
+        if not 0 < start < n:
+            sys.exit("the checkpoint holds %d sweeps, the input %d: nothing to resume" % (start, n))
+        row0 = hd.trajectory(0, 1)[0]   # the start frame of the written trajectories is the sequence's first sweep
+        tf.LO2Cam0StartFrame(row0[0:4], row0[4:7], 0)
+        tf.MO2Cam0StartFrame(row0[7:11], row0[11:14], 0)
+    save_at = (a.at if a.at is not None else n) if a.save_checkpoint else -1
+    for count in range(start, n):
+        cloud = load_sweep(count)
         if a.vloam:
             if a.images:
                 hd.process_frame_image(cloud, kio.load_png_gray(real_images[count]) if real_images else synth.render_image(seq, count))
@@ -222,6 +243,9 @@ def main():
                                    "laserMapping": float(ms[2] - ms_prev[2])}
                 ms_prev = ms.copy()
             mf.write(json.dumps(rec) + "\n")
+        if count + 1 == save_at:
+            with open(a.save_checkpoint, "wb") as f:
+                f.write(hd.checkpoint())
     if mf:
         mf.close()
     if a.sweep_log:
@@ -230,7 +254,7 @@ def main():
     kio.write_trajectory(os.path.join(a.out, "MO0.txt"), mo_rows)
     if vo_rows:
         kio.write_trajectory(os.path.join(a.out, "VO0.txt"), vo_rows)
-    print("wrote %d rows to %s/{LO0,MO0%s}.txt" % (n, a.out, ",VO0" if vo_rows else ""))
+    print("wrote %d rows to %s/{LO0,MO0%s}.txt" % (n - start, a.out, ",VO0" if vo_rows else ""))
     if a.map_pub_number:
         print("wrote %d published maps to %s/map_<frame>.npy" % (n_pub, a.out))
 

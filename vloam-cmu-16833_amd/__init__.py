@@ -296,6 +296,21 @@ class Handle:
     def sync(self):
         self._chk(self.L.vloam_sync(self.h))
 
+    def checkpoint(self):
+        """The sequence as bytes (vloam_checkpoint_save): drains and synchronises, leaves the handle as it was.  Single-sequence handles
+        driven by scans only; for the same build of the library."""
+        n = C.c_longlong(0)
+        self._chk(self.L.vloam_checkpoint_size(self.h, C.byref(n)))
+        buf = C.create_string_buffer(max(n.value, 1))
+        self._chk(self.L.vloam_checkpoint_save(self.h, buf, C.c_longlong(n.value), C.byref(n)))
+        return buf.raw[:n.value]
+
+    def restore(self, data):
+        """Resume the sequence of checkpoint() in this handle, which must be fresh (vloam_checkpoint_load); its capacities may differ from
+        the saver's, its algorithmic parameters may not."""
+        data = bytes(data)
+        self._chk(self.L.vloam_checkpoint_load(self.h, data, C.c_longlong(len(data))))
+
     def frame_count(self):
         n = C.c_int(0)
         self._chk(self.L.vloam_frame_count(self.h, C.byref(n)))

@@ -208,6 +208,31 @@ void map_grow_progress_enqueue(MapContext* m, hipStream_t st) {
   VLOAM_LAUNCH_EV((ProfHook*)nullptr, kKNone, st, ev, k_map_progress, dim3(1), dim3(64), 0, st, m->state, m->tab[0].stats, m->tab[1].stats, m->grow->progress);
 }
 
+// vloam_checkpoint_load on a growable handle, whose tables are still empty.  map_grow_restore_log2: the smallest size from the current one up to
+// the ceiling under which the growth bound holds for a table of `live` records and `blk` block keys with one sweep to come.
+// map_grow_restore: the tables step to lg[] (a step of an empty table) and the report words say what the tables hold once the checkpoint's records
+// are in, as of mapped sweep `mapped`, so that the next sweep's decision starts from them.
+int map_grow_restore_log2(const MapContext* m, int kind, long long live, long long blk) {
+  const MapGrow& G = *m->grow;
+  int lg = G.lg[kind];
+  while (lg < G.max_log2 && ((live + G.inc_rec[kind]) * 10 > ((long long)1 << lg) * 6 || (blk + G.inc_blk[kind]) * 10 > ((long long)1 << (lg - 1)) * 6)) lg++;
+  return lg;
+}
+vloam_status map_grow_restore(MapContext* m, hipStream_t st, const int lg[2], const long long live[2], const long long blk[2], long long mapped) {
+  MapGrow& G = *m->grow;
+  for (int k = 0; k < 2; k++) {
+    const int old_lg = G.lg[k];
+    if (lg[k] != old_lg) {
+      if (map_grow_step(m, st, k, lg[k]) != VLOAM_OK) return VLOAM_ERR_HIP;
+      G.steps += lg[k] - old_lg - 1;   // (health counts doublings)
+    }
+    const u64 sweep = (u64)(unsigned)mapped << 32;
+    G.progress[3 * k] = sweep | (u64)(unsigned)live[k]; G.progress[3 * k + 1] = sweep | (u64)(unsigned)blk[k]; G.progress[3 * k + 2] = sweep | (u64)(unsigned)live[k];
+    G.step_at[k] = mapped;
+  }
+  return VLOAM_OK;
+}
+
 vloam_status map_force_grow(MapContext* m, hipStream_t st) {
   if (!m->grow) return VLOAM_ERR_INVALID;
   for (int k = 0; k < 2; k++)

@@ -237,6 +237,14 @@ void map_grow_destroy(MapContext* m);
 vloam_status map_grow_rehash(MapContext* m, hipStream_t st, int kind);
 vloam_status map_grow_before_sweep(MapContext* m, hipStream_t st);
 void map_grow_progress_enqueue(MapContext* m, hipStream_t st);
+// checkpoint of a sequence (vloam_checkpoint_save / _load; single-session handles, nothing in flight).  map_ckpt.hip: the live records of both
+// tables counted (n_rec) and, with d_out, packed into a device buffer the caller frees — corner records, then surf records; the reverse into the
+// empty tables of a fresh handle from host memory.  ms (may be null): kernel times, {count + scan, pack} / unpack.  map_grow.hip: what a
+// growable handle does first (the table size its growth bound asks for; the step to it and the report words).
+vloam_status map_ckpt_pack(MapContext* m, hipStream_t st, long long n_rec[2], VoxelRec** d_out, float ms[2]);
+vloam_status map_ckpt_unpack(MapContext* m, hipStream_t st, const void* recs, const long long n_rec[2], float* ms);
+int map_grow_restore_log2(const MapContext* m, int kind, long long live, long long blk);
+vloam_status map_grow_restore(MapContext* m, hipStream_t st, const int lg[2], const long long live[2], const long long blk[2], long long mapped);
 void map_destroy(MapContext* m);
 vloam_status map_counts(MapContext* m, long long c[16]);
 

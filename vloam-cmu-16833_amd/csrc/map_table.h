@@ -74,4 +74,29 @@ __device__ bool map_publish_block(const VoxelTable& T, int Ai, int Aj, int Ak, i
   return false;
 }
 
+// One live record of a checkpoint's stream (k_map_ckpt_unpack) into table Tn, as k_map_rebuild_insert and k_map_grow do it: claim a slot (same
+// hash, same kMaxProbe, same CAS; keys are unique in the source), store the value, publish the voxel's occupancy block and re-append a raw voxel
+// to the deferred list.  pend[] of Tn is not written (map_grow.hip).  false: no slot within the probe bound (kErrMapFull raised).
+// k_map_grow keeps its own text of these lines: calling this function from it changes its register allocation (measured on the device assembly),
+// and the code objects of handles that are never saved or loaded are to stay what they are.
+__device__ __forceinline__ bool map_reinsert(const VoxelTable& Tn, const RecVal& v, MapFrame* fr, int kind, int* __restrict__ deferred, int deferred_cap) {
+  bool done = false;
+  const int seq = key_seq(v.key);
+  unsigned s = (unsigned)mix64(v.key) & Tn.mask;
+  for (int probe = 0; probe < kMaxProbe && !done; probe++, s = (s + 1) & Tn.mask) {
+    if (atomicCAS(&Tn.rec[s].key, 0ull, v.key) != 0ull) continue;
+    rec_store_value(&Tn.rec[s], v.sum, v.count, seq ? v.pend_cnt : 0);
+    int Ai, Aj, Ak;
+    unpack_cube(v.key, &Ai, &Aj, &Ak);
+    if (seq == 0 && !map_publish_block(Tn, Ai, Aj, Ak, key_lx(v.key), key_ly(v.key), key_lz(v.key))) atomicOr(&fr->error, kErrMapFull);
+    if (seq == 0 && rec_raw(v.count)) {
+      const int dpos = atomicAdd(&fr->n_deferred[kind], 1);
+      if (dpos < deferred_cap) deferred[dpos] = (int)s;
+    }
+    done = true;
+  }
+  if (!done) atomicOr(&fr->error, kErrMapFull);
+  return done;
+}
+
 }  // namespace vloam
