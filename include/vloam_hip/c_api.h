@@ -360,6 +360,64 @@ _Static_assert(sizeof(vloam_sweep_record) == 192, "vloam_sweep_record is 32 ints
 vloam_status vloam_get_sweep_log(vloam_handle* h, int first, int count, vloam_sweep_record* out);
 vloam_status vloam_sweep_log_device_ptr(vloam_handle* h, void** d_rows, long long* bytes);
 
+/* == Per-sweep pose information matrices and degeneracy flags (vloam_pose_info_enable): how well the scan constrained the pose.  The reference
+ * leaves odomAftMapped.pose.covariance and laserOdometry.pose.covariance at zero (laser_mapping.cpp:714-757, laser_odometry.cpp:538-554).  Here,
+ * for every sweep and session, one fixed-size record holds -- for the laser odometry and for the mapping -- the Gauss-Newton information matrix
+ * of the LAST outer round's problem at the pose that round returned: sum of J^T J after the loss corrector (Huber 0.1) over the residual blocks
+ * the solve consumed, in the 6-D tangent space (delta theta, delta t) of EigenQuaternionParameterization, unscaled; with its six eigenvalues, the
+ * cost 0.5 sum rho at that pose, the residual-block counts and degeneracy flags (smallest eigenvalue below a threshold: a tunnel, an open
+ * field, a ground-only view).
+ * Off on every handle that does not ask.  vloam_pose_info_enable allocates max_frames rows of 832 bytes per session (6.5 MB per session at the
+ * default 8192) OUTSIDE the session arenas -- arena layout and checkpoint sizes are those of a handle without it -- and from then on each LiDAR
+ * stage writes its half of the row with one launch on its own stream behind its last solve; the mapping (the odometry when with_mapping == 0)
+ * stamps `frame`.  No stream waits for another, nothing synchronises, no floating-point atomics: a row is bit-identical from run to run, and
+ * poses and map are those of a handle without the product.
+ * *_VALID is clear and that half of the record is zero -- odometry: on the first sweep (laser_odometry.cpp:196-204); mapping: on a sweep
+ * skipped by mapping_skip_frame, when "Map corner and surf num are not enough" (laser_mapping.cpp:448), and on a handle without mapping.
+ * Rows do NOT travel in a checkpoint: after vloam_checkpoint_load into an enabled handle the restored sweeps read frame == -1, later sweeps
+ * are written normally.
+ * Not provided: the matrix of the VO solve (angle-axis problem); eigenvectors; the inversion to a covariance (INTEGRATION.md §5 has the host
+ * lines: sigma^2 H^-1 with sigma^2 = 2 cost / (residual rows - 6), residual rows = 3 edge blocks + plane blocks). */
+typedef struct vloam_pose_info_options {
+  int struct_size;              /* sizeof(vloam_pose_info_options) as compiled */
+  int reserved;                 /* 0 */
+  double lo_min_eigenvalue;     /* VLOAM_POSE_INFO_LO_DEGENERATE when the smallest eigenvalue of the odometry matrix is below this; 0 = never */
+  double map_min_eigenvalue;    /* the same for the mapping matrix */
+} vloam_pose_info_options;
+void vloam_default_pose_info_options(vloam_pose_info_options* opt);   /* struct_size set, thresholds 0 */
+enum {   /* vloam_pose_info_record::flags */
+  VLOAM_POSE_INFO_LO_VALID = 1,         /* the odometry half holds this sweep's last odometry round */
+  VLOAM_POSE_INFO_MAP_VALID = 2,        /* the mapping half holds this sweep's last mapping round */
+  VLOAM_POSE_INFO_LO_DEGENERATE = 4,    /* LO_VALID and lo_eig[0] < lo_min_eigenvalue */
+  VLOAM_POSE_INFO_MAP_DEGENERATE = 8    /* MAP_VALID and map_eig[0] < map_min_eigenvalue */
+};
+typedef struct vloam_pose_info_record {
+  int frame;                    /* 0-based sweep index; -1 while the row has not been completed */
+  int flags;                    /* VLOAM_POSE_INFO_* */
+  int lo_factors[2];            /* edge, plane residual blocks of the last odometry round */
+  int map_factors[2];           /* corner, surf residual blocks of the last mapping round */
+  int reserved[2];
+  /* per stage: the point of evaluation (q xyzw, t) = what the round returned; 0.5 sum rho there; the matrix, row-major; its eigenvalues, ascending */
+  double lo_x[7], lo_cost, lo_H[36], lo_eig[6];
+  double map_x[7], map_cost, map_H[36], map_eig[6];
+} vloam_pose_info_record;
+#if defined(__cplusplus)
+static_assert(sizeof(vloam_pose_info_record) == 832, "vloam_pose_info_record is 8 ints and 100 doubles");
+#elif defined(__STDC_VERSION__) && __STDC_VERSION__ >= 201112L
+_Static_assert(sizeof(vloam_pose_info_record) == 832, "vloam_pose_info_record is 8 ints and 100 doubles");
+#endif
+/* vloam_pose_info_enable: on a FRESH handle only (no sweep taken, stage 0; VLOAM_ERR_ORDER otherwise, also when called twice); single-sequence and
+ *   batched handles, with_mapping 0 or 1.  opt may be NULL (the defaults).  The options are checked first, before the handle is looked at:
+ *   VLOAM_ERR_INVALID for a struct_size other than sizeof(vloam_pose_info_options), a reserved other than 0, a negative, NaN or infinite threshold.
+ * vloam_get_pose_info: the rows of sweeps first .. first + count - 1 of the session chosen with vloam_select_session -> HOST buffer.  Like
+ *   vloam_get_sweep_log it first enqueues what the handle still owes (no wait) and then waits for the work behind sweep first + count - 1 only.
+ *   VLOAM_ERR_ORDER: the handle never enabled the product.  VLOAM_ERR_INVALID: a range beyond vloam_frame_count.  A sweep whose odometry or
+ *   mapping the caller left out (stage-wise driving) keeps frame == -1.
+ * vloam_pose_info_device_ptr: device address + byte size of the selected session's rows; rows are only complete after vloam_sync(). */
+vloam_status vloam_pose_info_enable(vloam_handle* h, const vloam_pose_info_options* opt);
+vloam_status vloam_get_pose_info(vloam_handle* h, int first, int count, vloam_pose_info_record* out);
+vloam_status vloam_pose_info_device_ptr(vloam_handle* h, void** d_rows, long long* bytes);
+
 /* == VisualOdometry::processPointCloud + solveNlsAll (visual_odometry.cpp:157-186,254-450).
  * prev_uv/curr_uv: n_match integer pixel pairs (the reference truncates keypoints to int, :283-294).
  * angle_axis/t: in = initial guess (cam0_curr_LOT_cam0_prev) unless reset_VO_to_identity, out = estimate. */

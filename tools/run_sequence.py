@@ -106,6 +106,11 @@ def main():
                          "for the publication only, never for the pipeline")
     ap.add_argument("--sweep-log", help="write the per-sweep diagnostics log (vloam_limits_ext::sweep_log) as JSON lines to this file: one line per sweep, read "
                                         "once after the run from the rows the stage streams wrote, with no per-frame synchronisation")
+    ap.add_argument("--pose-info", action="store_true",
+                    help="enable the per-sweep pose information matrices (vloam_pose_info_enable, thresholds --lo-min-eig / --map-min-eig) and add "
+                         "lo_min_eig, map_min_eig, lo_degenerate, map_degenerate to the per-frame metrics (null where that stage did not solve)")
+    ap.add_argument("--lo-min-eig", type=float, default=0.0, help="with --pose-info: odometry degeneracy threshold on the smallest eigenvalue (0: never)")
+    ap.add_argument("--map-min-eig", type=float, default=0.0, help="with --pose-info: the same for the mapping")
     ap.add_argument("--save-checkpoint", metavar="PATH", help="write the sequence's checkpoint (vloam_checkpoint_save) to this file: after the last sweep, or with --at "
                                                               "FRAME once FRAME sweeps are done (a run resumed from it starts at sweep FRAME); the run itself goes on unchanged")
     ap.add_argument("--at", type=int, default=None, metavar="FRAME", help="with --save-checkpoint: sweeps done when the checkpoint is taken")
@@ -161,6 +166,8 @@ def main():
                                    **({"map_pub_number": a.map_pub_number} if a.map_pub_number else {}),
                                    **({"sweep_log": 1} if a.sweep_log else {}))
     hd = loam.hd
+    if a.pose_info:
+        hd.enable_pose_info(a.lo_min_eig, a.map_min_eig)
     if a.vloam:
         if real_images:   # PointCloudUtil::loadTransformations (point_cloud_util.cpp:5-116)
             hd.vo_set_calib(*kio.load_transformations(a.calib_cam_to_cam, a.calib_velo_to_cam))
@@ -226,6 +233,13 @@ def main():
                    "map_pose": [float(x) for x in list(q_mo) + list(t_mo)]}
             if a.map_pub_number:
                 rec["published_map"] = {"frame": last_pub, "points": pub_points, "overflow": pub_overflow}   # points: of a publication written by this frame, else null
+            if a.pose_info:
+                pi = hd.pose_info(count, 1)[0]
+                fl = int(pi["flags"])
+                rec["lo_min_eig"] = float(pi["lo_eig"][0]) if fl & vl.POSE_INFO_LO_VALID else None
+                rec["map_min_eig"] = float(pi["map_eig"][0]) if fl & vl.POSE_INFO_MAP_VALID else None
+                rec["lo_degenerate"] = bool(fl & vl.POSE_INFO_LO_DEGENERATE)
+                rec["map_degenerate"] = bool(fl & vl.POSE_INFO_MAP_DEGENERATE)
             if count > 0:
                 for name, st, item in (("lo_round0", 1, 2), ("lo_round1", 1, 18), ("map_round0", 2, 3), ("map_round1", 2, 19)):
                     r = hd.debug_lm_record(st, item)

@@ -4,6 +4,8 @@ after a short warm-up.  For A/B-ing a kernel change; bench.py remains the measur
   python tools/throughput_probe.py [--sessions 8] [--warm 60] [--steps 120] [--table]
   python tools/throughput_probe.py --no-batch --steps 200 --map-pub-number 20 --publish-registered-cloud --publish-ab 3
       the single sequence with the published clouds of the mapping stream (vloam_limits) off and on, alternately, in one process
+  python tools/throughput_probe.py --no-batch --steps 200 --pose-info-ab 3 [--table]
+      the single sequence with the pose information product (vloam_pose_info_enable) off and on, alternately
   python tools/throughput_probe.py --no-batch --steps 2000 --map-log2 20 --map-grow-ab 3
       the single sequence on a fixed handle and on a growable one (vloam_map_options::grow) of the same size, alternately
   python tools/throughput_probe.py --grow-step 18,21
@@ -36,6 +38,8 @@ ap.add_argument("--publish-registered-cloud", action="store_true", help="vloam_l
 ap.add_argument("--publish-ab", type=int, default=0, help="that many off / on pairs of single-sequence runs, products off first; replaces the normal run")
 ap.add_argument("--sweep-log-ab", type=int, default=0, help="that many off / on pairs of single-sequence runs (then of --sessions batches unless --no-batch), "
                                                          "vloam_limits_ext::sweep_log off first; replaces the normal run")
+ap.add_argument("--pose-info-ab", type=int, default=0, help="that many off / on pairs of single-sequence runs (then of --sessions batches unless --no-batch), the pose "
+                                                         "information product (vloam_pose_info_enable) off first; replaces the normal run")
 ap.add_argument("--map-grow-ab", type=int, default=0, help="that many fixed / growable pairs of single-sequence runs at --map-log2, fixed first; replaces the normal run")
 ap.add_argument("--grow-step", default="", help="comma-separated log2 sizes: a growable handle of that size, --warm sweeps, one forced growth step, timed on the host; replaces the normal run")
 ap.add_argument("--map-log2", type=int, default=22, help="map_capacity_log2 of the handles (voxel table slots)")
@@ -68,7 +72,11 @@ PUB = dict(map_pub_number=a.map_pub_number, publish_registered_cloud=int(a.publi
 
 
 def run(B, pub=PUB):
+    pub = dict(pub)
+    pose_info = pub.pop("pose_info", 0)
     h = vl.Handle(0, n_sessions=B, with_mapping=1, max_frames=a.warm + a.steps + 8, map_capacity_log2=a.map_log2, **pub)
+    if pose_info:
+        h.enable_pose_info()
     step = (lambda k: h.process_scan_device(ptr(k), npts)) if B == 1 else (lambda k: h.batch_process_scan_device([ptr(k)] * B, [npts] * B))
     for k in range(a.warm):
         step(k)
@@ -81,6 +89,7 @@ def run(B, pub=PUB):
     h.sync()
     dt = time.perf_counter() - t0
     note = "   sweep_log 1" if pub.get("sweep_log") else ""
+    note += "   pose_info 1" if pose_info else ""
     if pub.get("map_pub_number") or pub.get("publish_registered_cloud"):
         note += "   published: map every %d, registered cloud %d" % (pub["map_pub_number"], pub["publish_registered_cloud"])
     print("B = %2d: %8.0f scans/s   (%.1f us per step)%s" % (B, B * a.steps / dt, 1e6 * dt / a.steps, note), flush=True)
@@ -89,6 +98,9 @@ def run(B, pub=PUB):
         tot = sum(ms for ms, _ in rows.values())
         for name, (ms, cnt) in sorted(rows.items(), key=lambda kv: -kv[1][0])[:14]:
             print("   %-20s %6.1f us x %5d  (%4.1f %%)" % (name, 1e3 * ms / max(cnt, 1), cnt, 100 * ms / tot))
+        for name in ("k_lm_solve", "k_pose_info_lo", "k_pose_info_map"):
+            if pose_info and name in rows:
+                print("   %-20s %6.1f us x %5d  (new kernels next to one solve launch)" % (name, 1e3 * rows[name][0] / max(rows[name][1], 1), rows[name][1]))
     if pub.get("map_grow"):
         print("         growable: %s" % (h.health(),), flush=True)
     tr = h.trajectory(0, a.warm + a.steps)
@@ -155,6 +167,12 @@ if a.publish_ab:
     for _ in range(a.publish_ab):
         run(1, dict(map_pub_number=0, publish_registered_cloud=0))
         run(1)
+    sys.exit(0)
+if a.pose_info_ab:
+    for B in [1] + ([] if a.no_batch else [a.sessions]):
+        for _ in range(a.pose_info_ab):
+            run(B, dict(pose_info=0))
+            run(B, dict(pose_info=1))
     sys.exit(0)
 if a.sweep_log_ab:
     for B in [1] + ([] if a.no_batch else [a.sessions]):

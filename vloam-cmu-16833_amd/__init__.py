@@ -72,6 +72,19 @@ SWEEP_EMPTY, SWEEP_RING_TOO_LONG, SWEEP_MAP_FULL, SWEEP_MAP_RAW_CAPACITY, SWEEP_
 SWEEP_FLAG_FIRST, SWEEP_FLAG_MAP_SKIPPED, SWEEP_FLAG_MAP_NOT_OPTIMIZED, SWEEP_FLAG_LO_LESS_CORR_0, SWEEP_FLAG_LO_LESS_CORR_1, SWEEP_FLAG_SOLVE_DEGRADED = 1, 2, 4, 8, 16, 32
 
 
+class PoseInfoOptions(C.Structure):
+    """vloam_pose_info_options (c_api.h; vloam_pose_info_enable)."""
+    _fields_ = [("struct_size", C.c_int), ("reserved", C.c_int), ("lo_min_eigenvalue", C.c_double), ("map_min_eigenvalue", C.c_double)]
+
+
+# vloam_pose_info_record (c_api.h): 8 ints then 100 doubles, 832 bytes
+POSE_INFO_DTYPE = np.dtype([
+    ("frame", "<i4"), ("flags", "<i4"), ("lo_factors", "<i4", (2,)), ("map_factors", "<i4", (2,)), ("reserved", "<i4", (2,)),
+    ("lo_x", "<f8", (7,)), ("lo_cost", "<f8"), ("lo_H", "<f8", (36,)), ("lo_eig", "<f8", (6,)),
+    ("map_x", "<f8", (7,)), ("map_cost", "<f8"), ("map_H", "<f8", (36,)), ("map_eig", "<f8", (6,))])
+POSE_INFO_LO_VALID, POSE_INFO_MAP_VALID, POSE_INFO_LO_DEGENERATE, POSE_INFO_MAP_DEGENERATE = 1, 2, 4, 8
+
+
 class Calib(C.Structure):
     _fields_ = [("cam_T_velo", C.c_float * 16), ("rect0_T_cam", C.c_float * 16), ("P_rect0", C.c_float * 12)]
 
@@ -340,6 +353,28 @@ class Handle:
     def sweep_log_device_ptr(self):
         p, b = C.c_void_p(), C.c_longlong(0)
         self._chk(self.L.vloam_sweep_log_device_ptr(self.h, C.byref(p), C.byref(b)))
+        return p.value, b.value
+
+    def enable_pose_info(self, lo_min_eigenvalue=0.0, map_min_eigenvalue=0.0):
+        """vloam_pose_info_enable, on a fresh handle: from now on every sweep leaves a vloam_pose_info_record (information matrices of the last
+        odometry / mapping round at the returned pose, eigenvalues, degeneracy flags against the two thresholds; 0 = never degenerate)."""
+        opt = PoseInfoOptions()
+        self.L.vloam_default_pose_info_options(C.byref(opt))
+        opt.lo_min_eigenvalue, opt.map_min_eigenvalue = float(lo_min_eigenvalue), float(map_min_eigenvalue)
+        self._chk(self.L.vloam_pose_info_enable(self.h, C.byref(opt)))
+
+    def pose_info(self, first=0, count=None):
+        """vloam_get_pose_info: the rows of sweeps first .. first + count - 1 of the selected session as a structured array (POSE_INFO_DTYPE).
+        Waits for the work behind the last row asked for only, not for the pipeline."""
+        if count is None:
+            count = self.frame_count() - first
+        out = np.zeros(max(count, 1), dtype=POSE_INFO_DTYPE)
+        self._chk(self.L.vloam_get_pose_info(self.h, int(first), int(count), _fp(out)))
+        return out[:count]
+
+    def pose_info_device_ptr(self):
+        p, b = C.c_void_p(), C.c_longlong(0)
+        self._chk(self.L.vloam_pose_info_device_ptr(self.h, C.byref(p), C.byref(b)))
         return p.value, b.value
 
     def profile_kernel(self, name, max_launches=4096):

@@ -9,6 +9,7 @@
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <atomic>
+#include <float.h>
 #include <limits.h>
 #include <stdarg.h>
 #include <stddef.h>
@@ -24,6 +25,7 @@
 #include "lm_solve.h"
 #include "lo_kernels.h"
 #include "map_kernels.h"
+#include "pose_info.h"
 #include "sr_kernels.h"
 #include "stage_input_check.h"
 #include "stream_plan.h"
@@ -156,6 +158,12 @@ struct vloam_handle {
   static constexpr int kLogEvents = 2 * kSets, kLogStages = 3;   // scan registration, odometry, mapping
   hipEvent_t ev_log[kLogStages][kLogEvents] = {};
   int ev_log_frame[kLogStages][kLogEvents];
+  // per-sweep pose information matrices (vloam_pose_info_enable; null / unused on a handle without it).  Rows and scratch are allocations of their
+  // own, outside the arena.  ev_pi: the event behind each LiDAR stage's row write, a ring like ev_log
+  bool pose_info = false;
+  PoseInfo pi;
+  hipEvent_t ev_pi[2][kLogEvents] = {};
+  int ev_pi_frame[2][kLogEvents];
   hipEvent_t ev_vo[kSets] = {};     // depth map + matches of the frame in set c are in HBM
   bool vo_frame[kSets] = {};        // the sweep in set c came through vloam_process_frame (its odometry is preceded by the VO solve)
   bool have_extrinsics = false;
@@ -596,6 +604,7 @@ vloam_status vloam_create_with_options(const vloam_config* cfg, const vloam_limi
   }
   h->sweep_log = sweep_log != 0;
   for (int s = 0; s < vloam_handle::kLogStages; s++) for (int k = 0; k < vloam_handle::kLogEvents; k++) h->ev_log_frame[s][k] = -1;
+  for (int s = 0; s < 2; s++) for (int k = 0; k < vloam_handle::kLogEvents; k++) h->ev_pi_frame[s][k] = -1;
   h->device = device;
   *out = nullptr;
   vloam_status st = create_streams(h, plan, cfg);
@@ -632,6 +641,9 @@ vloam_status vloam_destroy(vloam_handle* h) {
   (void)hipSetDevice(h->device);
   for (hipStream_t st : {h->s_copy, h->stream, h->s_lo, h->s_map, h->s_ds, h->s_img}) if (st) (void)hipStreamSynchronize(st);
   if (h->arena) (void)hipFree(h->arena);
+  if (h->pi.rows) (void)hipFree(h->pi.rows);
+  if (h->pi.scratch) (void)hipFree(h->pi.scratch);
+  for (int s = 0; s < 2; s++) for (hipEvent_t e : h->ev_pi[s]) if (e) (void)hipEventDestroy(e);
   for (int k = 0; k < vloam_handle::kInRing; k++) if (h->ev_in_copied[k]) (void)hipEventDestroy(h->ev_in_copied[k]);
   for (int k = 0; k < 6; k++) if (h->ev[k]) (void)hipEventDestroy(h->ev[k]);
   for (int k = 0; k < vloam_handle::kSets; k++)
@@ -726,6 +738,13 @@ static inline hipEvent_t log_event(vloam_handle* h, int stage, int frame) {
   return h->ev_log[stage][slot];
 }
 
+// the same for the pose-information rows (stage 0 odometry, 1 mapping)
+static inline hipEvent_t pose_info_event(vloam_handle* h, int stage, int frame) {
+  const int slot = frame % vloam_handle::kLogEvents;
+  h->ev_pi_frame[stage][slot] = frame;
+  return h->ev_pi[stage][slot];
+}
+
 static vloam_status enqueue_sr(vloam_handle* h, const BatchIn& bi) {
   TRY(check_sweeps(h, (const void* const*)bi.in, bi.n, true));
   int n = 0;
@@ -808,6 +827,9 @@ static vloam_status enqueue_lo(vloam_handle* h, int frame) {
   if (h->sweep_log)
     sweep_log_lo_launch(h->s_lo, h->se, h->log_rows, frame, h->log_scratch, h->lo, h->lo_corr[0], h->lo_corr[1], h->lo_rec, &h->map.frame->fallback_solves,
                         !h->cfg.with_mapping, &h->prof, log_event(h, 1, frame));
+  // the information matrix of the second round's problem at the pose it returned: the table still holds that round's factors
+  if (h->pose_info)
+    pose_info_launch(h->s_lo, h->se, h->pi, 0, frame, h->lo_F, h->lo_rec + 1, frame > 0, nullptr, !h->cfg.with_mapping, &h->prof, pose_info_event(h, 0, frame));
   HIPCHK(hipGetLastError());
   if (h->cfg.timing) HIPCHK(hipEventRecord(h->ev[3], h->s_lo));
   return VLOAM_OK;
@@ -836,6 +858,11 @@ static vloam_status enqueue_map(vloam_handle* h, int frame) {
   if (s != VLOAM_OK) { set_err("map_enqueue failed: %s", hipGetErrorString(hipGetLastError())); return VLOAM_ERR_HIP; }
   if (h->sweep_log) {
     sweep_log_map_launch(h->s_map, h->se, h->log_rows, frame, h->log_scratch, h->map.state, h->map.frame, h->map.rec, skip, &h->prof, log_event(h, 2, frame));
+    HIPCHK(hipGetLastError());
+  }
+  // behind k_map_finalize: the second round's table is not rewritten before the next sweep's fit, and MapState::do_optimize is still this sweep's
+  if (h->pose_info) {
+    pose_info_launch(h->s_map, h->se, h->pi, 1, frame, h->map.F[1], h->map.rec + 1, !skip, &h->map.state->do_optimize, true, &h->prof, pose_info_event(h, 1, frame));
     HIPCHK(hipGetLastError());
   }
   if (sub_pose) HIPCHK(hipMemcpyAsync(h->traj + (size_t)frame * 14 + 7, h->sub_row + 7, 7 * sizeof(double), hipMemcpyDeviceToDevice, h->s_map));   // the map half of the log
@@ -1707,6 +1734,75 @@ vloam_status vloam_sweep_log_device_ptr(vloam_handle* h, void** d_rows, long lon
   TRY(require_sweep_log(h));
   *d_rows = SEL(h, h->log_rows);
   *bytes = (long long)h->cfg.max_frames * (long long)sizeof(vloam_sweep_record);
+  return VLOAM_OK;
+}
+
+// ------------------------------------------------------------------ per-sweep pose information matrices (vloam_pose_info_enable)
+void vloam_default_pose_info_options(vloam_pose_info_options* opt) {
+  if (!opt) return;
+  opt->struct_size = (int)sizeof(vloam_pose_info_options);
+  opt->reserved = 0;
+  opt->lo_min_eigenvalue = 0.0;
+  opt->map_min_eigenvalue = 0.0;
+}
+vloam_status vloam_pose_info_enable(vloam_handle* h, const vloam_pose_info_options* opt) {
+  vloam_pose_info_options o;
+  vloam_default_pose_info_options(&o);
+  if (opt) {   // the options first: before any device call, before anything of the handle is looked at
+    if (opt->struct_size != (int)sizeof(vloam_pose_info_options)) { set_err("vloam_pose_info_options: struct_size must be %d", (int)sizeof(vloam_pose_info_options)); return VLOAM_ERR_INVALID; }
+    if (opt->reserved != 0) { set_err("vloam_pose_info_options: reserved must be 0"); return VLOAM_ERR_INVALID; }
+    for (const double v : {opt->lo_min_eigenvalue, opt->map_min_eigenvalue})
+      if (!(v >= 0.0) || !(v <= DBL_MAX)) { set_err("vloam_pose_info_options: lo_min_eigenvalue / map_min_eigenvalue must be finite and >= 0 (0 = never degenerate)"); return VLOAM_ERR_INVALID; }
+    o = *opt;
+  }
+  if (!h) { set_err("vloam_pose_info_enable: null handle"); return VLOAM_ERR_INVALID; }
+  if (h->pose_info || h->frame != 0 || h->pend.valid || h->stage != 0) {
+    set_err("vloam_pose_info_enable: the handle is not fresh (%d sweeps taken, stage %d%s): the product is enabled right after creation, once", h->frame + (h->pend.valid ? 1 : 0),
+            h->stage, h->pose_info ? ", already enabled" : "");
+    return VLOAM_ERR_ORDER;
+  }
+  HIPCHK(hipSetDevice(h->device));
+  const size_t row_bytes = sizeof(vloam_pose_info_record) * (size_t)h->cfg.max_frames * (size_t)h->se.B;
+  PoseInfo P;
+  P.max_frames = h->cfg.max_frames;
+  P.min_eig[0] = o.lo_min_eigenvalue; P.min_eig[1] = o.map_min_eigenvalue;
+  if (hipMalloc((void**)&P.rows, row_bytes) != hipSuccess) { set_err("vloam_pose_info_enable: hipMalloc of %zu MB failed", row_bytes >> 20); return VLOAM_ERR_HIP; }
+  if (hipMalloc((void**)&P.scratch, sizeof(PoseInfoScratch) * 2 * (size_t)h->se.B) != hipSuccess) {
+    (void)hipFree(P.rows); set_err("vloam_pose_info_enable: hipMalloc failed"); return VLOAM_ERR_HIP;
+  }
+  h->pi = P;   // (vloam_destroy frees them, whatever the rest reaches)
+  for (int s = 0; s < 2; s++)
+    for (int k = 0; k < vloam_handle::kLogEvents; k++) HIPCHK(hipEventCreateWithFlags(&h->ev_pi[s][k], hipEventDisableTiming | hipEventBlockingSync));
+  HIPCHK(pose_info_init(h->stream, h->pi, h->se.B));
+  HIPCHK(hipStreamSynchronize(h->stream));   // the stage streams do not wait for this one
+  h->pose_info = true;
+  return VLOAM_OK;
+}
+static vloam_status require_pose_info(const vloam_handle* h) {
+  if (!h->pose_info) { set_err("the handle never enabled the pose information product (vloam_pose_info_enable)"); return VLOAM_ERR_ORDER; }
+  return VLOAM_OK;
+}
+vloam_status vloam_get_pose_info(vloam_handle* h, int first, int count, vloam_pose_info_record* out) {
+  if (!h) return VLOAM_ERR_INVALID;
+  TRY(require_pose_info(h));
+  if (!out || first < 0 || count < 0 || first + count > h->frame + (h->pend.valid ? 1 : 0)) {   // (a host sweep in flight is enqueued by the drain below)
+    set_err("vloam_get_pose_info: sweeps %d .. %d are not all handed over (vloam_frame_count)", first, first + count - 1); return VLOAM_ERR_INVALID;
+  }
+  HIPCHK(hipSetDevice(h->device));
+  TRY(drain_deferred(h, 0, 0));   // enqueue only
+  if (count == 0) return VLOAM_OK;
+  // rows complete in sweep order on both streams: wait for the two writers of the LAST row asked for, nothing younger
+  const int last = first + count - 1, slot = last % vloam_handle::kLogEvents;
+  for (int s = 0; s < 2; s++)
+    if (h->ev_pi_frame[s][slot] == last) HIPCHK(hipEventSynchronize(h->ev_pi[s][slot]));
+  HIPCHK(hipMemcpy(out, h->pi.rows + (size_t)h->sel * (size_t)h->cfg.max_frames + first, sizeof(vloam_pose_info_record) * (size_t)count, hipMemcpyDeviceToHost));
+  return VLOAM_OK;
+}
+vloam_status vloam_pose_info_device_ptr(vloam_handle* h, void** d_rows, long long* bytes) {
+  if (!h || !d_rows || !bytes) return VLOAM_ERR_INVALID;
+  TRY(require_pose_info(h));
+  *d_rows = h->pi.rows + (size_t)h->sel * (size_t)h->cfg.max_frames;
+  *bytes = (long long)h->cfg.max_frames * (long long)sizeof(vloam_pose_info_record);
   return VLOAM_OK;
 }
 

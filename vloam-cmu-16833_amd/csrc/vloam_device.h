@@ -64,7 +64,7 @@ enum KernelId : int {
   kKLoGridCount, kKLoGridScan, kKLoGridScatter, kKMapDsReduce, kKMapFit, kKLmCompact, kKVoFold, kKSrRingBig,
   kKImgSobel, kKImgEig, kKImgLocalMax, kKImgNeighbours, kKImgSelect, kKImgPyrDown, kKImgScharr, kKImgLk, kKLoAssocFast, kKSrRingLong,
   kKMapPubCount, kKMapPubScan, kKMapPubScatter, kKMapPubSort, kKMapPubRank, kKMapRegister,
-  kKSweepLogSr, kKSweepLogLo, kKSweepLogMapBegin, kKSweepLogMap, kKCount
+  kKSweepLogSr, kKSweepLogLo, kKSweepLogMapBegin, kKSweepLogMap, kKPoseInfoLo, kKPoseInfoMap, kKCount
 };
 static const char* const kKernelNames[kKCount] = {"", "k_sr_first_last", "k_sr_label", "k_sr_scan", "k_sr_scatter", "k_sr_ring",
   "k_sr_compact", "k_lo_assoc", "k_lm_solve", "k_lo_finish", "k_map_prepare", "k_map_ds_bin", "k_map_assoc", "k_map_insert",
@@ -72,7 +72,7 @@ static const char* const kKernelNames[kKCount] = {"", "k_sr_first_last", "k_sr_l
   "k_map_ds_reduce", "k_map_fit", "k_lm_compact", "k_vo_fold", "k_sr_ring_big_tier",
   "k_img_sobel", "k_img_eig", "k_img_localmax", "k_img_neighbours", "k_img_select", "k_img_pyrdown", "k_img_scharr", "k_img_lk", "k_lo_assoc_fast",
   "k_sr_ring_long", "k_map_pub_count", "k_map_pub_scan", "k_map_pub_scatter", "k_map_pub_sort", "k_map_pub_rank", "k_map_register",
-  "k_sweep_log_sr", "k_sweep_log_lo", "k_sweep_log_map_begin", "k_sweep_log_map"};
+  "k_sweep_log_sr", "k_sweep_log_lo", "k_sweep_log_map_begin", "k_sweep_log_map", "k_pose_info_lo", "k_pose_info_map"};
 constexpr int kKAll = -1;  // ProfHook::id: bracket every launch, whichever kernel
 
 // Records a HIP-event pair around every launch of one selected kernel (or of all kernels), on the stream it is launched on.
