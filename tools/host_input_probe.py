@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """vloam_process_scan from host memory on its own: the same 64 x 2048 sweeps as device pointers, from pinned memory and from pageable memory
 (a buffer of its own per sweep), mapping on, after a short lead-in.  Prints scans/s of each and the ratios (bench.py's host_input leg is the
-measurement of record; this is the quick A/B behind it: VLOAM_STAGE_INLINE of c_api.cpp).  --external-ring N adds the experiment the library's
+measurement of record; this is the quick A/B behind it: VLOAM_STAGE_INLINE of capi_sweep.cpp).  --external-ring N adds the experiment the library's
 deferred ring came from: the CALLER copies pinned sweeps on a stream of its own into N device buffers and hands device pointers over, one
 sweep behind (extring), not deferred (extring_nodefer), and with the copy stream created AFTER the handle's streams (extring_late: slow —
 which is why vloam_create creates and uses its copy stream first).
