@@ -557,6 +557,39 @@ vloam_status vloam_checkpoint_size(vloam_handle* h, long long* bytes);
 vloam_status vloam_checkpoint_save(vloam_handle* h, void* buf, long long cap, long long* bytes);
 vloam_status vloam_checkpoint_load(vloam_handle* h, const void* buf, long long bytes);
 
+/* Map queries: the k nearest map points of caller-supplied points, answered on the device from the map's own occupancy-block index.  Opt-in by
+ * calling: a handle that never queries allocates and launches nothing of this, and no kernel of a sweep changes.
+ *   Query points are packed float4 (w ignored) in the MAP frame — the frame of vloam_get_map and of the registered cloud, so
+ *   vloam_published_device_ptr(h, 1, ...) can be fed straight in.  The searched set is exactly what vloam_get_map returns at that moment for the
+ *   session chosen with vloam_select_session (kind 0: its corner clouds, 1: its surf clouds, 2: both).  Per query q: count[q] in 0 .. k;
+ *   neighbour j < count[q] at xyzi4[q*k + j] with squared distance d2[q*k + j], ascending; entries j >= count[q] are zero.
+ *   d2 = (dx*dx + dy*dy) + dz*dz in f32, every product and sum rounded on its own (no FMA); a neighbour qualifies when d2 <= max_radius*max_radius
+ *   (f32 product); equal d2 resolve to the point that comes first in vloam_get_map.  A query with a non-finite coordinate, or far outside the
+ *   map, returns count 0 and no error.
+ * Ordering: both calls first enqueue what the handle still owes (a deferred host sweep, trailing odometry and mapping); the query runs on the
+ *   mapping stream behind the last mapping (and any growth step of a growable handle).  vloam_map_query works with temporary allocations,
+ *   waits for the mapping stream only, and then returns a sticky map error of the handle (the one vloam_sync reports) instead of VLOAM_OK.
+ *   vloam_map_query_device enqueues and returns: all five addresses are device memory, results are complete after vloam_sync, and the buffers must
+ *   stay valid until then.
+ * Refusals, options first and before the handle is looked at (VLOAM_ERR_INVALID, each with its own vloam_last_error()): struct_size, kind
+ *   outside 0 .. 2, k outside 1 .. 8, reserved != 0, a radius that is <= 0 or not finite, a null buffer with n > 0, n < 0.  Then against the
+ *   handle: a radius above 16 leaves of the finest kind queried (mapping_line_resolution for 0 and 2, mapping_plane_resolution for 1:
+ *   VLOAM_ERR_INVALID naming the bound in metres); with_mapping == 0 (VLOAM_ERR_ORDER).  n == 0: VLOAM_OK, nothing launched.
+ * Not offered: queries in the sensor frame; points outside the 21 x 21 x 11 cube window (they are not part of the map). */
+typedef struct vloam_map_query_options {
+  int struct_size;     /* sizeof as compiled */
+  int kind;            /* 0 corner map, 1 surf map, 2 both (nearest over the union) */
+  int k;               /* 1 .. 8 neighbours per query */
+  int reserved;        /* 0 */
+  float max_radius;    /* metres, > 0, finite; <= 16 leaves of the finest kind queried */
+} vloam_map_query_options;
+void vloam_default_map_query_options(vloam_map_query_options* o);   /* kind 2, k 5, radius 1.0 */
+vloam_status vloam_map_query(vloam_handle* h, const vloam_map_query_options* o, const float* xyz_pad4, int n, float* xyzi4, float* d2, int* count);
+vloam_status vloam_map_query_device(vloam_handle* h, const vloam_map_query_options* o, const void* d_xyz_pad4, int n, void* d_xyzi4, void* d_d2,
+                                    void* d_count);
+/* The corner (kind 0) or surf (kind 1) half of vloam_get_map, same order within the half; same calling convention. */
+vloam_status vloam_get_map_kind(vloam_handle* h, int kind, float* xyzi4, long long cap, long long* n);
+
 /* Timing of the last vloam_sync()ed scans: HIP-event milliseconds accumulated per stage
  * {scanRegistration, laserOdometry, laserMapping, vo} and number of scans covered. */
 vloam_status vloam_get_stage_ms(vloam_handle* h, double ms4[4], int* scans);

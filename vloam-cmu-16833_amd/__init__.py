@@ -60,6 +60,11 @@ class MapOptions(C.Structure):
     _fields_ = [("struct_size", C.c_int), ("grow", C.c_int), ("max_capacity_log2", C.c_int)]
 
 
+class MapQueryOptions(C.Structure):
+    """vloam_map_query_options (c_api.h; vloam_map_query / vloam_map_query_device)."""
+    _fields_ = [("struct_size", C.c_int), ("kind", C.c_int), ("k", C.c_int), ("reserved", C.c_int), ("max_radius", C.c_float)]
+
+
 # vloam_sweep_record (c_api.h): 32 ints then 8 doubles, 192 bytes
 SWEEP_RECORD_DTYPE = np.dtype([
     ("frame", "<i4"), ("error_bits", "<i4"), ("flags", "<i4"), ("n_in", "<i4"), ("n_cloud", "<i4"), ("n_sharp", "<i4"), ("n_less_sharp", "<i4"),
@@ -669,6 +674,41 @@ class Handle:
         buf = np.zeros((max(n.value, 1), 4), dtype=np.float32)
         self._chk(self.L.vloam_get_map(self.h, _fp(buf), C.c_longlong(n.value), C.byref(n)))
         return buf[:n.value]
+
+    def get_map_kind(self, kind):
+        """The corner (kind 0) or surf (kind 1) half of get_map(), same order within the half (vloam_get_map_kind)."""
+        n = C.c_longlong(0)
+        self._chk(self.L.vloam_get_map_kind(self.h, int(kind), None, C.c_longlong(0), C.byref(n)))
+        buf = np.zeros((max(n.value, 1), 4), dtype=np.float32)
+        self._chk(self.L.vloam_get_map_kind(self.h, int(kind), _fp(buf), C.c_longlong(n.value), C.byref(n)))
+        return buf[:n.value]
+
+    def _query_options(self, k, max_radius, kind):
+        opt = MapQueryOptions()
+        self.L.vloam_default_map_query_options(C.byref(opt))
+        opt.kind, opt.k, opt.max_radius = int(kind), int(k), float(max_radius)
+        return opt
+
+    def map_query(self, points, k=5, max_radius=1.0, kind=2):
+        """vloam_map_query: the k nearest map points within max_radius of every row of points (float32 [n, 3] or [n, 4], map frame) in the
+        corner map (kind 0), the surf map (1) or both (2), of the selected session: (xyzi [n, k, 4], d2 [n, k] ascending, count [n]); entries
+        beyond count are zero.  Runs behind everything handed over so far and waits for the mapping stream only."""
+        p = np.asarray(points, dtype=np.float32)
+        q = np.zeros((p.shape[0], 4), dtype=np.float32)
+        q[:, :3] = p[:, :3]
+        n, k = q.shape[0], int(k)
+        xyzi = np.zeros((max(n, 1), max(k, 1), 4), dtype=np.float32)
+        d2 = np.zeros((max(n, 1), max(k, 1)), dtype=np.float32)
+        cnt = np.zeros(max(n, 1), dtype=np.int32)
+        opt = self._query_options(k, max_radius, kind)
+        self._chk(self.L.vloam_map_query(self.h, C.byref(opt), _fp(q), n, _fp(xyzi), _fp(d2), _fp(cnt)))
+        return xyzi[:n], d2[:n], cnt[:n]
+
+    def map_query_device(self, d_points, n, d_xyzi, d_d2, d_count, k=5, max_radius=1.0, kind=2):
+        """vloam_map_query_device: the same with device addresses (n packed float4 in; [n][k] float4, [n][k] float32 and [n] int32 out).  Enqueues
+        and returns: the results are complete after sync(), and the buffers must stay valid until then."""
+        opt = self._query_options(k, max_radius, kind)
+        self._chk(self.L.vloam_map_query_device(self.h, C.byref(opt), C.c_void_p(d_points), int(n), C.c_void_p(d_xyzi), C.c_void_p(d_d2), C.c_void_p(d_count)))
 
     def published_map(self):
         """The latest /laser_cloud_map the mapping stream published (vloam_limits::map_pub_number): (float32 [n, 4], 0-based sweep index),

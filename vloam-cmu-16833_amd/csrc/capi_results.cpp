@@ -2,6 +2,23 @@
 // health, stage times, the parity hooks (vloam_debug_get) and the per-kernel timer.
 #include "handle.h"
 
+// the handle's sticky map / solver error bits as the status and text vloam_sync reports them with (also vloam_map_query)
+vloam_status vloam::sticky_map_status(const vloam_handle* h, int merr) {
+  if ((merr & kErrMapFull) && h->map.grow) {
+    set_err("voxel hash full at the growable map's ceiling (max_capacity_log2=%d; corner table 2^%d, surf table 2^%d slots)", h->map.grow->max_log2, h->map.grow->lg[0], h->map.grow->lg[1]);
+    return VLOAM_ERR_CAPACITY;
+  }
+  if (merr & kErrMapFull) { set_err("voxel hash full (map_capacity_log2=%d)", h->cfg.map_capacity_log2); return VLOAM_ERR_CAPACITY; }
+  if (merr & kErrStackFull) {
+    set_err("mapping factor table full: more than %d surf points after VoxelGrid; raise vloam_limits::max_surf_stack_points", h->map.surf_cap);
+    return VLOAM_ERR_CAPACITY;
+  }
+  if (merr & kErrMapDeferred) { set_err("raw-point capacity of the map exceeded (more than 255 un-merged points in a voxel of a cube outside the valid block, or more than 64 raw voxels around one query)"); return VLOAM_ERR_CAPACITY; }
+  if (merr & kErrSolverSync) { set_err("a workgroup of the scan-feature VoxelGrid gave up waiting for the bins in front of it"); return VLOAM_ERR_HIP; }
+  if (merr & kErrVoDegenerate) { set_err("a VO solve returned a zero rotation angle: poses are NaN from that frame on, as in the reference (visual_odometry.cpp:427-430)"); return VLOAM_ERR_INVALID; }
+  return VLOAM_OK;
+}
+
 extern "C" {
 
 vloam_status vloam_get_features(vloam_handle* h, int which, float* xyzi4, int cap, int* n) {
@@ -109,18 +126,7 @@ vloam_status vloam_sync(vloam_handle* h) {
     h->fallback_solves = fb;
     if (merr & kErrEmpty) { set_err("no point survived NaN / minimum_range removal in at least one sweep since the last vloam_sync"); return VLOAM_ERR_EMPTY; }
     if (merr & kErrRingTooLong) { set_err("a ring held more than %d points (dropped) in at least one sweep since the last vloam_sync", h->cfg.max_ring_points); return VLOAM_ERR_CAPACITY; }
-    if ((merr & kErrMapFull) && h->map.grow) {
-      set_err("voxel hash full at the growable map's ceiling (max_capacity_log2=%d; corner table 2^%d, surf table 2^%d slots)", h->map.grow->max_log2, h->map.grow->lg[0], h->map.grow->lg[1]);
-      return VLOAM_ERR_CAPACITY;
-    }
-    if (merr & kErrMapFull) { set_err("voxel hash full (map_capacity_log2=%d)", h->cfg.map_capacity_log2); return VLOAM_ERR_CAPACITY; }
-    if (merr & kErrStackFull) {
-      set_err("mapping factor table full: more than %d surf points after VoxelGrid; raise vloam_limits::max_surf_stack_points", h->map.surf_cap);
-      return VLOAM_ERR_CAPACITY;
-    }
-    if (merr & kErrMapDeferred) { set_err("raw-point capacity of the map exceeded (more than 255 un-merged points in a voxel of a cube outside the valid block, or more than 64 raw voxels around one query)"); return VLOAM_ERR_CAPACITY; }
-    if (merr & kErrSolverSync) { set_err("a workgroup of the scan-feature VoxelGrid gave up waiting for the bins in front of it"); return VLOAM_ERR_HIP; }
-    if (merr & kErrVoDegenerate) { set_err("a VO solve returned a zero rotation angle: poses are NaN from that frame on, as in the reference (visual_odometry.cpp:427-430)"); return VLOAM_ERR_INVALID; }
+    TRY(sticky_map_status(h, merr));
   }
   if (h->img.max_w != 0 && h->img.count >= 0) {
     // the image front-end's own sticky word: a corner / match set cut by one of its capacities differs from goodFeaturesToTrack's and was

@@ -1,6 +1,6 @@
 // Host-only: the handle behind the C ABI and what the translation units of the host side share (c_api.cpp: creation and destruction;
 // capi_sweep.cpp: the sweep pipeline; capi_frame.cpp: coupled frames, images, VO; capi_results.cpp: getters and debug hooks; capi_rows.cpp: the
-// per-sweep row products; capi_ckpt.cpp: checkpoints).  No .hip file includes this.  Helpers that cross files live in namespace vloam (mangled,
+// per-sweep row products; capi_ckpt.cpp: checkpoints; capi_query.cpp: map queries).  No .hip file includes this.  Helpers that cross files live in namespace vloam (mangled,
 // out of the C symbol list); a helper of one file is static there.
 #pragma once
 #include "../../include/vloam_hip/c_api.h"
@@ -211,8 +211,9 @@ static inline bool is_fresh(const vloam_handle* h) { return h->frame == 0 && !h-
 // from now on this handle launches one-workgroup solves (capi_sweep.cpp: poll_coop_flag; vloam_sync)
 static inline void set_no_coop(vloam_handle* h) { h->se.no_coop = 1; h->map.se.no_coop = 1; h->vo.se.no_coop = 1; }
 
-// ------------------------------------------------------------------ helpers that cross files (all defined in capi_sweep.cpp)
+// ------------------------------------------------------------------ helpers that cross files (all defined in capi_sweep.cpp, but the first: capi_results.cpp)
 namespace vloam {
+vloam_status sticky_map_status(const vloam_handle* h, int merr);         // the sticky map / solver bits of a handle's error word as vloam_sync reports them
 vloam_status sync_all(vloam_handle* h);                                  // drain, then synchronise every stream of the handle
 vloam_status drain_deferred(vloam_handle* h, int lag_lo, int lag_map);   // enqueue the odometry / mapping still owed (0, 0: all of it, the pending host sweep first)
 vloam_status check_host_sweeps(const vloam_handle* h, const float* const* xyz_pad4, const int* n);   // admission of host sweeps, before anything is copied

@@ -214,6 +214,12 @@ vloam_status map_error(MapContext* m, int* err_bits, int clear_mask = 0, long lo
 vloam_status map_debug_get(MapContext* m, int item, void* buf, long long cap, long long* n);
 // == /laser_cloud_map (laser_mapping.cpp:778-793): every cube's corner cloud then surf cloud, cube index ascending
 vloam_status map_export(MapContext* m, hipStream_t st, float* xyzi4, long long cap, long long* n);
+// the corner (0) or surf (1) half of it, same order within the half
+vloam_status map_export_kind(MapContext* m, hipStream_t st, int kind, float* xyzi4, long long cap, long long* n);
+// map_query.hip (a code object of its own): the k <= 8 nearest map points within `radius` of n query points (device addresses, map frame) of the
+// selected session, kind 0 corner map / 1 surf map / 2 both.  Enqueue only, no allocation: d_xyzi4 [n][k] float4, d_d2 [n][k], d_count [n].
+vloam_status map_query_enqueue(MapContext* m, hipStream_t st, int kind, int k, float radius, const void* d_xyz_pad4, int n, void* d_xyzi4, void* d_d2,
+                               void* d_count);
 // Publications of sweep `frame`, enqueued on the mapping stream behind map_enqueue of that sweep: the registered cloud first, then `done`
 // (non-null on a handle with the registered cloud, whose map_enqueue was given done == nullptr: k_map_register still reads the sweep's buffer
 // set), then the map, which reads the voxel tables only.  cloud / S: the sweep's laserCloudFullRes and its scalars, session 0's addresses.

@@ -20,7 +20,8 @@
 //                             21x21x11 window (tombstones); table health -> host-mapped rebuild flag
 //   k_map_rebuild_* grid      (rare, between sweeps) gather live records, clear, reinsert: tombstone reclamation
 //   (map_grow.hip)            growable handles: k_map_grow rehashes a table into a fresh one between sweeps, k_map_progress reports its keys
-//   k_map_export    grid      /laser_cloud_map (LM:778-793) for vloam_get_map
+//   k_map_export    grid      /laser_cloud_map (LM:778-793) for vloam_get_map / vloam_get_map_kind
+//   (map_query.hip)           k_map_query: the k nearest map points of caller-supplied points, on request (vloam_map_query)
 //   k_map_pub_*     grid      the same cloud ordered on the device, published behind a sweep's mapping (vloam_limits::map_pub_number)
 #include <hip/hip_runtime.h>
 #include <float.h>
@@ -1450,7 +1451,8 @@ __global__ __launch_bounds__(256) void k_map_export(VoxelTable T, const MapState
   }
 }
 
-vloam_status map_export(MapContext* m0, hipStream_t st, float* xyzi4, long long cap, long long* n) {
+// kinds: bit 0 the corner clouds, bit 1 the surf clouds
+static vloam_status map_export_kinds(MapContext* m0, hipStream_t st, int kinds, float* xyzi4, long long cap, long long* n) {
   const MapContext msel = m0->for_session(m0->sel);
   const MapContext* m = &msel;
   if (hipStreamSynchronize(st) != hipSuccess) return VLOAM_ERR_HIP;
@@ -1463,7 +1465,7 @@ vloam_status map_export(MapContext* m0, hipStream_t st, float* xyzi4, long long 
   vloam_status rc = VLOAM_OK;
   unsigned long long cnt = 0;
   if (hipMemsetAsync(d_n, 0, sizeof(*d_n), st) != hipSuccess) rc = VLOAM_ERR_HIP;
-  for (int k = 0; k < 2 && rc == VLOAM_OK; k++) VL_RAW_LAUNCH(k_map_export, dim3(1024), dim3(256), 0, st, m->tab[k], m->state, k, d_rows, bound, d_n);
+  for (int k = 0; k < 2 && rc == VLOAM_OK; k++) if ((kinds >> k) & 1) VL_RAW_LAUNCH(k_map_export, dim3(1024), dim3(256), 0, st, m->tab[k], m->state, k, d_rows, bound, d_n);
   if (rc == VLOAM_OK && (hipStreamSynchronize(st) != hipSuccess || hipMemcpy(&cnt, d_n, sizeof(cnt), hipMemcpyDeviceToHost) != hipSuccess)) rc = VLOAM_ERR_HIP;
   std::vector<ExportRow> rows((size_t)((long long)cnt < bound ? (long long)cnt : bound));
   if (rc == VLOAM_OK && !rows.empty() && hipMemcpy(rows.data(), d_rows, rows.size() * sizeof(ExportRow), hipMemcpyDeviceToHost) != hipSuccess) rc = VLOAM_ERR_HIP;
@@ -1475,6 +1477,9 @@ vloam_status map_export(MapContext* m0, hipStream_t st, float* xyzi4, long long 
   for (long long i = 0; xyzi4 && i < c; i++) { xyzi4[4 * i] = rows[(size_t)i].x; xyzi4[4 * i + 1] = rows[(size_t)i].y; xyzi4[4 * i + 2] = rows[(size_t)i].z; xyzi4[4 * i + 3] = rows[(size_t)i].w; }
   return VLOAM_OK;
 }
+
+vloam_status map_export(MapContext* m, hipStream_t st, float* xyzi4, long long cap, long long* n) { return map_export_kinds(m, st, 3, xyzi4, cap, n); }
+vloam_status map_export_kind(MapContext* m, hipStream_t st, int kind, float* xyzi4, long long cap, long long* n) { return map_export_kinds(m, st, 1 << kind, xyzi4, cap, n); }
 
 vloam_status map_get_cloud(MapContext* m0, hipStream_t st, int which, const SRBuffers& cur, float* xyzi4, int cap, int* n) {
   // `cur` is already the selected session's buffer set (the caller rebased it)
