@@ -1,5 +1,5 @@
 // How fast does a KERNEL read a 2 MB sweep out of pinned host memory (zero-copy over PCIe), against hipMemcpyAsync of the same buffer — on the
-// GPU (HIP events) and on the HOST (time inside the API calls)?  Behind the host-input path of c_api.cpp.
+// GPU (HIP events) and on the HOST (time inside the API calls)?  Behind the host-input path of capi_sweep.cpp.
 //   hipcc --offload-arch=gfx950 -O3 -Wno-unused-result -o /tmp/pinned_read tools/microbench/pinned_read.hip && /tmp/pinned_read
 #include <hip/hip_runtime.h>
 #include <chrono>

@@ -160,11 +160,11 @@ vloam_status vloam_trajectory_device_ptr(vloam_handle* h, void** d_ptr, long lon
 }
 
 // ------------------------------------------------------------------ parity hooks
+// copy_dev (vloam_device.h) + what HIPCHK adds to a failure: the text of vloam_last_error
 static vloam_status copy_out(const void* d_src, size_t bytes, void* buf, long long cap, long long* n) {
-  if (n) *n = (long long)bytes;
-  size_t m = bytes < (size_t)cap ? bytes : (size_t)cap;
-  if (buf && m) HIPCHK(hipMemcpy(buf, d_src, m, hipMemcpyDeviceToHost));
-  return VLOAM_OK;
+  const vloam_status s = copy_dev(d_src, bytes, buf, cap, n);
+  if (s != VLOAM_OK) set_err("hipMemcpy(buf, d_src, m, hipMemcpyDeviceToHost) failed: %s (%s:%d)", hipGetErrorString(hipPeekAtLastError()), __FILE__, __LINE__);
+  return s;
 }
 
 vloam_status vloam_debug_get(vloam_handle* h, int stage, int item, void* buf, long long cap, long long* n) {

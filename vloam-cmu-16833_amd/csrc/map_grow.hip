@@ -1,6 +1,6 @@
 // Growable voxel map (vloam_map_options::grow, single-sequence handles): the rehash of a table into a larger one between two sweeps, the
 // per-sweep report the host's growth decision starts from, and that decision.  A translation unit (and code object) of its own: the kernels
-// every handle launches (map_kernels.hip) are not touched by it.
+// every handle launches (map_kernels.hip, map_stack.hip, map_output.hip) are not touched by it.
 //   k_map_grow_begin  1 thread  the lists that hold slot ids and the table's counters start over
 //   k_map_grow        grid      every live record of the old table -> the new one
 //   k_map_progress    1 WG      behind k_map_finalize of every mapped sweep: live keys, block keys, keys incl. tombstones -> host-mapped words

@@ -1,4 +1,4 @@
-// laserMapping on gfx950 — host-visible interface (map_kernels.hip).
+// laserMapping on gfx950 — host-visible interface of the map_*.hip files (the prototypes at the end are grouped by implementing file).
 //
 // The reference keeps 21x21x11 cubes of pcl clouds, gathers the 5x5x3 block around the sensor, builds
 // two kd-trees per sweep and re-voxelises every valid cube (laser_mapping.cpp:198-708).  Here the map
@@ -21,14 +21,14 @@ constexpr int kStackCapSurf = 24576;    // voxels of one sweep's lessFlat cloud 
 constexpr int kMapFactorCap = kStackCapCorner + kStackCapSurf;
 // Large stack tier (vloam_limits::max_surf_stack_points): a handle may size its surf stack — and everything indexed by a stack slot — up to
 // kStackCapSurfMax in steps of kStackCapSurfStep.  Corner slots stay [0, kStackCapCorner), surf slots behind them.  Such a handle launches the
-// *_tier forms of the kernels that bake the constants above in (map_kernels.hip) and solves in the packed form (more than 512 mask rows).
+// *_tier forms of the kernels that bake the constants above in (map_kernels.hip, map_prepare_fit.inc.h) and solves in the packed form (more than 512 mask rows).
 constexpr int kStackCapSurfStep = 8192, kStackCapSurfMax = 131072;
 static_assert(kStackCapSurfMax <= (1 << 17), "the tier's raw-point arrival stamp keeps 17 bits of stack index (k_map_finalize_tier)");
 constexpr int kPendCap = 16;            // stack points that may land in one map voxel in one sweep
 // Voxel indices one axis of a 50 m cube can take at a leaf of 1 / inv (+ slack: the first index of a cube is taken one cell early, and the
 // cube test runs in f64 on the point while the voxel index is an f32 product): the radix of k_map_assoc's 32-bit tie rank — the position of
 // a voxel in the reference's gathered map cloud, 75 cubes x radix^3.  vloam_create keeps 75 radix^3 below 2^32 (leaf >= 0.132 m); the
-// voxel key itself has 9 bits per axis (map_kernels.hip).
+// voxel key itself has 9 bits per axis (map_table.h).
 __host__ __device__ inline int vox_radix(float inv) { return (int)(50.0f * inv) + 4; }
 
 // One map voxel == one 32-byte record, so that a candidate of the 5-NN search, an insert and a finalize each touch ONE cache line
@@ -203,23 +203,22 @@ struct MapContext {
   float inv_leaf[2] = {0, 0};
 };
 
+// ---- map_kernels.hip: the mapping chain and its state
 // layout: carve the session arena (called twice: dry to measure, then for real); init: the initial device state of session 0
 vloam_status map_layout(MapContext* m, const vloam_config& cfg, Arena& A);
 vloam_status map_init(MapContext* m, hipStream_t st);
-vloam_status map_stack_enqueue(MapContext* m, hipStream_t st, const SRBuffers& cur, int set, ProfHook* ph, hipEvent_t done = nullptr);
 vloam_status map_enqueue(MapContext* m, const vloam_config& cfg, hipStream_t st, const SRBuffers& cur, LOState* lo, double* traj_row14,
                          bool skip_frame, int set, ProfHook* ph, hipEvent_t done = nullptr);
+vloam_status map_force_rebuild(MapContext* m, hipStream_t st);  // every session
+void map_destroy(MapContext* m);
+// ---- map_stack.hip: the scan-feature VoxelGrid, enqueued on the scan-registration stream
+vloam_status map_stack_enqueue(MapContext* m, hipStream_t st, const SRBuffers& cur, int set, ProfHook* ph, hipEvent_t done = nullptr);
+// ---- map_output.hip: what a caller reads of the map and of a sweep's clouds
 vloam_status map_get_cloud(MapContext* m, hipStream_t st, int which, const SRBuffers& cur, float* xyzi4, int cap, int* n);
-vloam_status map_error(MapContext* m, int* err_bits, int clear_mask = 0, long long* fallback_solves = nullptr);
-vloam_status map_debug_get(MapContext* m, int item, void* buf, long long cap, long long* n);
 // == /laser_cloud_map (laser_mapping.cpp:778-793): every cube's corner cloud then surf cloud, cube index ascending
 vloam_status map_export(MapContext* m, hipStream_t st, float* xyzi4, long long cap, long long* n);
 // the corner (0) or surf (1) half of it, same order within the half
 vloam_status map_export_kind(MapContext* m, hipStream_t st, int kind, float* xyzi4, long long cap, long long* n);
-// map_query.hip (a code object of its own): the k <= 8 nearest map points within `radius` of n query points (device addresses, map frame) of the
-// selected session, kind 0 corner map / 1 surf map / 2 both.  Enqueue only, no allocation: d_xyzi4 [n][k] float4, d_d2 [n][k], d_count [n].
-vloam_status map_query_enqueue(MapContext* m, hipStream_t st, int kind, int k, float radius, const void* d_xyz_pad4, int n, void* d_xyzi4, void* d_d2,
-                               void* d_count);
 // Publications of sweep `frame`, enqueued on the mapping stream behind map_enqueue of that sweep: the registered cloud first, then `done`
 // (non-null on a handle with the registered cloud, whose map_enqueue was given done == nullptr: k_map_register still reads the sweep's buffer
 // set), then the map, which reads the voxel tables only.  cloud / S: the sweep's laserCloudFullRes and its scalars, session 0's addresses.
@@ -230,20 +229,27 @@ vloam_status map_publish_enqueue(MapContext* m, hipStream_t st, const float4* cl
 // which: 0 map, 1 registered cloud; the latest publication of the selected session.  Waits for that publication's event only.
 // d_ptr (may be NULL): its device address.  xyzi4 (may be NULL): host buffer of cap points.  VLOAM_ERR_CAPACITY: the map overflowed (*n = true count).
 vloam_status map_published_get(MapContext* m, int which, float* xyzi4, long long cap, long long* n, int* frame, void** d_ptr);
-vloam_status map_force_rebuild(MapContext* m, hipStream_t st);  // every session
-// growable handles (m->grow != null).  map_force_grow: test hook, one doubling of both tables now (between two sweeps, on the mapping stream).
+// ---- map_inspect.hip: host inspection (sticky error words, parity hooks, counts)
+vloam_status map_error(MapContext* m, int* err_bits, int clear_mask = 0, long long* fallback_solves = nullptr);
+vloam_status map_debug_get(MapContext* m, int item, void* buf, long long cap, long long* n);
+vloam_status map_counts(MapContext* m, long long c[16]);
+// ---- map_query.hip (a code object of its own): the k <= 8 nearest map points within `radius` of n query points (device addresses, map frame) of the
+// selected session, kind 0 corner map / 1 surf map / 2 both.  Enqueue only, no allocation: d_xyzi4 [n][k] float4, d_d2 [n][k], d_count [n].
+vloam_status map_query_enqueue(MapContext* m, hipStream_t st, int kind, int k, float radius, const void* d_xyz_pad4, int n, void* d_xyzi4, void* d_d2,
+                               void* d_count);
+// ---- map_grow.hip: growable handles (m->grow != null).  map_force_grow: test hook, one doubling of both tables now (between two sweeps, on the mapping stream).
 // map_grow_release: frees retired buffers whose grow chain has finished (hipEventQuery); call with nothing of the handle in flight — hipFree
 // synchronises the device.
 vloam_status map_force_grow(MapContext* m, hipStream_t st);
 void map_grow_release(MapContext* m);
-// the rest of map_grow.hip's interface, for map_kernels.hip: the tables' first allocation / everything the option owns; a rehash of table
+// the rest of map_grow.hip's interface, for map_kernels.hip (map_layout / map_init / map_destroy / map_enqueue): the tables' first allocation / everything the option owns; a rehash of table
 // `kind` at its size (tombstone reclamation); the growth decision in front of a mapped sweep; k_map_progress behind its k_map_finalize
 vloam_status map_grow_init(MapContext* m, hipStream_t st);
 void map_grow_destroy(MapContext* m);
 vloam_status map_grow_rehash(MapContext* m, hipStream_t st, int kind);
 vloam_status map_grow_before_sweep(MapContext* m, hipStream_t st);
 void map_grow_progress_enqueue(MapContext* m, hipStream_t st);
-// checkpoint of a sequence (vloam_checkpoint_save / _load; single-session handles, nothing in flight).  map_ckpt.hip: the live records of both
+// ---- map_ckpt.hip, map_grow.hip: checkpoint of a sequence (vloam_checkpoint_save / _load; single-session handles, nothing in flight).  map_ckpt.hip: the live records of both
 // tables counted (n_rec) and, with d_out, packed into a device buffer the caller frees — corner records, then surf records; the reverse into the
 // empty tables of a fresh handle from host memory.  ms (may be null): kernel times, {count + scan, pack} / unpack.  map_grow.hip: what a
 // growable handle does first (the table size its growth bound asks for; the step to it and the report words).
@@ -251,7 +257,5 @@ vloam_status map_ckpt_pack(MapContext* m, hipStream_t st, long long n_rec[2], Vo
 vloam_status map_ckpt_unpack(MapContext* m, hipStream_t st, const void* recs, const long long n_rec[2], float* ms);
 int map_grow_restore_log2(const MapContext* m, int kind, long long live, long long blk);
 vloam_status map_grow_restore(MapContext* m, hipStream_t st, const int lg[2], const long long live[2], const long long blk[2], long long mapped);
-void map_destroy(MapContext* m);
-vloam_status map_counts(MapContext* m, long long c[16]);
 
 }  // namespace vloam

@@ -1,14 +1,10 @@
-// laserMapping on gfx950: scan-to-map ICP against a persistent voxel hash.
-// Restates LaserMapping::input / solveMapping, /root/reference/src/lidar_odometry_mapping/src/laser_mapping.cpp:167-708
+// laserMapping on gfx950: scan-to-map ICP against a persistent voxel hash — the mapping chain, which sets the sweep period, and what owns its state.
+// Restates LaserMapping::input / solveMapping, the reference's src/lidar_odometry_mapping/src/laser_mapping.cpp:167-708
 // ("LM:<line>").  One sweep = 11 launches incl. 2 Levenberg–Marquardt solves (which compact on their own), no host synchronisation; the two
-// k_map_ds_* launches only need the sweep's feature clouds and run on a stream of their own.  Every kernel carries the session
+// k_map_ds_* launches (map_stack.hip) only need the sweep's feature clouds and run on a stream of their own.  Every kernel carries the session
 // index of a batched handle in blockIdx.z and rebases its pointer arguments by blockIdx.z * ss (vloam_device.h).
 //   k_map_prepare   1 WG      initial guess (LM:193-194), centre cube + grid roll (LM:207-402), gate (LM:448); stops taking sweeps
 //                             when the voxel table is full
-//   k_map_ds_bin    grid      pcl::VoxelGrid of the scan features (LM:432-440) without a global hash, pass 1: PCL's cell index from the cloud's
-//                             bounding box (incl. its index-overflow guard: output = input), sample splitters, (cell << 24 | point) keys binned
-//   k_map_ds_reduce 64 WGs    pass 2: bins drawn by ticket, sorted in LDS, output slots by a decoupled look-back over the bins' cell counts,
-//                             per cell the input-ordered f32 centroid, output in PCL's order (cells ascending)
 //   k_map_assoc     1 wave/pt pointAssociateToMap, exact 5-NN through the block-occupancy index of the voxel hash (one 32-byte
 //                             record per candidate); the second outer round re-ranks the first round's candidates             x2
 //   k_map_fit       1 thread/pt 3x3 eigen / 5x3 least squares, emission of LidarEdgeFactor / LidarPlaneNormFactor (LM:472-581) x2
@@ -19,68 +15,26 @@
 //                             raw voxels of cubes that became valid; after a grid roll drops the voxels whose cube left the
 //                             21x21x11 window (tombstones); table health -> host-mapped rebuild flag
 //   k_map_rebuild_* grid      (rare, between sweeps) gather live records, clear, reinsert: tombstone reclamation
+//   (map_stack.hip)           k_map_ds_bin / k_map_ds_reduce: pcl::VoxelGrid of the scan features (LM:432-440), on the scan-registration stream
 //   (map_grow.hip)            growable handles: k_map_grow rehashes a table into a fresh one between sweeps, k_map_progress reports its keys
-//   k_map_export    grid      /laser_cloud_map (LM:778-793) for vloam_get_map / vloam_get_map_kind
+//   (map_output.hip)          k_map_register, k_map_export, k_map_pub_*: vloam_get_map, vloam_get_features(h, 11), the published clouds
 //   (map_query.hip)           k_map_query: the k nearest map points of caller-supplied points, on request (vloam_map_query)
-//   k_map_pub_*     grid      the same cloud ordered on the device, published behind a sweep's mapping (vloam_limits::map_pub_number)
+//   (map_inspect.hip)         host inspection: sticky error words, parity hooks (map_debug_get), counts
+//   (map_device.h)            the device helpers these files share
 #include <hip/hip_runtime.h>
-#include <float.h>
-#include <limits.h>
 #include <math.h>
 #include <string.h>
-#include <algorithm>
 #include <type_traits>
 #include "lm_solve.h"
 #include "map_kernels.h"
+#include "map_device.h"
 #include "map_table.h"
 #include "subwave.h"
-#include "bitonic.h"
 
 namespace vloam {
 
-// ---------------------------------------------------------------------------------------------- helpers
-// LM:207-216 / LM:643-652: C int() truncation plus the "< 0" correction; absolute cube coordinate (no centre offset)
-__device__ __forceinline__ int cube_abs(double v) {
-  int c = int((v + 25.0) / 50.0);
-  if (v + 25.0 < 0) c--;
-  return c;
-}
-__device__ __forceinline__ int cube_lo(double v) { return (int)floor((v - 1e-3 + 25.0) * 0.02); }
-__device__ __forceinline__ int cube_hi(double v) { return (int)floor((v + 1e-3 + 25.0) * 0.02); }
-// first global voxel index that can belong to cube A (minus one cell of slack so the local index is never negative)
-__device__ __forceinline__ int cube_voxel_base(int A, float inv) { return (int)floor((50.0 * (double)A - 25.0) * (double)inv) - 1; }
-
-// Eigen q * v (see lm_solve.hip / lo_kernels.hip) followed by + t, rounded to f32: pointAssociateToMap, LM:146-155
-__device__ __forceinline__ float4 associate_to_map(float4 pi, const double* q, const double* t) {
-  const double ux = q[0], uy = q[1], uz = q[2], w = q[3];
-  const double vx = pi.x, vy = pi.y, vz = pi.z;
-  double cx = uy * vz - uz * vy, cy = uz * vx - ux * vz, cz = ux * vy - uy * vx;
-  cx = cx + cx; cy = cy + cy; cz = cz + cz;
-  const double dx = uy * cz - uz * cy, dy = uz * cx - ux * cz, dz = ux * cy - uy * cx;
-  float4 o;
-  o.x = (float)(((vx + w * cx) + dx) + t[0]);
-  o.y = (float)(((vy + w * cy) + dy) + t[1]);
-  o.z = (float)(((vz + w * cz) + dz) + t[2]);
-  o.w = pi.w;
-  return o;
-}
-
-__device__ __forceinline__ void dquat_mul(const double* a, const double* b, double* r) {
-  r[0] = a[3] * b[0] + a[0] * b[3] + a[1] * b[2] - a[2] * b[1];
-  r[1] = a[3] * b[1] + a[1] * b[3] + a[2] * b[0] - a[0] * b[2];
-  r[2] = a[3] * b[2] + a[2] * b[3] + a[0] * b[1] - a[1] * b[0];
-  r[3] = a[3] * b[3] - a[0] * b[0] - a[1] * b[1] - a[2] * b[2];
-}
-__device__ __forceinline__ void dquat_rot(const double* q, const double* v, double* o) {
-  const double ux = q[0], uy = q[1], uz = q[2], w = q[3];
-  double cx = uy * v[2] - uz * v[1], cy = uz * v[0] - ux * v[2], cz = ux * v[1] - uy * v[0];
-  cx = cx + cx; cy = cy + cy; cz = cz + cz;
-  const double dx = uy * cz - uz * cy, dy = uz * cx - ux * cz, dz = ux * cy - uy * cx;
-  o[0] = (v[0] + w * cx) + dx; o[1] = (v[1] + w * cy) + dy; o[2] = (v[2] + w * cz) + dz;
-}
-
 // ---------------------------------------------------------------------------------------------- prepare
-// k_map_prepare (and, below, k_map_fit): map_kernels_capped.inc, included once per form further down
+// k_map_prepare (and, below, k_map_fit): map_prepare_fit.inc.h, included once per form further down
 // Drop voxels whose cube left the window (the reference clears the slab that wraps, LM:240-241 etc.).  Only after a roll.
 // The window is +-500 m around the sensor while queries and inserts stay within the +-125 m valid block, so nothing of the
 // sweep that rolled can touch such a voxel: the sweep's last launch (k_map_finalize) does the purge on its way out, instead
@@ -99,346 +53,7 @@ __device__ void map_purge(const VoxelTable& T, const MapState* ms, int first, in
   if (dead) atomicAdd(&T.stats[1], dead);  // tombstones: the key stays (probe chains run through it) until the table is rebuilt
 }
 
-// ---------------------------------------------------------------------------------------------- scan VoxelGrid
-// pcl::VoxelGrid<PointXYZI> (PCL 1.10 filters/impl/voxel_grid.hpp applyFilter) of laserCloudCornerLast / laserCloudSurfLast, LM:432-440:
-// getMinMax3D -> the overflow guard (more than INT_MAX cells in the bounding box: a warning and output = input) -> cell index
-// idx = ijk0 + ijk1 * div0 + ijk2 * div0 * div1 with ijk = floor(p * inverse_leaf) - min_b -> sort by idx -> one centroid per cell, f32
-// sums in the order of the sorted index vector (std::sort leaves the order inside a cell open; canonical here and in the oracle: input order).
-//
-// Two launches, no global hash, no whole-chip ranking (rounds 1 - 4 hashed the points into a table, ranked the occupied cells by counting
-// — u^2 compares — and folded one wavefront per cell: 80 k of the 227 k wavefront-microseconds a sweep cost at B = 8, 14 MB of traffic for
-// 0.6 MB of points):
-//   k_map_ds_bin     cuts the key space into P = ceil(n / 512) bins at the quantiles of a sample of the cloud (every workgroup sorts the same
-//                    <= 2 048 sampled keys in LDS: same splitters everywhere, no exchange), and appends every point's sort key
-//                    (cell index << 24 | point index) to its bin's region — one device-scope atomic per run of equal bins in a wavefront;
-//   k_map_ds_reduce  one workgroup per bin: bitonic sort of the bin's keys in LDS, cell heads, the bin's cell count published for the bins
-//                    behind it (look-back over the lower bins, in ticket order: a workgroup only ever waits for workgroups that started
-//                    before it), centroids in input order, written at their final place in VoxelGrid's output order.
-// A bin is a contiguous range of cell indices, so bin order == output order.  Correctness never rests on the sample: a bin that outgrows
-// its region (kDsBinCap keys, e.g. thousands of points in ONE cell with a coarse leaf) spills into an overflow list and takes the slow path
-// (gather, rank by counting in global memory); test_scan_voxel_bins_overflow drives it.
-struct DsGrid { float mnb[3]; int div0, div1; bool overflow; };
-
-// getMinMax3D + the guard + min_b / div_b (voxel_grid.hpp), from the per-scan-line boxes k_sr_compact left; every lane gets the result
-__device__ __forceinline__ DsGrid ds_grid(const FrameScalars* __restrict__ S, int kind, float inv) {
-  const int lane = threadIdx.x & 63;
-  float mn[3], mx[3];
-#pragma unroll
-  for (int a = 0; a < 3; a++) { mn[a] = S->less_bbox[kind][lane][a]; mx[a] = S->less_bbox[kind][lane][3 + a]; }
-#pragma unroll
-  for (int a = 0; a < 3; a++)
-    for (int d = 32; d > 0; d >>= 1) { mn[a] = fminf(mn[a], __shfl_xor(mn[a], d)); mx[a] = fmaxf(mx[a], __shfl_xor(mx[a], d)); }
-  DsGrid g;
-  const long long dx = (long long)((mx[0] - mn[0]) * inv) + 1, dy = (long long)((mx[1] - mn[1]) * inv) + 1, dz = (long long)((mx[2] - mn[2]) * inv) + 1;
-  g.overflow = dx * dy * dz > (long long)INT_MAX;
-  int minb[3], maxb[3];
-#pragma unroll
-  for (int a = 0; a < 3; a++) { minb[a] = (int)floorf(mn[a] * inv); maxb[a] = (int)floorf(mx[a] * inv); g.mnb[a] = (float)minb[a]; }
-  g.div0 = maxb[0] - minb[0] + 1; g.div1 = maxb[1] - minb[1] + 1;
-  return g;
-}
-__device__ __forceinline__ u64 ds_cell(float4 p, float inv, const DsGrid& g) {
-  const int i0 = (int)(floorf(p.x * inv) - g.mnb[0]), i1 = (int)(floorf(p.y * inv) - g.mnb[1]), i2 = (int)(floorf(p.z * inv) - g.mnb[2]);
-  return (u64)(unsigned)i0 + (u64)(unsigned)g.div0 * ((u64)(unsigned)i1 + (u64)(unsigned)g.div1 * (u64)(unsigned)i2);
-}
-constexpr int kDsIdxBits = 24;   // point index in the low bits of a sort key (max_points <= 2^24, vloam_create); the cell index (< 2^33) above
-__device__ __forceinline__ int ds_num_bins(int n) { const int p = (n + kDsBinTarget - 1) / kDsBinTarget; return p < 1 ? 1 : (p > kDsMaxBins ? kDsMaxBins : p); }
-__device__ __forceinline__ int ds_num_samples(int P) { return P <= 32 ? 256 : (P <= 64 ? 512 : (P <= 128 ? 1024 : 2048)); }
-// bin of a cell: the number of splitters <= cell (upper bound; equal cells always share a bin)
-__device__ __forceinline__ int ds_bin_of(const u64* split, int P, u64 cell) {
-  int lo = 0, hi = P - 1;   // answer in [0, P - 1]
-  while (lo < hi) { const int mid = (lo + hi) >> 1; if (split[mid] <= cell) lo = mid + 1; else hi = mid; }
-  return lo;
-}
-
-constexpr int kDsTile = 2048;   // points a workgroup of the binning pass takes per trip
-constexpr int kDsReduceGrid = 64;   // workgroups of the reduce pass per cloud (each keeps drawing bins)
-__global__ __launch_bounds__(256) void k_map_ds_bin(const float4* __restrict__ corner_last, const float4* __restrict__ surf_last,
-                                                    const FrameScalars* __restrict__ S, DsScratch D0, DsScratch D1, float inv0, float inv1,
-                                                    float4* __restrict__ stack0, float4* __restrict__ stack1, StackInfo* fr, size_t ss) {
-  VL_SESSION(ss); RB(corner_last); RB(surf_last); RB(S); D0.rebase(so_); D1.rebase(so_); RB(stack0); RB(stack1); RB(fr);
-  __shared__ __attribute__((aligned(16))) u64 s_key[2048];
-  __shared__ __attribute__((aligned(16))) u64 s_srt[512];
-  __shared__ u64 s_split[kDsMaxBins];
-  __shared__ int s_cnt[kDsMaxBins], s_base[kDsMaxBins];
-  const int kind = blockIdx.y, tid = threadIdx.x;
-  const DsScratch D = kind ? D1 : D0;
-  const float inv = kind ? inv1 : inv0;
-  const float4* pts = kind ? surf_last : corner_last;
-  float4* stack = kind ? stack1 : stack0;
-  const int n = kind ? S->n_less_flat : S->n_less_sharp;
-  if (blockIdx.x == 0 && tid == 0) D.cursor[kDsMaxBins + 1] = 0;   // the reduce pass's ticket counter (nothing of the previous sweep draws from it any more)
-  if (n <= 0) { if (blockIdx.x == 0 && tid == 0) fr->n_stack[kind] = 0; return; }
-  if ((int)blockIdx.x * kDsTile >= n) return;
-  const DsGrid g = ds_grid(S, kind, inv);
-  if (g.overflow) {   // "Leaf size is too small for the input dataset. Integer indices would overflow." — output = *input_
-    for (int t0 = blockIdx.x * kDsTile; t0 < n; t0 += gridDim.x * kDsTile)   // (only the workgroups whose first tile exists are here)
-      for (int i = t0 + tid; i < min(t0 + kDsTile, n); i += 256) if (i < D.stack_cap) stack[i] = pts[i];
-    if (blockIdx.x == 0 && tid == 0) { fr->n_stack[kind] = min(n, D.stack_cap); if (n > D.stack_cap) atomicOr(&fr->error, kErrStackFull); }
-    return;
-  }
-  const int P = ds_num_bins(n);
-  if (P > 1) {
-    // the splitters: P - 1 quantiles of Sn evenly spaced sample points; every workgroup computes the same ones
-    const int Sn = ds_num_samples(P);
-    for (int j = tid; j < Sn; j += 256) s_key[j] = ds_cell(pts[(int)(((long long)j * n) / Sn)], inv, g);
-    __syncthreads();
-    const u64* srt = s_key;
-    if (Sn <= 512) {
-      // few samples: rank by counting (every lane reads every key once, broadcast LDS reads, no dependent exchange stages — a bitonic
-      // network over 512 keys is ~45 dependent stages; this is the prologue of EVERY workgroup of the pass)
-      for (int j = tid; j < Sn; j += 256) {
-        const u64 mine = s_key[j];
-        int rank = 0;
-#pragma unroll 8
-        for (int e = 0; e < Sn; e += 2) {   // (unrolled: eight LDS reads in flight, or every iteration waits out the LDS latency)
-          const ulonglong2 k2 = *(const ulonglong2*)&s_key[e];
-          rank += (k2.x < mine || (k2.x == mine && e < j)) ? 1 : 0;
-          rank += (k2.y < mine || (k2.y == mine && e + 1 < j)) ? 1 : 0;
-        }
-        s_srt[rank] = mine;
-      }
-      __syncthreads();
-      srt = s_srt;
-    } else {
-      block_bitonic_sort_u64(s_key, Sn, tid, 256);
-    }
-    for (int j = tid; j < P - 1; j += 256) {
-      const u64 sp = srt[(int)(((long long)(j + 1) * Sn) / P)];
-      s_split[j] = sp;
-      if (blockIdx.x == 0) D.splitters[j] = sp;   // the reduce pass's slow path tells the bins of the overflow list by them
-    }
-    __syncthreads();
-  }
-  for (int t0 = blockIdx.x * kDsTile; t0 < n; t0 += gridDim.x * kDsTile) {
-    // the tile's points are counted per bin in LDS first: ONE device-scope cursor update per (workgroup, bin) and one memory round trip for
-    // all of them, instead of a dependent atomic round trip per 64 points
-    constexpr int kPer = kDsTile / 256;
-    __syncthreads();
-    for (int b = tid; b < P; b += 256) s_cnt[b] = 0;
-    __syncthreads();
-    float4 p[kPer];
-#pragma unroll
-    for (int e = 0; e < kPer; e++) { const int i = t0 + e * 256 + tid; p[e] = i < n ? pts[i] : make_float4(0.f, 0.f, 0.f, 0.f); }
-    u64 cell[kPer];
-    int bin[kPer], pos[kPer];
-#pragma unroll
-    for (int e = 0; e < kPer; e++) {
-      const int i = t0 + e * 256 + tid;
-      bin[e] = -1; pos[e] = 0; cell[e] = 0ull;
-      if (i < n) {
-        cell[e] = ds_cell(p[e], inv, g);
-        bin[e] = P > 1 ? ds_bin_of(s_split, P, cell[e]) : 0;
-        pos[e] = atomicAdd(&s_cnt[bin[e]], 1);
-      }
-    }
-    __syncthreads();
-    for (int b = tid; b < P; b += 256) { const int c = s_cnt[b]; s_base[b] = c > 0 ? atomicAdd(&D.cursor[b], c) : 0; }
-    __syncthreads();
-#pragma unroll
-    for (int e = 0; e < kPer; e++) {
-      const int i = t0 + e * 256 + tid;
-      if (i < n) {
-        const u64 key = (cell[e] << kDsIdxBits) | (u64)(unsigned)i;
-        const int at = s_base[bin[e]] + pos[e];
-        if (at < kDsBinCap) D.region[(size_t)bin[e] * kDsBinCap + at] = key;
-        else { const int o = atomicAdd(&D.cursor[kDsMaxBins], 1); D.over[o] = key; }   // (o < n <= max_points: every point is written exactly once)
-      }
-    }
-  }
-}
-
-__device__ __forceinline__ float rl(float v, int src) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), src)); }
-
-// heads / look-back / centroids of one bin whose keys lie sorted in `key` (LDS on the fast path, global memory on the slow one)
-template <bool LDS_KEYS>
-__device__ __forceinline__ void ds_reduce_sorted(const u64* key, int m, int bin, int P, const float4* __restrict__ pts, float4* __restrict__ stack,
-                                                 const DsScratch& D, StackInfo* fr, int kind, unsigned gen, int* s_cnt /* [256 + 8] */, int* s_big /* [3 * kDsBigCap + 1] */) {
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  // contiguous chunks: thread t owns keys [t * per, t * per + per)
-  const int per = (m + 255) / 256;
-  const int c0 = min(tid * per, m), c1 = min(c0 + per, m);
-  int heads = 0;
-  for (int i = c0; i < c1; i++) heads += (i == 0 || (key[i] >> kDsIdxBits) != (key[i - 1] >> kDsIdxBits)) ? 1 : 0;
-  // block exclusive scan of the head counts
-  int inc = heads;
-  for (int d = 1; d < 64; d <<= 1) { const int o = __shfl_up(inc, d); if (lane >= d) inc += o; }
-  if (lane == 63) s_cnt[256 + wave] = inc;
-  if (tid == 0) s_big[0] = 0;
-  __syncthreads();
-  int wbase = 0, u = 0;
-  for (int w = 0; w < 4; w++) { const int t = s_cnt[256 + w]; wbase += w < wave ? t : 0; u += t; }
-  const int rank0 = wbase + inc - heads;   // output rank (inside the bin) of this thread's first head
-  // publish this bin's cell count, then add up the bins in front (look-back; every one of them started before this workgroup took its ticket)
-  u64* done = D.done;
-  if (tid == 0) __hip_atomic_store(&done[bin], ((u64)gen << 32) | (u64)(unsigned)u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
-  int before = 0;
-  if (wave == 0) {
-    bool bad = false;
-    for (int b = lane; b < bin; b += 64) {
-      u64 v = 0ull;
-      int spins = 0;
-      for (;;) {
-        v = __hip_atomic_load(&done[b], __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT);
-        if ((unsigned)(v >> 32) == gen) break;
-        if (++spins > (1 << 22)) { bad = true; break; }
-        __builtin_amdgcn_s_sleep(2);
-      }
-      before += (int)(unsigned)(v & 0xffffffffull);
-    }
-    for (int d = 32; d > 0; d >>= 1) before += __shfl_xor(before, d);
-    // (never seen: a bounded wait instead of a hang.)  The offset would come from a partial sum: this bin stores NOTHING (its centroids would
-    // land on other bins' slots) and the sweep's stack is declared empty, so the mapping of this sweep associates nothing instead of
-    // consuming misplaced centroids; vloam_sync reports the sticky bit
-    const bool any_bad = __ballot(bad) != 0ull;
-    if (any_bad && lane == 0) { atomicOr(&fr->error, kErrSolverSync); }
-    if (lane == 0) s_cnt[0] = any_bad ? -1 : before;
-  }
-  __syncthreads();
-  const bool timed_out = s_cnt[0] < 0;
-  before = timed_out ? D.stack_cap : s_cnt[0];   // (every output slot then counts as beyond the stack: nothing is stored)
-  // centroids: the thread that owns a head walks the cell (its points in input order: the sort key ends in the point index); cells of more
-  // than kDsBigCell points are left to a whole wavefront each
-  int r = rank0;
-  for (int i = c0; i < c1; i++) {
-    const u64 ci = key[i] >> kDsIdxBits;
-    if (!(i == 0 || ci != (key[i - 1] >> kDsIdxBits))) continue;
-    int e = i + 1;
-    while (e < m && (key[e] >> kDsIdxBits) == ci) e++;
-    const int out = before + r;
-    r++;
-    if (out >= D.stack_cap) continue;   // reported by the last bin
-    if (e - i > kDsBigCell) {
-      const int q = atomicAdd(&s_big[0], 1);
-      if (q < kDsBigCap) { s_big[1 + 3 * q] = i; s_big[2 + 3 * q] = e; s_big[3 + 3 * q] = out; }
-      else {   // (more big cells than the list holds: this thread folds it after all)
-        float sx = 0.f, sy = 0.f, sz = 0.f, si = 0.f;
-        for (int j = i; j < e; j++) { const float4 p = pts[(int)(key[j] & ((1ull << kDsIdxBits) - 1ull))]; sx += p.x; sy += p.y; sz += p.z; si += p.w; }
-        const float nn = (float)(e - i);
-        stack[out] = make_float4(sx / nn, sy / nn, sz / nn, si / nn);
-      }
-      continue;
-    }
-    float sx = 0.f, sy = 0.f, sz = 0.f, si = 0.f;
-    for (int j = i; j < e; j += 4) {   // four loads in flight, added in order
-      float4 p[4];
-#pragma unroll
-      for (int q = 0; q < 4; q++) if (j + q < e) p[q] = pts[(int)(key[j + q] & ((1ull << kDsIdxBits) - 1ull))];
-#pragma unroll
-      for (int q = 0; q < 4; q++) if (j + q < e) { sx += p[q].x; sy += p[q].y; sz += p[q].z; si += p[q].w; }
-    }
-    const float nn = (float)(e - i);
-    stack[out] = make_float4(sx / nn, sy / nn, sz / nn, si / nn);
-  }
-  __syncthreads();
-  const int nbig = min(s_big[0], kDsBigCap);
-  for (int q = wave; q < nbig; q += 4) {   // a wavefront per big cell: 64 points fetched at once, folded one by one (f32, CentroidPoint's order)
-    const int i = s_big[1 + 3 * q], e = s_big[2 + 3 * q], out = s_big[3 + 3 * q];
-    float sx = 0.f, sy = 0.f, sz = 0.f, si = 0.f;
-    for (int j0 = i; j0 < e; j0 += 64) {
-      const int mm = min(64, e - j0);
-      const float4 p = lane < mm ? pts[(int)(key[j0 + lane] & ((1ull << kDsIdxBits) - 1ull))] : make_float4(0.f, 0.f, 0.f, 0.f);
-      for (int t = 0; t < mm; t++) { sx += rl(p.x, t); sy += rl(p.y, t); sz += rl(p.z, t); si += rl(p.w, t); }
-    }
-    if (lane == 0) { const float nn = (float)(e - i); stack[out] = make_float4(sx / nn, sy / nn, sz / nn, si / nn); }
-  }
-  if (bin == P - 1 && tid == 0) {
-    // the last bin has seen every other bin's count, i.e. every workgroup of this pass is done with the region counters, the overflow list
-    // and the ticket: hand them back clean for the next sweep
-    const int total = timed_out ? 0 : before + u;
-    fr->n_stack[kind] = min(total, D.stack_cap);
-    if (total > D.stack_cap) atomicOr(&fr->error, kErrStackFull);
-    D.cursor[kDsMaxBins] = 0; D.cursor[kDsMaxBins + 2] = 0;   // (the ticket counter is reset by the next sweep's binning pass: workgroups still draw from it)
-  }
-}
-
-__global__ __launch_bounds__(256) void k_map_ds_reduce(const float4* __restrict__ corner_last, const float4* __restrict__ surf_last,
-                                                       const FrameScalars* __restrict__ S, DsScratch D0, DsScratch D1, float inv0, float inv1,
-                                                       float4* __restrict__ stack0, float4* __restrict__ stack1, StackInfo* __restrict__ fr, unsigned gen,
-                                                       size_t ss) {
-  VL_SESSION(ss); RB(corner_last); RB(surf_last); RB(S); D0.rebase(so_); D1.rebase(so_); RB(stack0); RB(stack1); RB(fr);
-  __shared__ __attribute__((aligned(16))) u64 s_key[kDsBinCap];
-  __shared__ u64 s_split[kDsMaxBins];
-  __shared__ int s_cnt[256 + 8];
-  __shared__ int s_big[3 * kDsBigCap + 1];
-  __shared__ int s_bin;
-  const int kind = blockIdx.y, tid = threadIdx.x;
-  const DsScratch D = kind ? D1 : D0;
-  const float inv = kind ? inv1 : inv0;
-  const float4* pts = kind ? surf_last : corner_last;
-  float4* stack = kind ? stack1 : stack0;
-  const int n = kind ? S->n_less_flat : S->n_less_sharp;
-  if (n <= 0) return;
-  const int P = ds_num_bins(n);
-  if ((int)blockIdx.x >= P) return;
-  if (ds_grid(S, kind, inv).overflow) return;   // the binning pass copied the cloud (voxel_grid.hpp's guard)
-  // Bins are taken in ticket order, not in blockIdx order: the look-back then only waits for workgroups that are already running.  The
-  // grid is a fraction of kDsMaxBins (a capacity): a workgroup keeps taking tickets until the bins are gone — workgroups that only
-  // find out that there is nothing for them cost a wave slot for a memory round trip each, and on a chip full of sessions that adds up
-  // (8 192 such workgroups per launch at B = 16 were 85 % of this kernel's wave-microseconds).
-  for (;;) {
-  __syncthreads();   // (the previous bin's LDS is no longer read)
-  if (tid == 0) s_bin = atomicAdd(&D.cursor[kDsMaxBins + 1], 1);
-  __syncthreads();
-  const int bin = s_bin;
-  if (bin >= P) {
-    return;   // every ticket is out (the counter is reset by the next sweep's binning pass)
-  }
-  const int m_raw = D.cursor[bin];
-  __syncthreads();
-  if (tid == 0) D.cursor[bin] = 0;   // this bin's region counter, clean for the next sweep
-  if (m_raw <= kDsBinCap) {
-    int P2 = 256;
-    while (P2 < m_raw) P2 <<= 1;
-    const u64* reg = D.region + (size_t)bin * kDsBinCap;
-    for (int i = tid; i < P2; i += 256) s_key[i] = i < m_raw ? reg[i] : ~0ull;
-    __syncthreads();
-    block_bitonic_sort_u64(s_key, P2, tid, 256);
-    ds_reduce_sorted<true>(s_key, m_raw, bin, P, pts, stack, D, fr, kind, gen, s_cnt, s_big);
-    continue;
-  }
-  // ---- slow path: the bin outgrew its region.  Gather region + this bin's share of the overflow list, rank by counting (keys are unique:
-  // they end in the point index), continue from global memory.
-  const int n_over = D.cursor[kDsMaxBins];
-  for (int j = tid; j < P - 1; j += 256) s_split[j] = D.splitters[j];
-  __syncthreads();
-  int mine = 0;
-  for (int j = tid; j < n_over; j += 256) mine += (P > 1 ? ds_bin_of(s_split, P, D.over[j] >> kDsIdxBits) : 0) == bin ? 1 : 0;
-  for (int d = 32; d > 0; d >>= 1) mine += __shfl_xor(mine, d);
-  if ((tid & 63) == 0) s_cnt[256 + (tid >> 6)] = mine;
-  __syncthreads();
-  const int m = kDsBinCap + s_cnt[256] + s_cnt[257] + s_cnt[258] + s_cnt[259];
-  __syncthreads();
-  if (tid == 0) { s_cnt[1] = atomicAdd(&D.cursor[kDsMaxBins + 2], m); s_cnt[2] = kDsBinCap; }
-  __syncthreads();
-  u64* raw = D.tmp + s_cnt[1];
-  u64* srt = D.sorted + s_cnt[1];
-  const u64* reg = D.region + (size_t)bin * kDsBinCap;
-  for (int i = tid; i < kDsBinCap; i += 256) raw[i] = reg[i];
-  for (int j = tid; j < n_over; j += 256) {
-    const u64 k = D.over[j];
-    if ((P > 1 ? ds_bin_of(s_split, P, k >> kDsIdxBits) : 0) == bin) raw[atomicAdd(&s_cnt[2], 1)] = k;
-  }
-  __threadfence();
-  __syncthreads();
-  for (int i = tid; i < m; i += 256) {
-    const u64 k = raw[i];
-    int rank = 0;
-    for (int j = 0; j < m; j++) rank += raw[j] < k ? 1 : 0;
-    srt[rank] = k;
-  }
-  __threadfence();
-  __syncthreads();
-  ds_reduce_sorted<false>(srt, m, bin, P, pts, stack, D, fr, kind, gen, s_cnt, s_big);
-  }   // next ticket
-}
-
 // ---------------------------------------------------------------------------------------------- data association
-__device__ __forceinline__ void lds_sync_wave() {
-  __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
-  __builtin_amdgcn_wave_barrier();
-}
-
 // Largest two eigenvalues + unit eigenvector of the largest, of a symmetric 3x3 (the only outputs LM:500-506 uses of
 // Eigen::SelfAdjointEigenSolver).  Closed form (trigonometric solution of the characteristic cubic; eigenvector from the
 // best-conditioned cross product of two rows of A - lambda I): ~2 us of dependent f64 latency instead of ~25 us for the
@@ -895,13 +510,13 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(5))) void k
 #define VL_MAP_CAP_PARAM
 #define VL_MAP_SURF_CAP kStackCapSurf
 #define VL_MAP_FACTOR_CAP kMapFactorCap
-#include "map_kernels_capped.inc"
+#include "map_prepare_fit.inc.h"
 #define VL_MAP_TIER 1
 #define VL_MAP_KERNEL(name) name##_tier
 #define VL_MAP_CAP_PARAM , int surf_cap
 #define VL_MAP_SURF_CAP surf_cap
 #define VL_MAP_FACTOR_CAP F.cap
-#include "map_kernels_capped.inc"
+#include "map_prepare_fit.inc.h"
 
 // ---------------------------------------------------------------------------------------------- update / insert / finalize
 // transformUpdate + the map half of the trajectory row; done by one lane of k_map_insert (nothing else in that launch reads
@@ -1215,13 +830,6 @@ __global__ __launch_bounds__(256) void k_map_rebuild_insert(VoxelTable T, const 
   }
 }
 
-__global__ void k_map_register(const float4* __restrict__ cloud, const FrameScalars* __restrict__ S, const MapState* __restrict__ ms,
-                               float4* __restrict__ out) {
-  const int n = S->N2;
-  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x)
-    out[i] = associate_to_map(cloud[i], ms->parameters, ms->parameters + 4);  // LM:795-799
-}
-
 // ---------------------------------------------------------------------------------------------- host side
 vloam_status map_layout(MapContext* m, const vloam_config& cfg, Arena& A) {
   bool ok = true;
@@ -1295,21 +903,6 @@ vloam_status map_init(MapContext* m, hipStream_t st) {
   init.cenW = 10; init.cenH = 10; init.cenD = 5;                                      // laser_mapping.h:76-78
   if (hipMemcpyAsync(m->state, &init, sizeof(init), hipMemcpyHostToDevice, st) != hipSuccess) return VLOAM_ERR_HIP;
   return hipStreamSynchronize(st) == hipSuccess ? VLOAM_OK : VLOAM_ERR_HIP;
-}
-
-// pcl::VoxelGrid of this sweep's lessSharp / lessFlat clouds (LM:432-440) -> stack set `set`.  Needs nothing but the scan
-// registration output, so it is enqueued on the scan-registration stream, ahead of the mapping stage that consumes it.
-vloam_status map_stack_enqueue(MapContext* m, hipStream_t st, const SRBuffers& cur, int set, ProfHook* ph, hipEvent_t done) {
-  StackInfo* si = m->stack_info[set];
-  const unsigned Z = (unsigned)m->se.B;
-  const size_t ss = m->se.ss;
-  m->ds_gen++;   // tags the per-bin cell counts of this sweep's reduce pass (look-back words are never reset)
-  VLOAM_LAUNCH(ph, kKMapStack, st, k_map_ds_bin, dim3(32, 2, Z), dim3(256), 0, st, cur.less_sharp, cur.less_flat, cur.S, m->ds[0], m->ds[1],
-               m->inv_leaf[0], m->inv_leaf[1], m->stack_sets[set][0], m->stack_sets[set][1], si, ss);
-  // `done` (the stack of this sweep is complete) is bound to the last dispatch instead of a marker packet behind it
-  VLOAM_LAUNCH_EV(ph, kKMapDsReduce, st, done, k_map_ds_reduce, dim3(kDsReduceGrid, 2, Z), dim3(256), 0, st, cur.less_sharp, cur.less_flat, cur.S, m->ds[0], m->ds[1],
-                  m->inv_leaf[0], m->inv_leaf[1], m->stack_sets[set][0], m->stack_sets[set][1], si, m->ds_gen, ss);
-  return hipGetLastError() == hipSuccess ? VLOAM_OK : VLOAM_ERR_HIP;
 }
 
 void map_destroy(MapContext* m) {
@@ -1416,385 +1009,6 @@ vloam_status map_enqueue(MapContext* m, const vloam_config& cfg, hipStream_t st,
 #undef VL_FINALIZE
   if (m->grow) map_grow_progress_enqueue(m, st);
   return hipGetLastError() == hipSuccess ? VLOAM_OK : VLOAM_ERR_HIP;
-}
-
-// ---------------------------------------------------------------------------------------------- map export
-// /laser_cloud_map (LM:778-793): for cube index 0..4850 the corner cloud then the surf cloud of the cube.  A cube cloud that has been
-// through its VoxelGrid re-filter (every cube that was ever valid) is ordered by voxel (iz, iy, ix); points that arrived while the cube
-// was outside the valid block follow un-merged, in arrival order (sweep, then stack order) — the raw point records of k_map_finalize; a
-// centroid that became raw point number one (stamp 0) keeps its place in the voxel-ordered part.  The device compacts the live records
-// with their order key; the final ordering of this OUTPUT path is a host sort of the compacted list.
-struct ExportRow { u64 okey; float x, y, z, w; };
-__global__ __launch_bounds__(256) void k_map_export(VoxelTable T, const MapState* __restrict__ ms, int kind, ExportRow* __restrict__ out, long long cap,
-                                                    unsigned long long* n_out) {
-  const int cW = ms->cenW, cH = ms->cenH, cD = ms->cenD;
-  for (unsigned s = blockIdx.x * 256 + threadIdx.x; s <= T.mask; s += gridDim.x * 256) {
-    const RecVal v = rec_load(&T.rec[s]);
-    if (v.key == 0ull || v.count == 0) continue;
-    const int seq = key_seq(v.key);
-    if (seq == 0 && rec_raw(v.count)) continue;   // a raw voxel is published through its point records
-    int Ai, Aj, Ak;
-    unpack_cube(v.key, &Ai, &Aj, &Ak);
-    const int i = Ai + cW, j = Aj + cH, k = Ak + cD;
-    if (i < 0 || i >= kCubeW || j < 0 || j >= kCubeH || k < 0 || k >= kCubeD) continue;
-    const u64 cube = (u64)(i + kCubeW * j + kCubeW * kCubeH * k);
-    const u64 lx = (u64)key_lx(v.key), ly = (u64)key_ly(v.key), lz = (u64)key_lz(v.key);
-    const bool tail = seq != 0 && v.pend_cnt != 0;   // an un-merged arrival: behind the voxel-ordered part, by arrival stamp
-    ExportRow r;
-    r.okey = (cube << 50) | ((u64)kind << 49) | ((u64)(tail ? 1 : 0) << 48) | (tail ? (u64)(unsigned)v.pend_cnt : ((lz << (2 * kVoxBits)) | (ly << kVoxBits) | lx));
-    const int n = seq ? 1 : rec_n(v.count);
-    const float nn = (float)n;
-    r.x = n > 1 ? v.sum.x / nn : v.sum.x; r.y = n > 1 ? v.sum.y / nn : v.sum.y; r.z = n > 1 ? v.sum.z / nn : v.sum.z;
-    r.w = n > 1 ? v.sum.w / nn : v.sum.w;
-    const unsigned long long o = atomicAdd(n_out, 1ull);
-    if ((long long)o < cap) out[o] = r;
-  }
-}
-
-// kinds: bit 0 the corner clouds, bit 1 the surf clouds
-static vloam_status map_export_kinds(MapContext* m0, hipStream_t st, int kinds, float* xyzi4, long long cap, long long* n) {
-  const MapContext msel = m0->for_session(m0->sel);
-  const MapContext* m = &msel;
-  if (hipStreamSynchronize(st) != hipSuccess) return VLOAM_ERR_HIP;
-  int stats[2][4];
-  for (int k = 0; k < 2; k++) if (hipMemcpy(stats[k], m->tab[k].stats, sizeof(stats[k]), hipMemcpyDeviceToHost) != hipSuccess) return VLOAM_ERR_HIP;
-  const long long bound = (long long)stats[0][0] + stats[1][0] + 1;  // keys ever inserted >= live voxels
-  ExportRow* d_rows = nullptr;
-  unsigned long long* d_n = nullptr;
-  if (hipMalloc((void**)&d_rows, (size_t)bound * sizeof(ExportRow)) != hipSuccess || hipMalloc((void**)&d_n, sizeof(*d_n)) != hipSuccess) return VLOAM_ERR_HIP;
-  vloam_status rc = VLOAM_OK;
-  unsigned long long cnt = 0;
-  if (hipMemsetAsync(d_n, 0, sizeof(*d_n), st) != hipSuccess) rc = VLOAM_ERR_HIP;
-  for (int k = 0; k < 2 && rc == VLOAM_OK; k++) if ((kinds >> k) & 1) VL_RAW_LAUNCH(k_map_export, dim3(1024), dim3(256), 0, st, m->tab[k], m->state, k, d_rows, bound, d_n);
-  if (rc == VLOAM_OK && (hipStreamSynchronize(st) != hipSuccess || hipMemcpy(&cnt, d_n, sizeof(cnt), hipMemcpyDeviceToHost) != hipSuccess)) rc = VLOAM_ERR_HIP;
-  std::vector<ExportRow> rows((size_t)((long long)cnt < bound ? (long long)cnt : bound));
-  if (rc == VLOAM_OK && !rows.empty() && hipMemcpy(rows.data(), d_rows, rows.size() * sizeof(ExportRow), hipMemcpyDeviceToHost) != hipSuccess) rc = VLOAM_ERR_HIP;
-  (void)hipFree(d_rows); (void)hipFree(d_n);
-  if (rc != VLOAM_OK) return rc;
-  std::sort(rows.begin(), rows.end(), [](const ExportRow& a, const ExportRow& b) { return a.okey < b.okey; });
-  if (n) *n = (long long)rows.size();
-  const long long c = (long long)rows.size() < cap ? (long long)rows.size() : cap;
-  for (long long i = 0; xyzi4 && i < c; i++) { xyzi4[4 * i] = rows[(size_t)i].x; xyzi4[4 * i + 1] = rows[(size_t)i].y; xyzi4[4 * i + 2] = rows[(size_t)i].z; xyzi4[4 * i + 3] = rows[(size_t)i].w; }
-  return VLOAM_OK;
-}
-
-vloam_status map_export(MapContext* m, hipStream_t st, float* xyzi4, long long cap, long long* n) { return map_export_kinds(m, st, 3, xyzi4, cap, n); }
-vloam_status map_export_kind(MapContext* m, hipStream_t st, int kind, float* xyzi4, long long cap, long long* n) { return map_export_kinds(m, st, 1 << kind, xyzi4, cap, n); }
-
-vloam_status map_get_cloud(MapContext* m0, hipStream_t st, int which, const SRBuffers& cur, float* xyzi4, int cap, int* n) {
-  // `cur` is already the selected session's buffer set (the caller rebased it)
-  const MapContext msel = m0->for_session(m0->sel);
-  const MapContext* m = &msel;
-  if (hipStreamSynchronize(st) != hipSuccess) return VLOAM_ERR_HIP;
-  MapState ms;
-  if (hipMemcpy(&ms, m->state, sizeof(ms), hipMemcpyDeviceToHost) != hipSuccess) return VLOAM_ERR_HIP;
-  const float4* src = nullptr;
-  int cnt = 0;
-  if (which == 7) { src = m->stack[0]; cnt = ms.n_corner_stack; }
-  else if (which == 8) { src = m->stack[1]; cnt = ms.n_surf_stack; }
-  else if (which == 11) {
-    FrameScalars S;
-    if (hipMemcpy(&S, cur.S, sizeof(S), hipMemcpyDeviceToHost) != hipSuccess) return VLOAM_ERR_HIP;
-    VL_RAW_LAUNCH(k_map_register, dim3(256), dim3(256), 0, st, cur.cloud, cur.S, m->state, m->registered);
-    if (hipStreamSynchronize(st) != hipSuccess) return VLOAM_ERR_HIP;
-    src = m->registered; cnt = S.N2;
-  } else return VLOAM_ERR_INVALID;
-  *n = cnt;
-  const int c = cnt < cap ? cnt : cap;
-  if (xyzi4 && c > 0 && hipMemcpy(xyzi4, src, (size_t)c * sizeof(float4), hipMemcpyDeviceToHost) != hipSuccess) return VLOAM_ERR_HIP;
-  return VLOAM_OK;
-}
-
-// ---------------------------------------------------------------------------------------------- published clouds (MapPub, map_kernels.h)
-// /laser_cloud_map ordered on the device, on the mapping stream, behind k_map_finalize of the publishing sweep.  The order key is
-// k_map_export's: | cube 13 | kind 1 | tail 1 | 16 zero bits | voxel (lz, ly, lx) or arrival stamp, 32 |; its top 14 bits name the bucket.
-//   k_map_pub_count    both tables: live records per bucket
-//   k_map_pub_scan     exclusive scan of the 9 702 counts, the publication's header (count, overflow), cursors cleared
-//   k_map_pub_scatter  both tables again: every record into its bucket's segment (place inside the segment: arrival, fixed up next)
-//   k_map_pub_sort     one workgroup per bucket: segments of up to kPubLdsKeys records ordered in LDS (bitonic.h), points written out
-//   k_map_pub_rank     the longer segments: a record's place is the number of smaller keys in its segment
-// Keys are unique (one record per cube, kind and voxel, one per arrival stamp), so the result is the host sort's of map_export, byte for byte.
-// A publication that does not fit the capacity writes the header only.
-__device__ __forceinline__ bool pub_row(const RecVal& v, int cW, int cH, int cD, int kind, u64* okey, float4* p) {
-  if (v.key == 0ull || v.count == 0) return false;
-  const int seq = key_seq(v.key);
-  if (seq == 0 && rec_raw(v.count)) return false;   // a raw voxel is published through its point records
-  int Ai, Aj, Ak;
-  unpack_cube(v.key, &Ai, &Aj, &Ak);
-  const int i = Ai + cW, j = Aj + cH, k = Ak + cD;
-  if (i < 0 || i >= kCubeW || j < 0 || j >= kCubeH || k < 0 || k >= kCubeD) return false;
-  const u64 cube = (u64)(i + kCubeW * j + kCubeW * kCubeH * k);
-  const u64 lx = (u64)key_lx(v.key), ly = (u64)key_ly(v.key), lz = (u64)key_lz(v.key);
-  const bool tail = seq != 0 && v.pend_cnt != 0;
-  *okey = (cube << 50) | ((u64)kind << 49) | ((u64)(tail ? 1 : 0) << 48) | (tail ? (u64)(unsigned)v.pend_cnt : ((lz << (2 * kVoxBits)) | (ly << kVoxBits) | lx));
-  const int n = seq ? 1 : rec_n(v.count);
-  const float nn = (float)n;
-  p->x = n > 1 ? v.sum.x / nn : v.sum.x; p->y = n > 1 ? v.sum.y / nn : v.sum.y; p->z = n > 1 ? v.sum.z / nn : v.sum.z;
-  p->w = n > 1 ? v.sum.w / nn : v.sum.w;
-  return true;
-}
-__device__ __forceinline__ int pub_bucket(u64 okey) { return (int)(okey >> 49); }   // cube * 2 + kind < kPubBuckets
-
-__global__ __launch_bounds__(256) void k_map_pub_count(VoxelTable T0, VoxelTable T1, const MapState* __restrict__ ms, int* __restrict__ cnt, size_t ss) {
-  VL_SESSION(ss); T0.rebase(so_); T1.rebase(so_); RB(ms); RB(cnt);
-  const int kind = blockIdx.y;
-  const VoxelTable& T = kind ? T1 : T0;
-  const int cW = ms->cenW, cH = ms->cenH, cD = ms->cenD;
-  for (unsigned s = blockIdx.x * 256 + threadIdx.x; s <= T.mask; s += gridDim.x * 256) {
-    const RecVal v = rec_load(&T.rec[s]);
-    u64 okey; float4 p;
-    if (pub_row(v, cW, cH, cD, kind, &okey, &p)) atomicAdd(&cnt[pub_bucket(okey)], 1);
-  }
-}
-
-constexpr int kPubScanPer = (kPubBuckets + 255) / 256;   // buckets per thread of the one-workgroup scan
-__global__ __launch_bounds__(256) void k_map_pub_scan(const int* __restrict__ cnt, int* __restrict__ off, int* __restrict__ cur, PubHeader* __restrict__ hdr,
-                                                      long long cap, size_t ss) {
-  VL_SESSION(ss); RB(cnt); RB(off); RB(cur); RB(hdr);
-  __shared__ int part[256];
-  const int tid = threadIdx.x, b0 = tid * kPubScanPer;
-  int sum = 0;
-  for (int e = 0; e < kPubScanPer; e++) if (b0 + e < kPubBuckets) sum += cnt[b0 + e];
-  part[tid] = sum;
-  __syncthreads();
-  for (int d = 1; d < 256; d <<= 1) {   // inclusive scan of the 256 partial sums
-    const int add = tid >= d ? part[tid - d] : 0;
-    __syncthreads();
-    part[tid] += add;
-    __syncthreads();
-  }
-  int run = part[tid] - sum;
-  for (int e = 0; e < kPubScanPer; e++)
-    if (b0 + e < kPubBuckets) { off[b0 + e] = run; cur[b0 + e] = 0; run += cnt[b0 + e]; }
-  if (tid == 255) {
-    const int total = part[255];
-    off[kPubBuckets] = total;
-    hdr->n = (long long)total;
-    hdr->overflow = (long long)total > cap ? 1 : 0;
-  }
-}
-
-__global__ __launch_bounds__(256) void k_map_pub_scatter(VoxelTable T0, VoxelTable T1, const MapState* __restrict__ ms, const int* __restrict__ off,
-                                                         int* __restrict__ cur, const PubHeader* __restrict__ hdr, u64* __restrict__ keys,
-                                                         float4* __restrict__ vals, long long cap, size_t ss) {
-  VL_SESSION(ss); T0.rebase(so_); T1.rebase(so_); RB(ms); RB(off); RB(cur); RB(hdr); RB(keys); RB(vals);
-  if (hdr->overflow) return;
-  const int kind = blockIdx.y;
-  const VoxelTable& T = kind ? T1 : T0;
-  const int cW = ms->cenW, cH = ms->cenH, cD = ms->cenD;
-  for (unsigned s = blockIdx.x * 256 + threadIdx.x; s <= T.mask; s += gridDim.x * 256) {
-    const RecVal v = rec_load(&T.rec[s]);
-    u64 okey; float4 p;
-    if (!pub_row(v, cW, cH, cD, kind, &okey, &p)) continue;
-    const int b = pub_bucket(okey);
-    const long long pos = (long long)off[b] + atomicAdd(&cur[b], 1);
-    if (pos < cap) { keys[pos] = okey; vals[pos] = p; }   // (always: the tables have not changed since the count)
-  }
-}
-
-constexpr int kPubIdxBits = 13;   // a record's index inside its segment rides in the low bits of the LDS sort key
-static_assert(kPubLdsKeys <= (1 << kPubIdxBits) && 49 + kPubIdxBits <= 63, "key below the bucket bits + index must fit 64 bits under the padding value");
-__global__ __launch_bounds__(256) void k_map_pub_sort(int* __restrict__ cnt, const int* __restrict__ off, const PubHeader* __restrict__ hdr,
-                                                      const u64* __restrict__ keys, const float4* __restrict__ vals, float4* __restrict__ out, long long cap,
-                                                      size_t ss) {
-  VL_SESSION(ss); RB(cnt); RB(off); RB(hdr); RB(keys); RB(vals); RB(out);
-  __shared__ u64 a[kPubLdsKeys];
-  const int b = blockIdx.x, tid = threadIdx.x;
-  const int n = cnt[b], base = off[b];
-  const bool skip = hdr->overflow != 0;
-  __syncthreads();
-  if (tid == 0) cnt[b] = 0;   // ready for the next publication
-  if (skip || n == 0 || n > kPubLdsKeys || (long long)base + n > cap) return;   // longer segments: k_map_pub_rank
-  if (n == 1) { if (tid == 0) out[base] = vals[base]; return; }
-  int P2 = 256;
-  while (P2 < n) P2 <<= 1;
-  for (int e = tid; e < P2; e += 256)
-    a[e] = e < n ? (((keys[base + e] & ((1ull << 49) - 1)) << kPubIdxBits) | (u64)e) : ~0ull;
-  __syncthreads();
-  block_bitonic_sort_u64(a, P2, tid, 256);
-  for (int e = tid; e < n; e += 256) out[base + e] = vals[base + (int)(a[e] & ((1u << kPubIdxBits) - 1))];
-}
-
-__global__ __launch_bounds__(256) void k_map_pub_rank(const int* __restrict__ off, const PubHeader* __restrict__ hdr, const u64* __restrict__ keys,
-                                                      const float4* __restrict__ vals, float4* __restrict__ out, long long cap, size_t ss) {
-  VL_SESSION(ss); RB(off); RB(hdr); RB(keys); RB(vals); RB(out);
-  if (hdr->overflow) return;
-  const long long total = hdr->n < cap ? hdr->n : cap;
-  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
-    const u64 key = keys[i];
-    const int b = pub_bucket(key);
-    const int lo = off[b], hi = off[b + 1];
-    if (hi - lo <= kPubLdsKeys) continue;   // k_map_pub_sort wrote it
-    int r = 0;
-    for (int j = lo; j < hi; j++) r += keys[j] < key ? 1 : 0;
-    out[lo + r] = vals[i];
-  }
-}
-
-bool map_publishes(const MapContext* m, bool skip_frame) {
-  const MapPub& P = m->pub;
-  if (P.cloud_on) return true;
-  // LM:778 with frameCount == MapState::sweep_no after this sweep's increment; a skipped sweep leaves the last publication current
-  return P.pub_number > 0 && !skip_frame && P.due(P.mapped + 1);
-}
-
-vloam_status map_publish_enqueue(MapContext* m, hipStream_t st, const float4* cloud, const FrameScalars* S, int frame, bool skip_frame, ProfHook* ph,
-                                 hipEvent_t done) {
-  MapPub& P = m->pub;
-  const unsigned Z = (unsigned)m->se.B;
-  const size_t ss = m->se.ss;
-  if (P.cloud_on) {
-    const int slot = P.cloud_seq & 1;
-    for (int b = 0; b < m->se.B; b++) {   // k_map_register as vloam_get_features(h, 11) launches it, once per session
-      const size_t o = (size_t)b * ss;
-      const float4* c = cloud; const FrameScalars* Sb = S; const MapState* msb = m->state; float4* dst = P.cloud[slot]; int* nb = P.cloud_n[slot];
-      rbp(c, o); rbp(Sb, o); rbp(msb, o); rbp(dst, o); rbp(nb, o);
-      VLOAM_LAUNCH(ph, kKMapRegister, st, k_map_register, dim3(256), dim3(256), 0, st, c, Sb, msb, dst);
-      if (hipMemcpyAsync(nb, &Sb->N2, sizeof(int), hipMemcpyDeviceToDevice, st) != hipSuccess) return VLOAM_ERR_HIP;
-    }
-    if (hipEventRecord(P.ev_cloud[slot], st) != hipSuccess) return VLOAM_ERR_HIP;
-    P.cloud_frame[slot] = frame;
-    P.cloud_seq++;
-  }
-  if (done && hipEventRecord(done, st) != hipSuccess) return VLOAM_ERR_HIP;   // the sweep's buffer set is free once k_map_register has read it
-  if (P.pub_number > 0 && !skip_frame && P.due(P.mapped)) {   // (map_enqueue has counted the sweep)
-    const int slot = P.map_seq & 1;
-    VLOAM_LAUNCH(ph, kKMapPubCount, st, k_map_pub_count, dim3(1024, 2, Z), dim3(256), 0, st, m->tab[0], m->tab[1], m->state, P.cnt, ss);
-    VLOAM_LAUNCH(ph, kKMapPubScan, st, k_map_pub_scan, dim3(1, 1, Z), dim3(256), 0, st, P.cnt, P.off, P.cur, P.hdr[slot], P.cap, ss);
-    VLOAM_LAUNCH(ph, kKMapPubScatter, st, k_map_pub_scatter, dim3(1024, 2, Z), dim3(256), 0, st, m->tab[0], m->tab[1], m->state, P.off, P.cur, P.hdr[slot],
-                 P.keys, P.vals, P.cap, ss);
-    VLOAM_LAUNCH(ph, kKMapPubSort, st, k_map_pub_sort, dim3(kPubBuckets, 1, Z), dim3(256), 0, st, P.cnt, P.off, P.hdr[slot], P.keys, P.vals, P.out[slot], P.cap, ss);
-    VLOAM_LAUNCH(ph, kKMapPubRank, st, k_map_pub_rank, dim3(1024, 1, Z), dim3(256), 0, st, P.off, P.hdr[slot], P.keys, P.vals, P.out[slot], P.cap, ss);
-    if (hipEventRecord(P.ev_map[slot], st) != hipSuccess) return VLOAM_ERR_HIP;
-    P.map_frame[slot] = frame;
-    P.map_seq++;
-  }
-  return hipGetLastError() == hipSuccess ? VLOAM_OK : VLOAM_ERR_HIP;
-}
-
-vloam_status map_published_get(MapContext* m0, int which, float* xyzi4, long long cap, long long* n, int* frame, void** d_ptr) {
-  const MapContext msel = m0->for_session(m0->sel);
-  const MapPub& P = msel.pub;
-  const int seq = which == 0 ? P.map_seq : P.cloud_seq;
-  *n = 0; *frame = -1;
-  if (d_ptr) *d_ptr = nullptr;
-  if (seq == 0) return VLOAM_OK;   // nothing published yet
-  const int slot = (seq - 1) & 1;
-  if (hipEventSynchronize(which == 0 ? P.ev_map[slot] : P.ev_cloud[slot]) != hipSuccess) return VLOAM_ERR_HIP;
-  *frame = which == 0 ? P.map_frame[slot] : P.cloud_frame[slot];
-  const float4* src = nullptr;
-  if (which == 0) {
-    PubHeader hd;
-    if (hipMemcpy(&hd, P.hdr[slot], sizeof(hd), hipMemcpyDeviceToHost) != hipSuccess) return VLOAM_ERR_HIP;
-    *n = hd.n;
-    if (hd.overflow) return VLOAM_ERR_CAPACITY;
-    src = P.out[slot];
-  } else {
-    int cnt = 0;
-    if (hipMemcpy(&cnt, P.cloud_n[slot], sizeof(cnt), hipMemcpyDeviceToHost) != hipSuccess) return VLOAM_ERR_HIP;
-    *n = cnt;
-    src = P.cloud[slot];
-  }
-  if (d_ptr) *d_ptr = (void*)src;
-  const long long c = *n < cap ? *n : cap;
-  if (xyzi4 && c > 0 && hipMemcpy(xyzi4, src, (size_t)c * sizeof(float4), hipMemcpyDeviceToHost) != hipSuccess) return VLOAM_ERR_HIP;
-  return VLOAM_OK;
-}
-
-__global__ void k_map_error_fetch(MapFrame* fr, int clear_mask, int* out) { out[0] = atomicAnd(&fr->error, ~clear_mask); out[1] = fr->fallback_solves; }
-
-// the sticky error words of all sessions OR-ed; the bits of clear_mask are reported once and cleared (transient per-sweep conditions)
-vloam_status map_error(MapContext* m, int* e, int clear_mask, long long* fallback_solves) {
-  *e = 0;
-  if (fallback_solves) *fallback_solves = 0;
-  for (int b = 0; b < m->se.B; b++) {
-    const MapContext mb = m->for_session(b);
-    int* d_out = mb.rebuild_n;  // scratch ints (no rebuild can be in flight: the caller has synchronised the streams)
-    VL_RAW_LAUNCH(k_map_error_fetch, dim3(1), dim3(1), 0, 0, mb.frame, clear_mask, d_out);
-    int v[2] = {0, 0};
-    if (hipMemcpy(v, d_out, sizeof(v), hipMemcpyDeviceToHost) != hipSuccess) return VLOAM_ERR_HIP;
-    *e |= v[0];
-    if (fallback_solves) *fallback_solves += v[1];
-  }
-  return VLOAM_OK;
-}
-
-static vloam_status copy_dev(const void* src, size_t bytes, void* buf, long long cap, long long* n) {
-  if (n) *n = (long long)bytes;
-  const size_t c = bytes < (size_t)cap ? bytes : (size_t)cap;
-  if (buf && c && hipMemcpy(buf, src, c, hipMemcpyDeviceToHost) != hipSuccess) return VLOAM_ERR_HIP;
-  return VLOAM_OK;
-}
-
-// item = outer * 16 + k:  k = 0 factor types i32[cap = 8 192 + the surf capacity], 1 A f64[3][cap], 2 B f64[3][cap], 3 LM record, 4 residuals f64[3][cap],
-//                         5 p f64[3][cap].  item 64: MapState.  item 65: MapFrame.  item 66: cube_cnt i32[2][4851].
-//                         item 67/68: dump of the corner / surf table as rows {key lo, key hi, count, x, y, z, w} (7 x 4 bytes) for live slots.
-vloam_status map_debug_get(MapContext* m0, int item, void* buf, long long cap, long long* n) {
-  const MapContext msel = m0->for_session(m0->sel);
-  const MapContext* m = &msel;
-  if (item == 64) return copy_dev(m->state, sizeof(MapState), buf, cap, n);
-  if (item == 65) return copy_dev(m->frame, sizeof(MapFrame), buf, cap, n);
-  if (item == 66) return copy_dev(m->cube_cnt, sizeof(int) * 2 * kCubeNum, buf, cap, n);
-  if (item == 67 || item == 68) {
-    const VoxelTable& T = m->tab[item - 67];
-    const size_t slots = (size_t)T.mask + 1;
-    std::vector<VoxelRec> recs(slots);
-    if (hipMemcpy(recs.data(), T.rec, slots * sizeof(VoxelRec), hipMemcpyDeviceToHost) != hipSuccess) return VLOAM_ERR_HIP;
-    std::vector<unsigned> rows;
-    for (size_t s = 0; s < slots; s++) {
-      if (recs[s].key == 0 || recs[s].count == 0) continue;
-      if ((recs[s].key >> 56) == 0 && (recs[s].count & (1 << 30))) continue;   // a raw voxel shows up as its point records (seq != 0)
-      unsigned r[7];
-      r[0] = (unsigned)(recs[s].key & 0xffffffffu); r[1] = (unsigned)(recs[s].key >> 32); r[2] = (unsigned)recs[s].count;
-      memcpy(r + 3, &recs[s].sx, 16);
-      rows.insert(rows.end(), r, r + 7);
-    }
-    if (n) *n = (long long)(rows.size() * 4);
-    const size_t c = rows.size() * 4 < (size_t)cap ? rows.size() * 4 : (size_t)cap;
-    if (buf && c) memcpy(buf, rows.data(), c);
-    return VLOAM_OK;
-  }
-  if (item == 72) return copy_dev(m->ts_log, sizeof(long long) * 2048, buf, cap, n);   // VLOAM_TS_LOG=1: [sweep % 1024][prepare start, finalize start], 100 MHz ticks
-  if (item == 73) return copy_dev(m->cbox, sizeof(int4) * 2 * (size_t)m->factor_cap(), buf, cap, n);   // per stack slot: the first round's search box + its candidate count (-1: not cached)
-  if (item == 71) return copy_dev(m->assoc_cyc, sizeof(long long) * 16, buf, cap, n);   // k_map_assoc phase cycles (debug handles): [outer][6 phases, spare, wavefronts]
-  if (item == 69) {  // table health: {keys, purged, block keys, spare} x {corner, surf}, rebuilds, largest candidate list
-    int out[12] = {0};
-    for (int k = 0; k < 2; k++) if (hipMemcpy(out + 4 * k, m->tab[k].stats, 4 * sizeof(int), hipMemcpyDeviceToHost) != hipSuccess) return VLOAM_ERR_HIP;
-    MapFrame fr;
-    if (hipMemcpy(&fr, m->frame, sizeof(fr), hipMemcpyDeviceToHost) != hipSuccess) return VLOAM_ERR_HIP;
-    out[8] = (int)m0->rebuilds; out[9] = fr.max_candidates; out[10] = fr.n_deferred[0] + fr.n_newraw[0]; out[11] = fr.n_deferred[1] + fr.n_newraw[1];
-    if (n) *n = sizeof(out);
-    if (buf) memcpy(buf, out, (size_t)cap < sizeof(out) ? (size_t)cap : sizeof(out));
-    return VLOAM_OK;
-  }
-  const int outer = item / 16, k = item % 16;
-  if (outer < 0 || outer > 1) return VLOAM_ERR_INVALID;
-  const FactorTable& F = m->F[outer];
-  switch (k) {
-    case 0: return copy_dev(F.type, sizeof(int) * F.cap, buf, cap, n);
-    case 1: return copy_dev(F.A, sizeof(double) * 3 * F.cap, buf, cap, n);
-    case 2: return copy_dev(F.B, sizeof(double) * 3 * F.cap, buf, cap, n);
-    case 3: return copy_dev(m->rec + outer, sizeof(LMRecord), buf, cap, n);
-    case 4: return copy_dev(F.resid, sizeof(double) * 3 * F.cap, buf, cap, n);
-    case 5: return copy_dev(F.p, sizeof(double) * 3 * F.cap, buf, cap, n);
-  }
-  return VLOAM_ERR_INVALID;
-}
-
-vloam_status map_counts(MapContext* m0, long long c[16]) {
-  const MapContext msel = m0->for_session(m0->sel);
-  const MapContext* m = &msel;
-  MapState ms;
-  MapFrame fr;
-  LMRecord rec[2];
-  if (hipMemcpy(&ms, m->state, sizeof(ms), hipMemcpyDeviceToHost) != hipSuccess) return VLOAM_ERR_HIP;
-  if (hipMemcpy(&fr, m->frame, sizeof(fr), hipMemcpyDeviceToHost) != hipSuccess) return VLOAM_ERR_HIP;
-  if (hipMemcpy(rec, m->rec, sizeof(rec), hipMemcpyDeviceToHost) != hipSuccess) return VLOAM_ERR_HIP;
-  c[11] = ms.n_corner_stack; c[12] = ms.n_surf_stack;
-  c[13] = fr.n_factors[1][0] + fr.n_factors[1][1];
-  c[14] = ms.do_optimize ? (long long)(rec[0].n_evals + rec[1].n_evals) : 0;
-  c[15] = ms.n_map_corner + ms.n_map_surf;
-  return VLOAM_OK;
 }
 
 }  // namespace vloam

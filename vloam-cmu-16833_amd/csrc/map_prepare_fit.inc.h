@@ -3,6 +3,7 @@
 //   large tier     VL_MAP_TIER 1: k_map_prepare_tier / k_map_fit_tier take the handle's capacity at run time (vloam_limits::max_surf_stack_points)
 // A textual include instead of a template: inlining a template body perturbs the register allocation of these two kernels' default forms,
 // and the default code objects are to stay register for register what they are (profiles/r07_surf_stack_tier.txt).
+// The name ends in .h because the Makefile's HDRS wildcard and the content hash of csrc/ (tools/pmc_summary.py) both go by suffix.
 //   VL_MAP_KERNEL(name)  the kernel's name          VL_MAP_CAP_PARAM   the trailing parameter of the tier form (or nothing)
 //   VL_MAP_SURF_CAP      surf stack capacity        VL_MAP_FACTOR_CAP  slots of the factor table: 8 192 corner + the surf capacity
 

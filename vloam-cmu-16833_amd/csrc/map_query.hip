@@ -26,7 +26,7 @@ constexpr unsigned kQNone = 0xffffffffu;
 
 struct QPoint { float4 p; u64 okey; };
 
-// the point a live record stands for and its place in vloam_get_map's order: k_map_export's arithmetic (map_kernels.hip)
+// the point a live record stands for and its place in vloam_get_map's order: k_map_export's arithmetic (map_output.hip)
 __device__ __forceinline__ QPoint q_point(const RecVal& v, int wi, int wj, int wk, int kind) {
   const int seq = key_seq(v.key);
   const u64 cube = (u64)(wi + kCubeW * wj + kCubeW * kCubeH * wk);

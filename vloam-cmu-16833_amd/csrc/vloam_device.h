@@ -6,6 +6,7 @@
 #include <hip/hip_ext.h>
 #include <math.h>
 #include <stdint.h>
+#include "../../include/vloam_hip/c_api.h"
 
 namespace vloam {
 
@@ -128,6 +129,15 @@ extern int g_vl_plain_events;   // VLOAM_PLAIN_EVENTS=1 (A/B switch): a marker p
     if ((stop_ev) && ::vloam::g_vl_plain_events) (void)hipEventRecord((stop_ev), (stream));                 \
     if (prof_) (ph)->end((st));                                                                             \
   } while (0)
+
+// device -> host copy behind the debug getters: *n = the item's size in bytes, the first min(bytes, cap) of them land in buf (may be null).
+// static: the library exports no symbol for it, as with the per-file copies it replaces
+static inline vloam_status copy_dev(const void* src, size_t bytes, void* buf, long long cap, long long* n) {
+  if (n) *n = (long long)bytes;
+  const size_t c = bytes < (size_t)cap ? bytes : (size_t)cap;
+  if (buf && c && hipMemcpy(buf, src, c, hipMemcpyDeviceToHost) != hipSuccess) return VLOAM_ERR_HIP;
+  return VLOAM_OK;
+}
 
 enum ErrorBits : int {
   kErrEmpty = 1,       // no point survived S1

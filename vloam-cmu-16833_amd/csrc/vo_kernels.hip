@@ -392,13 +392,6 @@ vloam_status vo_solve(VOContext* v, const vloam_config& cfg, hipStream_t st, con
   return VLOAM_OK;
 }
 
-static vloam_status copy_dev(const void* src, size_t bytes, void* buf, long long cap, long long* n) {
-  if (n) *n = (long long)bytes;
-  const size_t c = bytes < (size_t)cap ? bytes : (size_t)cap;
-  if (buf && c && hipMemcpy(buf, src, c, hipMemcpyDeviceToHost) != hipSuccess) return VLOAM_ERR_HIP;
-  return VLOAM_OK;
-}
-
 // item 0..3: bucket_x / bucket_y / bucket_depth / bucket_count of the CURRENT map; 4..7 the same of the PREVIOUS map;
 // 8: per-match rows f64[n][7]; 9: LM record; 10: projected points f32[n][4] (u, v, depth, bucket id bits)
 vloam_status vo_debug_get(VOContext* v, int item, void* buf, long long cap, long long* n) {
