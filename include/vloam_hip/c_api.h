@@ -376,8 +376,8 @@ vloam_status vloam_sweep_log_device_ptr(vloam_handle* h, void** d_rows, long lon
  * skipped by mapping_skip_frame, when "Map corner and surf num are not enough" (laser_mapping.cpp:448), and on a handle without mapping.
  * Rows do NOT travel in a checkpoint: after vloam_checkpoint_load into an enabled handle the restored sweeps read frame == -1, later sweeps
  * are written normally.
- * Not provided: the matrix of the VO solve (angle-axis problem); eigenvectors; the inversion to a covariance (INTEGRATION.md §5 has the host
- * lines: sigma^2 H^-1 with sigma^2 = 2 cost / (residual rows - 6), residual rows = 3 edge blocks + plane blocks). */
+ * Not in this record: the matrix of the VO solve (angle-axis problem), the eigenvectors and the inversion to a covariance.  They are the rows of
+ * vloam_pose_cov_enable below (vloam_get_pose_cov), an add-on of this product that leaves these 832 bytes bit for bit what they are. */
 typedef struct vloam_pose_info_options {
   int struct_size;              /* sizeof(vloam_pose_info_options) as compiled */
   int reserved;                 /* 0 */
@@ -417,6 +417,70 @@ _Static_assert(sizeof(vloam_pose_info_record) == 832, "vloam_pose_info_record is
 vloam_status vloam_pose_info_enable(vloam_handle* h, const vloam_pose_info_options* opt);
 vloam_status vloam_get_pose_info(vloam_handle* h, int first, int count, vloam_pose_info_record* out);
 vloam_status vloam_pose_info_device_ptr(vloam_handle* h, void** d_rows, long long* bytes);
+
+/* == Per-sweep pose covariance rows (vloam_pose_cov_enable): eigenvectors, covariances and the VO solve's matrix.  An add-on of the pose
+ * information product for callers that feed the poses to a filter or a pose graph, or that want to know WHICH direction a degenerate sweep
+ * left unobserved.  For every sweep and session one fixed-size record holds, for the laser odometry, the mapping and the VO solve:
+ *   eig, V   the eigen-decomposition of the stage's information matrix H (lo_H / map_H of the pose information row; vo_H here): eig ascending,
+ *            column i of V (row-major, V[r * 6 + i]) belongs to eig[i]; in every column the component of largest magnitude is positive (ties:
+ *            the lowest row), so rows are bit-identical from run to run.  f64 cyclic Jacobi on one wavefront, the three disjoint rotations of
+ *            a round-robin step on different lanes at once, to the stopping rule of the pose information rows' eigenvalues.
+ *   rank     eigenvalues kept by the pseudo-inverse: lambda >= max(the stage's threshold, 1e-12 lambda_max) and lambda > 0; *_TRUNCATED when < 6.
+ *   sigma2   2 cost / (residual rows - rank); residual rows = 3 edge + plane blocks (odometry), 3 corner + surf blocks (mapping),
+ *            2 CostFunctor32 + CostFunctor22 blocks (VO).
+ *   cov      sigma2 * sum over the kept eigenvalues of v v^T / lambda, row-major, in the parameters of H: (delta theta, delta t) of
+ *            EigenQuaternionParameterization for the LiDAR stages, (angle-axis, t) of cam0_curr_T_cam0_last for the VO.
+ * The LiDAR halves are written by ONE one-wavefront launch per stage on the stage's own stream directly behind the pose information launch of
+ * the same sweep, from the H, cost and counts that launch just wrote (no second walk over the factors).  *_VALID mirrors the pose information
+ * row's valid bit; a half whose bit is clear there is all zero.
+ * The VO half is written by the frame entry points (vloam_process_frame*, vloam_process_frame_image*, and the batch forms) on the stream that ran
+ * the VO solve, behind it: vo_x = the returned (angles_0to1, t_0to1), vo_H = sum rho' J^T J (Huber 0.1, as solveNlsAll) over the residual blocks
+ * the solve consumed, at vo_x, in that problem's own 6 parameters; vo_cost = 0.5 sum rho there; vo_factors = counter32, counter22.  VO_VALID is
+ * clear and the half is zero on the first frame, on sweeps driven by vloam_process_scan* or the stage-wise calls, and when the estimate is not
+ * finite or its rotation angle is zero (the case in which the reference's transform is NaN, visual_odometry.cpp:427-430).  The stage-wise
+ * vloam_vo_solve does NOT write rows.
+ * When residual rows - rank <= 0 there is no redundancy to estimate sigma2 from: sigma2 and cov are zero and *_VALID is clear, while eig, V,
+ * rank and *_TRUNCATED (and vo_x, vo_cost, vo_H, vo_factors) still describe the problem -- a frame with a handful of VO features shows here.
+ * No floating-point atomics anywhere; poses, map and the 832-byte rows are those of a handle with pose information alone.  Rows do NOT travel in
+ * a checkpoint (restored sweeps read frame == -1).  Not provided: propagation of the covariance along the trajectory. */
+typedef struct vloam_pose_cov_options {
+  int struct_size;              /* sizeof(vloam_pose_cov_options) as compiled */
+  int reserved;                 /* 0 */
+  double lo_min_eigenvalue;     /* eigenvalues below this are treated as unobserved in the pseudo-inverse; 0 = only lambda <= 1e-12 * lambda_max */
+  double map_min_eigenvalue;
+  double vo_min_eigenvalue;
+} vloam_pose_cov_options;
+void vloam_default_pose_cov_options(vloam_pose_cov_options* opt);   /* struct_size set, thresholds 0 */
+enum {   /* vloam_pose_cov_record::flags */
+  VLOAM_POSE_COV_LO_VALID = 1, VLOAM_POSE_COV_MAP_VALID = 2, VLOAM_POSE_COV_VO_VALID = 4,           /* sigma2 and cov of that stage are set */
+  VLOAM_POSE_COV_LO_TRUNCATED = 8, VLOAM_POSE_COV_MAP_TRUNCATED = 16, VLOAM_POSE_COV_VO_TRUNCATED = 32   /* rank < 6 */
+};
+typedef struct vloam_pose_cov_record {
+  int frame;                    /* 0-based sweep index; -1 while the row has not been completed */
+  int flags;                    /* VLOAM_POSE_COV_* */
+  int rank[3];                  /* lo, map, vo: eigenvalues kept */
+  int vo_factors[2];            /* counter32, counter22 residual blocks of the VO solve */
+  int reserved;
+  double sigma2[3], reserved_d;
+  double lo_eig[6], lo_V[36], lo_cov[36];
+  double map_eig[6], map_V[36], map_cov[36];
+  double vo_x[6], vo_cost, vo_reserved, vo_H[36], vo_eig[6], vo_V[36], vo_cov[36];
+} vloam_pose_cov_record;
+#if defined(__cplusplus)
+static_assert(sizeof(vloam_pose_cov_record) == 2288, "vloam_pose_cov_record is 8 ints and 282 doubles");
+#elif defined(__STDC_VERSION__) && __STDC_VERSION__ >= 201112L
+_Static_assert(sizeof(vloam_pose_cov_record) == 2288, "vloam_pose_cov_record is 8 ints and 282 doubles");
+#endif
+/* vloam_pose_cov_enable: only on a handle that has already enabled pose information and has taken no sweep yet (VLOAM_ERR_ORDER otherwise, also
+ *   when called twice); single-sequence and batched handles.  Allocates max_frames rows of 2288 bytes per session outside the session arenas.
+ *   opt may be NULL (the defaults).  The options are checked first, before the handle is looked at: VLOAM_ERR_INVALID for a struct_size other
+ *   than sizeof(vloam_pose_cov_options), a reserved other than 0, a negative, NaN or infinite threshold.
+ * vloam_get_pose_cov: the rows of sweeps first .. first + count - 1 of the session chosen with vloam_select_session -> HOST buffer; waiting and
+ *   range rules of vloam_get_pose_info.  VLOAM_ERR_ORDER: the handle never enabled the product.  VLOAM_ERR_INVALID: a range beyond vloam_frame_count.
+ * vloam_pose_cov_device_ptr: device address + byte size of the selected session's rows; rows are only complete after vloam_sync(). */
+vloam_status vloam_pose_cov_enable(vloam_handle* h, const vloam_pose_cov_options* opt);
+vloam_status vloam_get_pose_cov(vloam_handle* h, int first, int count, vloam_pose_cov_record* out);
+vloam_status vloam_pose_cov_device_ptr(vloam_handle* h, void** d_rows, long long* bytes);
 
 /* == VisualOdometry::processPointCloud + solveNlsAll (visual_odometry.cpp:157-186,254-450).
  * prev_uv/curr_uv: n_match integer pixel pairs (the reference truncates keypoints to int, :283-294).

@@ -111,6 +111,10 @@ def main():
                          "lo_min_eig, map_min_eig, lo_degenerate, map_degenerate to the per-frame metrics (null where that stage did not solve)")
     ap.add_argument("--lo-min-eig", type=float, default=0.0, help="with --pose-info: odometry degeneracy threshold on the smallest eigenvalue (0: never)")
     ap.add_argument("--map-min-eig", type=float, default=0.0, help="with --pose-info: the same for the mapping")
+    ap.add_argument("--pose-cov", action="store_true",
+                    help="enable the per-sweep pose covariance rows (vloam_pose_cov_enable; implies --pose-info) and add, for lo, map and vo, *_rank, "
+                         "*_sigma_t and *_sigma_r to the per-frame metrics: the eigenvalues kept by the pseudo-inverse and the square root of the largest "
+                         "eigenvalue of the translation / rotation block of the covariance (null where that stage has no covariance)")
     ap.add_argument("--save-checkpoint", metavar="PATH", help="write the sequence's checkpoint (vloam_checkpoint_save) to this file: after the last sweep, or with --at "
                                                               "FRAME once FRAME sweeps are done (a run resumed from it starts at sweep FRAME); the run itself goes on unchanged")
     ap.add_argument("--at", type=int, default=None, metavar="FRAME", help="with --save-checkpoint: sweeps done when the checkpoint is taken")
@@ -119,6 +123,7 @@ def main():
     ap.add_argument("--imu-T-velo", help="16 numbers, row major (default: KITTI 2011_09_26 extrinsics, approx.)")
     ap.add_argument("--imu-T-cam0", help="16 numbers, row major")
     a = ap.parse_args()
+    a.pose_info = a.pose_info or a.pose_cov
     vl = load_pkg()
     import importlib
     kio = importlib.import_module("vloam_amd.kitti_io")
@@ -168,6 +173,8 @@ def main():
     hd = loam.hd
     if a.pose_info:
         hd.enable_pose_info(a.lo_min_eig, a.map_min_eig)
+    if a.pose_cov:
+        hd.pose_cov_enable()
     if a.vloam:
         if real_images:   # PointCloudUtil::loadTransformations (point_cloud_util.cpp:5-116)
             hd.vo_set_calib(*kio.load_transformations(a.calib_cam_to_cam, a.calib_velo_to_cam))
@@ -240,6 +247,15 @@ def main():
                 rec["map_min_eig"] = float(pi["map_eig"][0]) if fl & vl.POSE_INFO_MAP_VALID else None
                 rec["lo_degenerate"] = bool(fl & vl.POSE_INFO_LO_DEGENERATE)
                 rec["map_degenerate"] = bool(fl & vl.POSE_INFO_MAP_DEGENERATE)
+            if a.pose_cov:
+                pc = hd.get_pose_cov(count, 1)[0]
+                # rotation block first in all three parameterisations: (delta theta, delta t) of the LiDAR stages, (angle-axis, t) of the VO
+                for k, (stage, bit) in enumerate((("lo", vl.POSE_COV_LO_VALID), ("map", vl.POSE_COV_MAP_VALID), ("vo", vl.POSE_COV_VO_VALID))):
+                    ok = bool(int(pc["flags"]) & bit)
+                    cov = pc[stage + "_cov"].reshape(6, 6)
+                    rec[stage + "_rank"] = int(pc["rank"][k]) if ok else None
+                    rec[stage + "_sigma_t"] = float(np.sqrt(max(np.linalg.eigvalsh(cov[3:, 3:])[-1], 0.0))) if ok else None
+                    rec[stage + "_sigma_r"] = float(np.sqrt(max(np.linalg.eigvalsh(cov[:3, :3])[-1], 0.0))) if ok else None
             if count > 0:
                 for name, st, item in (("lo_round0", 1, 2), ("lo_round1", 1, 18), ("map_round0", 2, 3), ("map_round1", 2, 19)):
                     r = hd.debug_lm_record(st, item)

@@ -90,6 +90,23 @@ POSE_INFO_DTYPE = np.dtype([
 POSE_INFO_LO_VALID, POSE_INFO_MAP_VALID, POSE_INFO_LO_DEGENERATE, POSE_INFO_MAP_DEGENERATE = 1, 2, 4, 8
 
 
+class PoseCovOptions(C.Structure):
+    """vloam_pose_cov_options (c_api.h; vloam_pose_cov_enable)."""
+    _fields_ = [("struct_size", C.c_int), ("reserved", C.c_int), ("lo_min_eigenvalue", C.c_double), ("map_min_eigenvalue", C.c_double),
+                ("vo_min_eigenvalue", C.c_double)]
+
+
+# vloam_pose_cov_record (c_api.h): 8 ints then 282 doubles, 2288 bytes
+POSE_COV_DTYPE = np.dtype([
+    ("frame", "<i4"), ("flags", "<i4"), ("rank", "<i4", (3,)), ("vo_factors", "<i4", (2,)), ("reserved", "<i4"),
+    ("sigma2", "<f8", (3,)), ("reserved_d", "<f8"),
+    ("lo_eig", "<f8", (6,)), ("lo_V", "<f8", (36,)), ("lo_cov", "<f8", (36,)),
+    ("map_eig", "<f8", (6,)), ("map_V", "<f8", (36,)), ("map_cov", "<f8", (36,)),
+    ("vo_x", "<f8", (6,)), ("vo_cost", "<f8"), ("vo_reserved", "<f8"), ("vo_H", "<f8", (36,)), ("vo_eig", "<f8", (6,)), ("vo_V", "<f8", (36,)),
+    ("vo_cov", "<f8", (36,))])
+POSE_COV_LO_VALID, POSE_COV_MAP_VALID, POSE_COV_VO_VALID, POSE_COV_LO_TRUNCATED, POSE_COV_MAP_TRUNCATED, POSE_COV_VO_TRUNCATED = 1, 2, 4, 8, 16, 32
+
+
 class Calib(C.Structure):
     _fields_ = [("cam_T_velo", C.c_float * 16), ("rect0_T_cam", C.c_float * 16), ("P_rect0", C.c_float * 12)]
 
@@ -380,6 +397,29 @@ class Handle:
     def pose_info_device_ptr(self):
         p, b = C.c_void_p(), C.c_longlong(0)
         self._chk(self.L.vloam_pose_info_device_ptr(self.h, C.byref(p), C.byref(b)))
+        return p.value, b.value
+
+    def pose_cov_enable(self, lo_min_eigenvalue=0.0, map_min_eigenvalue=0.0, vo_min_eigenvalue=0.0):
+        """vloam_pose_cov_enable, on a fresh handle right after enable_pose_info: from now on every sweep also leaves a vloam_pose_cov_record
+        (eigenvectors, rank, sigma^2 and pseudo-inverse covariance of the odometry, mapping and VO problems; the thresholds are the eigenvalues
+        below which a direction counts as unobserved, 0 = only lambda <= 1e-12 lambda_max)."""
+        opt = PoseCovOptions()
+        self.L.vloam_default_pose_cov_options(C.byref(opt))
+        opt.lo_min_eigenvalue, opt.map_min_eigenvalue, opt.vo_min_eigenvalue = float(lo_min_eigenvalue), float(map_min_eigenvalue), float(vo_min_eigenvalue)
+        self._chk(self.L.vloam_pose_cov_enable(self.h, C.byref(opt)))
+
+    def get_pose_cov(self, first=0, count=None):
+        """vloam_get_pose_cov: the rows of sweeps first .. first + count - 1 of the selected session as a structured array (POSE_COV_DTYPE).
+        Waits for the work behind the last row asked for only, not for the pipeline."""
+        if count is None:
+            count = self.frame_count() - first
+        out = np.zeros(max(count, 1), dtype=POSE_COV_DTYPE)
+        self._chk(self.L.vloam_get_pose_cov(self.h, int(first), int(count), _fp(out)))
+        return out[:count]
+
+    def pose_cov_device_ptr(self):
+        p, b = C.c_void_p(), C.c_longlong(0)
+        self._chk(self.L.vloam_pose_cov_device_ptr(self.h, C.byref(p), C.byref(b)))
         return p.value, b.value
 
     def profile_kernel(self, name, max_launches=4096):

@@ -470,6 +470,8 @@ vloam_status vloam_destroy(vloam_handle* h) {
   if (h->pi.rows) (void)hipFree(h->pi.rows);
   if (h->pi.scratch) (void)hipFree(h->pi.scratch);
   h->pi_ring.destroy();
+  if (h->pc.rows) (void)hipFree(h->pc.rows);
+  if (h->pc.scratch) (void)hipFree(h->pc.scratch);
   for (int k = 0; k < vloam_handle::kInRing; k++) if (h->ev_in_copied[k]) (void)hipEventDestroy(h->ev_in_copied[k]);
   for (int k = 0; k < 6; k++) if (h->ev[k]) (void)hipEventDestroy(h->ev[k]);
   for (int k = 0; k < vloam_handle::kSets; k++)

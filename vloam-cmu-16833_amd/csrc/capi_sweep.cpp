@@ -126,6 +126,8 @@ static vloam_status enqueue_lo(vloam_handle* h, int frame) {
     if (frame > 0) {  // Section 4: if (count > 0) VO->solveNlsAll()
       vloam_status s = vo_solve_enqueue(&h->vo, h->cfg, h->s_lo, frame, h->lo, &h->prof);
       if (s != VLOAM_OK) { set_err("vo_solve_enqueue failed"); return s; }
+      // the VO half of the covariance row: the solve's own factor storage at the estimate it just left in vo.x
+      if (h->pose_cov) pose_cov_vo_launch(h->s_lo, h->se, h->pc, frame, h->vo.F, h->vo.x);
     }
     // vloam_tf->VO2VeloAndBase(VO->cam0_curr_T_cam0_last) + (combined mode) the first outer round's para_q / para_t overwrite
     lo_set_prior_launch(h->s_lo, h->se, h->lo, use_prior && frame > 0, h->vo.x, frame > 0, h->vo_traj + (size_t)frame * 7, &h->map.frame->error);
@@ -149,8 +151,11 @@ static vloam_status enqueue_lo(vloam_handle* h, int frame) {
     sweep_log_lo_launch(h->s_lo, h->se, h->log_rows, frame, h->log_scratch, h->lo, h->lo_corr[0], h->lo_corr[1], h->lo_rec, &h->map.frame->fallback_solves,
                         !h->cfg.with_mapping, &h->prof, h->log_ring.bind(1, frame));
   // the information matrix of the second round's problem at the pose it returned: the table still holds that round's factors
-  if (h->pose_info)
-    pose_info_launch(h->s_lo, h->se, h->pi, 0, frame, h->lo_F, h->lo_rec + 1, frame > 0, nullptr, !h->cfg.with_mapping, &h->prof, h->pi_ring.bind(0, frame));
+  if (h->pose_info) {
+    hipEvent_t done = h->pi_ring.bind(0, frame);
+    pose_info_launch(h->s_lo, h->se, h->pi, 0, frame, h->lo_F, h->lo_rec + 1, frame > 0, nullptr, !h->cfg.with_mapping, &h->prof, h->pose_cov ? nullptr : done);
+    if (h->pose_cov) pose_cov_launch(h->s_lo, h->se, h->pc, h->pi.rows, 0, frame, !h->cfg.with_mapping, done);   // from the row that launch just wrote
+  }
   HIPCHK(hipGetLastError());
   if (h->cfg.timing) HIPCHK(hipEventRecord(h->ev[3], h->s_lo));
   return VLOAM_OK;
@@ -183,7 +188,9 @@ static vloam_status enqueue_map(vloam_handle* h, int frame) {
   }
   // behind k_map_finalize: the second round's table is not rewritten before the next sweep's fit, and MapState::do_optimize is still this sweep's
   if (h->pose_info) {
-    pose_info_launch(h->s_map, h->se, h->pi, 1, frame, h->map.F[1], h->map.rec + 1, !skip, &h->map.state->do_optimize, true, &h->prof, h->pi_ring.bind(1, frame));
+    hipEvent_t done = h->pi_ring.bind(1, frame);
+    pose_info_launch(h->s_map, h->se, h->pi, 1, frame, h->map.F[1], h->map.rec + 1, !skip, &h->map.state->do_optimize, true, &h->prof, h->pose_cov ? nullptr : done);
+    if (h->pose_cov) pose_cov_launch(h->s_map, h->se, h->pc, h->pi.rows, 1, frame, true, done);
     HIPCHK(hipGetLastError());
   }
   if (sub_pose) HIPCHK(hipMemcpyAsync(h->traj + (size_t)frame * 14 + 7, h->sub_row + 7, 7 * sizeof(double), hipMemcpyDeviceToDevice, h->s_map));   // the map half of the log

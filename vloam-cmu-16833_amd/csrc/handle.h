@@ -24,6 +24,7 @@
 #include "lm_solve.h"
 #include "lo_kernels.h"
 #include "map_kernels.h"
+#include "pose_cov.h"
 #include "pose_info.h"
 #include "sr_kernels.h"
 #include "stage_input_check.h"
@@ -170,6 +171,10 @@ struct vloam_handle {
   bool pose_info = false;
   PoseInfo pi;
   RowEvents pi_ring;
+  // ... and its add-on, the pose covariance rows (vloam_pose_cov_enable; null / unused without it).  No ring of its own: once enabled, the launch
+  // behind each stage's pose information launch is the one pi_ring's event is bound to (the last writer of both products on that stream)
+  bool pose_cov = false;
+  PoseCov pc;
   hipEvent_t ev_vo[kSets] = {};     // depth map + matches of the frame in set c are in HBM
   bool vo_frame[kSets] = {};        // the sweep in set c came through vloam_process_frame (its odometry is preceded by the VO solve)
   bool have_extrinsics = false;
