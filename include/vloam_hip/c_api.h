@@ -654,6 +654,61 @@ vloam_status vloam_map_query_device(vloam_handle* h, const vloam_map_query_optio
 /* The corner (kind 0) or surf (kind 1) half of vloam_get_map, same order within the half; same calling convention. */
 vloam_status vloam_get_map_kind(vloam_handle* h, int kind, float* xyzi4, long long cap, long long* n);
 
+/* Localisation: a dry run of LaserMapping::input + solveMapping (laser_mapping.cpp:167-196, 198-636) against the map as it is.  It stops in
+ * front of the map update (laser_mapping.cpp:637 onwards) and returns the pose the mapping would have reported; nothing the sequence can see
+ * changes: no odometry row is consumed, the cube window does not roll, no voxel is inserted, q_wmap_wodom stays, no trajectory / sweep-log /
+ * pose-information row is written, and the handle's sticky error words are not touched.  Opt-in by calling: the scratch state (its own
+ * MapState, counters, stacks, factor tables, candidate cache) is allocated by the first call, outside the session arena, and freed by
+ * vloam_destroy; a handle that never localises allocates and launches nothing of this, and no kernel of a sweep changes.
+ *   Clouds: what vloam_set_mapping_input takes as laserCloudCornerLast / laserCloudSurfLast — packed (x, y, z, intensity) in the sensor frame,
+ *   at most 7680 corner points and max_points surf points, every float finite (the host form checks; the device form trusts its caller).
+ *   (q, t): pose_frame 0 — an odometry-frame pose q_wodom_curr / t_wodom_curr; the guess is formed with the handle's current q_wmap_wodom /
+ *   t_wmap_wodom exactly as LaserMapping::input does (laser_mapping.cpp:182-195).  pose_frame 1 — the guess itself, in the map frame.
+ *   corner == NULL && surf == NULL: the sweep in progress, between vloam_laser_odometry and vloam_laser_mapping of a stage-wise sweep — the
+ *   stacks the real mapping will consume (clouds handed to vloam_set_mapping_input included), read-only; with q == NULL && t == NULL also that
+ *   sweep's odometry pose (pose_frame is then ignored: it is an odometry pose).  The record's q_map / t_map are then bit for bit what the
+ *   vloam_laser_mapping that follows returns.
+ * Ordering: both calls first enqueue what the handle still owes; the chain runs on the mapping stream behind the last mapping (and any growth
+ *   step of a growable handle).  vloam_map_localize waits for that stream only, copies the record out, and then returns a sticky map error of
+ *   the handle (the one vloam_sync reports) instead of VLOAM_OK.  vloam_map_localize_device enqueues and returns: d_corner, d_surf and d_result
+ *   (sizeof(vloam_localize_result) bytes) are device memory, the record is complete after vloam_sync, the buffers must stay valid until then.
+ * Refusals, options first and before the handle is looked at (VLOAM_ERR_INVALID, each with its own vloam_last_error()): struct_size,
+ *   pose_frame outside 0 .. 1, reserved != 0, only one of the two clouds null, a null pose with non-null clouds (or only one of q, t null), a
+ *   negative count, more than 7680 corner or 16777216 surf points, a null result, a non-finite float or pose component, a quaternion whose
+ *   norm is off 1 by more than 1e-6.  Then the handle: with_mapping == 0 (VLOAM_ERR_ORDER); n_sessions > 1 (VLOAM_ERR_INVALID); a handle of
+ *   the large stack tier (VLOAM_ERR_INVALID, "not offered"); more surf points than max_points (VLOAM_ERR_CAPACITY); null clouds outside the
+ *   odometry-to-mapping window of a stage-wise, mapped sweep (VLOAM_ERR_ORDER).
+ * Not offered: batched handles, the large stack tier, raw sweeps as input (run vloam_scan_registration on a second handle with
+ *   with_mapping == 0 and take vloam_get_features(h, 2) / (h, 4)), several hypotheses per launch, information matrices of a localisation. */
+enum {
+  VLOAM_LOC_SOLVED = 1,          /* both outer rounds ran their solve */
+  VLOAM_LOC_NOT_OPTIMIZED = 2,   /* "Map corner and surf num are not enough" (laser_mapping.cpp:448,631-635): q_map / t_map == q_guess / t_guess */
+  VLOAM_LOC_WOULD_ROLL = 4,      /* a mapping at this pose would have shifted the cube window */
+  VLOAM_LOC_DEGRADED = 8         /* a cooperative solve of this call fell back to one workgroup */
+};
+typedef struct vloam_localize_options {
+  int struct_size;     /* sizeof as compiled */
+  int pose_frame;      /* 0: (q, t) is an odometry-frame pose; 1: (q, t) is the guess itself, in the map frame */
+  int reserved[2];     /* 0 */
+} vloam_localize_options;
+typedef struct vloam_localize_result {   /* 216 bytes: 18 ints (the last one padding), then 18 doubles */
+  int flags;                       /* VLOAM_LOC_* */
+  int error_bits;                  /* VLOAM_SWEEP_* bits this call raised on its own scratch (STACK_FULL, DS_TIMEOUT, MAP_FULL, MAP_RAW_CAPACITY) */
+  int center_cube[3];              /* laserCloudCen{Width,Height,Depth} indices of the pose's cube in the (would-be shifted) window */
+  int n_stack[2], n_map[2];        /* scan features after VoxelGrid; map points in the valid 5x5x3 block (laser_mapping.cpp:404-430) */
+  int n_factors[2][2];             /* [round][corner, surf] */
+  int iterations[2], termination[2];
+  int pad;
+  double q_guess[4], t_guess[3];   /* the pose the solve started from */
+  double q_map[4], t_map[3];       /* what vloam_laser_mapping would have returned */
+  double initial_cost[2], final_cost[2];
+} vloam_localize_result;
+void vloam_default_localize_options(vloam_localize_options* o);   /* pose_frame 0 */
+vloam_status vloam_map_localize(vloam_handle* h, const vloam_localize_options* o, const float* corner_xyzi4, int n_corner, const float* surf_xyzi4,
+                                int n_surf, const double q[4], const double t[3], vloam_localize_result* out);
+vloam_status vloam_map_localize_device(vloam_handle* h, const vloam_localize_options* o, const void* d_corner, int n_corner, const void* d_surf,
+                                       int n_surf, const double q[4], const double t[3], void* d_result);
+
 /* Timing of the last vloam_sync()ed scans: HIP-event milliseconds accumulated per stage
  * {scanRegistration, laserOdometry, laserMapping, vo} and number of scans covered. */
 vloam_status vloam_get_stage_ms(vloam_handle* h, double ms4[4], int* scans);

@@ -82,6 +82,31 @@ def write_sweep_log(vl, hd, path):
     print("wrote %d sweep records to %s" % (rows.shape[0], path))
 
 
+def localize_only(vl, kio, tf, hd, a, load_sweep, n, start):
+    """--resume CKPT --localize-only: every sweep of the input against the restored map, each from the previous result; the first one from the
+    restored sequence's last map pose.  The feature clouds come from a second handle without mapping (scan registration only); the map is
+    never updated."""
+    sr = vl.Handle(a.device, with_mapping=0, **({"max_ring_points": a.max_ring_points} if a.max_ring_points else {}))
+    row = hd.trajectory(start - 1, 1)[0]
+    q, t = row[7:11].copy(), row[11:14].copy()
+    row0 = hd.trajectory(0, 1)[0]
+    tf.MO2Cam0StartFrame(row0[7:11], row0[11:14], 0)   # rows are expressed in the start frame of the MAP's sequence, like MO0.txt of the saving run
+    rows, solved = [], 0
+    for count in range(n):
+        sr.reset_frame()
+        sr.scan_registration(load_sweep(count))
+        r = hd.map_localize(sr.features(2), sr.features(4), q / np.linalg.norm(q), t, pose_frame=1)
+        if r["error_bits"]:
+            print("sweep %d: error bits %d" % (count, r["error_bits"]), file=sys.stderr)
+        solved += 1 if r["flags"] & vl.LOC_SOLVED else 0
+        q, t = r["q_map"], r["t_map"]
+        rows.append(tf.MO2Cam0StartFrame(q, t, count + 1))
+    sr.close()
+    os.makedirs(a.out, exist_ok=True)
+    kio.write_trajectory(os.path.join(a.out, "LOC0.txt"), rows)
+    print("localised %d sweeps against the map of %d restored ones (%d solved), wrote %s/LOC0.txt" % (n, start, solved, a.out))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--velodyne", help="directory of KITTI raw velodyne .bin sweeps")
@@ -120,6 +145,9 @@ def main():
     ap.add_argument("--at", type=int, default=None, metavar="FRAME", help="with --save-checkpoint: sweeps done when the checkpoint is taken")
     ap.add_argument("--resume", metavar="PATH", help="load this checkpoint (vloam_checkpoint_load) into the fresh handle and go on with the sweep behind the saved ones: "
                                                      "the same input and the same algorithmic options as the saving run; outputs start at the restored sweep")
+    ap.add_argument("--localize-only", action="store_true",
+                    help="with --resume: localise EVERY sweep of the input against the restored map (vloam_map_localize, each from the previous result, "
+                         "pose_frame = 1) and write LOC0.txt in the results-row format; the map is never updated, no sweep is added to the sequence")
     ap.add_argument("--imu-T-velo", help="16 numbers, row major (default: KITTI 2011_09_26 extrinsics, approx.)")
     ap.add_argument("--imu-T-cam0", help="16 numbers, row major")
     a = ap.parse_args()
@@ -155,6 +183,8 @@ def main():
         real_images = sorted(glob.glob(os.path.join(a.image_dir, "*.png")))
         if len(real_images) < n:
             sys.exit("%d sweeps but only %d images in %s" % (n, len(real_images), a.image_dir))
+    if a.localize_only and not a.resume:
+        sys.exit("--localize-only needs a map: add --resume CKPT")
     if a.vloam and (a.save_checkpoint or a.resume):
         sys.exit("--save-checkpoint / --resume are for sequences driven by sweeps only: the VO's previous-frame state is not saved")
     if a.at is not None and not (a.save_checkpoint and 0 < a.at <= n):
@@ -191,6 +221,9 @@ def main():
         with open(a.resume, "rb") as f:
             hd.restore(f.read())
         start = hd.frame_count()
+        if a.localize_only:
+            localize_only(vl, kio, tf, hd, a, load_sweep, n, start)
+            return
         if not 0 < start < n:
             sys.exit("the checkpoint holds %d sweeps, the input %d: nothing to resume" % (start, n))
         row0 = hd.trajectory(0, 1)[0]   # the start frame of the written trajectories is the sequence's first sweep

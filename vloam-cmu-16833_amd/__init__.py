@@ -65,6 +65,20 @@ class MapQueryOptions(C.Structure):
     _fields_ = [("struct_size", C.c_int), ("kind", C.c_int), ("k", C.c_int), ("reserved", C.c_int), ("max_radius", C.c_float)]
 
 
+class LocalizeOptions(C.Structure):
+    """vloam_localize_options (c_api.h; vloam_map_localize / vloam_map_localize_device)."""
+    _fields_ = [("struct_size", C.c_int), ("pose_frame", C.c_int), ("reserved", C.c_int * 2)]
+
+
+# vloam_localize_result (c_api.h): 18 ints (the last one padding) then 18 doubles, 216 bytes
+LOCALIZE_RESULT_DTYPE = np.dtype([
+    ("flags", "<i4"), ("error_bits", "<i4"), ("center_cube", "<i4", (3,)), ("n_stack", "<i4", (2,)), ("n_map", "<i4", (2,)),
+    ("n_factors", "<i4", (2, 2)), ("iterations", "<i4", (2,)), ("termination", "<i4", (2,)), ("pad", "<i4"),
+    ("q_guess", "<f8", (4,)), ("t_guess", "<f8", (3,)), ("q_map", "<f8", (4,)), ("t_map", "<f8", (3,)),
+    ("initial_cost", "<f8", (2,)), ("final_cost", "<f8", (2,))])
+LOC_SOLVED, LOC_NOT_OPTIMIZED, LOC_WOULD_ROLL, LOC_DEGRADED = 1, 2, 4, 8
+
+
 # vloam_sweep_record (c_api.h): 32 ints then 8 doubles, 192 bytes
 SWEEP_RECORD_DTYPE = np.dtype([
     ("frame", "<i4"), ("error_bits", "<i4"), ("flags", "<i4"), ("n_in", "<i4"), ("n_cloud", "<i4"), ("n_sharp", "<i4"), ("n_less_sharp", "<i4"),
@@ -749,6 +763,41 @@ class Handle:
         and returns: the results are complete after sync(), and the buffers must stay valid until then."""
         opt = self._query_options(k, max_radius, kind)
         self._chk(self.L.vloam_map_query_device(self.h, C.byref(opt), C.c_void_p(d_points), int(n), C.c_void_p(d_xyzi), C.c_void_p(d_d2), C.c_void_p(d_count)))
+
+    def _localize_args(self, q, t, pose_frame):
+        opt = LocalizeOptions()
+        self.L.vloam_default_localize_options(C.byref(opt))
+        opt.pose_frame = int(pose_frame)
+        q = None if q is None else np.ascontiguousarray(q, dtype=np.float64)
+        t = None if t is None else np.ascontiguousarray(t, dtype=np.float64)
+        return opt, q, t
+
+    def map_localize(self, corner=None, surf=None, q=None, t=None, pose_frame=0):
+        """vloam_map_localize: a dry run of the mapping stage against the map as it is — where would this sweep be registered?  corner / surf:
+        float32 [n, 4] (x, y, z, intensity) in the sensor frame, what set_mapping_input takes; (q, t): an odometry-frame pose (pose_frame 0)
+        or the guess itself in the map frame (1).  corner = surf = None: the sweep in progress (between laser_odometry and laser_mapping),
+        with q = t = None under its own odometry pose.  Returns the fields of vloam_localize_result as a dict; nothing of the sequence
+        changes.  Runs behind everything handed over so far and waits for the mapping stream only."""
+        opt, q, t = self._localize_args(q, t, pose_frame)
+        c, s = self._cloud_arg(corner), self._cloud_arg(surf)
+        out = np.zeros(1, dtype=LOCALIZE_RESULT_DTYPE)
+        self._chk(self.L.vloam_map_localize(self.h, C.byref(opt), c[1], c[2], s[1], s[2], None if q is None else _fp(q), None if t is None else _fp(t), _fp(out)))
+        return {k: (out[0][k].copy() if out[0][k].ndim else out[0][k].item()) for k in LOCALIZE_RESULT_DTYPE.names if k != "pad"}
+
+    def map_localize_device(self, corner, surf, q, t, result, pose_frame=0):
+        """vloam_map_localize_device: the same with torch tensors on the device — corner / surf float32 [n, 4] (or both None), result a uint8
+        tensor of LOCALIZE_RESULT_DTYPE.itemsize bytes.  Enqueues and returns: the record is complete after sync(), the tensors must stay
+        alive until then."""
+        opt, q, t = self._localize_args(q, t, pose_frame)
+        assert result.is_cuda and result.is_contiguous() and result.numel() * result.element_size() >= LOCALIZE_RESULT_DTYPE.itemsize
+        ptr = [None, None]
+        n = [0, 0]
+        for k, c in enumerate((corner, surf)):
+            if c is not None:
+                assert c.is_cuda and c.is_contiguous() and c.dtype.is_floating_point and c.element_size() == 4 and c.shape[-1] == 4
+                ptr[k], n[k] = C.c_void_p(c.data_ptr() or result.data_ptr()), int(c.shape[0])   # (an empty tensor has no address: any non-null one will do)
+        self._chk(self.L.vloam_map_localize_device(self.h, C.byref(opt), ptr[0], n[0], ptr[1], n[1], None if q is None else _fp(q),
+                                                   None if t is None else _fp(t), C.c_void_p(result.data_ptr())))
 
     def published_map(self):
         """The latest /laser_cloud_map the mapping stream published (vloam_limits::map_pub_number): (float32 [n, 4], 0-based sweep index),

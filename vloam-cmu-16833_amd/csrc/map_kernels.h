@@ -149,6 +149,28 @@ struct MapGrow {
   std::vector<void*> leftover;    // what a failed allocation had got already: freed by map_grow_release (hipFree synchronises the device)
 };
 
+// Scratch of a localisation (vloam_map_localize; map_localize.hip): a dry run of the mapping chain works on its own MapState / MapFrame, stacks,
+// factor tables and candidate cache.  One allocation of its own, made by the first call, outside the session arena; null on a handle that never localises.
+struct LocAux { int shift[3]; int si_error; double guess[7]; };   // k_map_loc_prepare -> k_map_loc_finish
+struct MapLocalize {
+  char* base = nullptr;            // the allocation
+  MapState* state = nullptr;
+  MapFrame* frame = nullptr;
+  LocAux* aux = nullptr;
+  StackInfo* si = nullptr;         // foreign clouds: counters of their VoxelGrid
+  FrameScalars* S = nullptr;       // ... and its counts / bounding boxes (k_sr_adopt)
+  float4* in[2] = {nullptr, nullptr};      // the host form's uploaded clouds
+  float4* stack[2] = {nullptr, nullptr};
+  DsScratch ds[2];
+  unsigned ds_gen = 0;
+  FactorTable F[2];
+  LMRecord* rec = nullptr;         // [2]
+  float4* nbr = nullptr;
+  int4* cbox = nullptr;
+  float4* ccand = nullptr;
+  vloam_localize_result* result = nullptr;   // the host form's record
+};
+
 struct MapContext {
   MapState* state = nullptr;
   MapFrame* frame = nullptr;
@@ -195,6 +217,7 @@ struct MapContext {
     m.se.B = 1; m.sel = 0;
     return m;
   }
+  MapLocalize* loc = nullptr;   // localisation scratch: null until the first vloam_map_localize* call (host-side; not rebased: single-sequence handles only)
   MapPub pub;              // published clouds (off on a default handle)
   float4* registered = nullptr;  // full-resolution cloud in the map frame, on request
   long long* assoc_cyc = nullptr;  // [2][8] debug: phase cycle sums of k_map_assoc per outer round
@@ -237,6 +260,19 @@ vloam_status map_counts(MapContext* m, long long c[16]);
 // selected session, kind 0 corner map / 1 surf map / 2 both.  Enqueue only, no allocation: d_xyzi4 [n][k] float4, d_d2 [n][k], d_count [n].
 vloam_status map_query_enqueue(MapContext* m, hipStream_t st, int kind, int k, float radius, const void* d_xyz_pad4, int n, void* d_xyzi4, void* d_d2,
                                void* d_count);
+// ---- map_localize.hip (a code object of its own) + map_localize_enqueue in map_kernels.hip, beside map_enqueue: a dry run of the mapping chain
+// on scratch state (vloam_map_localize).  Single-sequence handles of the default stack tier.  corner / surf: device clouds (sensor frame), or both
+// null: stack set `set` as map_stack_enqueue left it, read-only.  row7: device address of an odometry pose (q xyzw, t), or null: pose7 (host
+// values, passed by value).  pose_frame 1: the pose is the guess itself.  d_result: device address the record is packed into.
+vloam_status map_localize_alloc(MapContext* m, hipStream_t st);   // first call: the scratch, zeroed on st; VLOAM_ERR_HIP when the allocation fails
+void map_localize_free(MapContext* m);
+vloam_status map_localize_enqueue(MapContext* m, hipStream_t st, const float4* corner, int n_corner, const float4* surf, int n_surf, int set,
+                                  const double* row7, const double pose7[7], int pose_frame, vloam_localize_result* d_result);
+// the two kernels of map_localize.hip, launched by map_localize_enqueue
+void map_loc_prepare_launch(hipStream_t st, const MapContext* m, const StackInfo* si, const double* row7, const double pose7[7], int pose_frame);
+void map_loc_finish_launch(hipStream_t st, const MapContext* m, vloam_localize_result* d_result);
+// map_stack.hip: the scan-feature VoxelGrid of foreign clouds into the localisation scratch (the kernels and grids of map_stack_enqueue)
+void map_stack_enqueue_loc(MapContext* m, hipStream_t st, const float4* corner, const float4* surf);
 // ---- map_grow.hip: growable handles (m->grow != null).  map_force_grow: test hook, one doubling of both tables now (between two sweeps, on the mapping stream).
 // map_grow_release: frees retired buffers whose grow chain has finished (hipEventQuery); call with nothing of the handle in flight — hipFree
 // synchronises the device.

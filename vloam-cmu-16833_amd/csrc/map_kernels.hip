@@ -906,6 +906,7 @@ vloam_status map_init(MapContext* m, hipStream_t st) {
 }
 
 void map_destroy(MapContext* m) {
+  map_localize_free(m);
   if (m->grow) map_grow_destroy(m);
   if (m->host_flags) { (void)hipHostFree(m->host_flags); m->host_flags = nullptr; }
   for (int k = 0; k < 2; k++)
@@ -1008,6 +1009,42 @@ vloam_status map_enqueue(MapContext* m, const vloam_config& cfg, hipStream_t st,
 #undef VL_INSERT
 #undef VL_FINALIZE
   if (m->grow) map_grow_progress_enqueue(m, st);
+  return hipGetLastError() == hipSuccess ? VLOAM_OK : VLOAM_ERR_HIP;
+}
+
+// A localisation (vloam_map_localize): map_enqueue's chain for a single sequence of the default stack tier up to the second solve, on the
+// scratch of m->loc — k_map_loc_prepare for k_map_prepare, no insert, no finalize, k_map_loc_finish packs the record (map_localize.hip).
+// The tables are m->tab[] as they are NOW, behind whatever growth step the last map_enqueue put on the stream.  No profiling hook: the
+// per-kernel timer counts sweeps' launches.
+vloam_status map_localize_enqueue(MapContext* m, hipStream_t st, const float4* corner, int n_corner, const float4* surf, int n_surf, int set,
+                                  const double* row7, const double pose7[7], int pose_frame, vloam_localize_result* d_result) {
+  MapLocalize* L = m->loc;
+  const float4* stack[2] = {m->stack_sets[set][0], m->stack_sets[set][1]};
+  const StackInfo* si = m->stack_info[set];
+  if (corner || surf) {
+    // counts and VoxelGrid boxes of the caller's clouds, then the VoxelGrid itself (the two launches of map_stack_enqueue)
+    SRBuffers b{};
+    b.S = L->S; b.less_sharp = const_cast<float4*>(corner); b.less_flat = const_cast<float4*>(surf);
+    if (hipMemsetAsync(L->si, 0, sizeof(StackInfo), st) != hipSuccess) return VLOAM_ERR_HIP;
+    sr_adopt_launch(st, b, -1, -1, n_corner, -1, n_surf);
+    map_stack_enqueue_loc(m, st, corner, surf);
+    stack[0] = L->stack[0]; stack[1] = L->stack[1];
+    si = L->si;
+  }
+  map_loc_prepare_launch(st, m, si, row7, pose7, pose_frame);
+  MapState* ms = L->state;
+  MapFrame* fr = L->frame;
+  Sess se = m->se;
+  se.B = 1; se.ss = 0;
+  for (int outer = 0; outer < 2; outer++) {
+    const int qw = 256 / 32;
+    VL_RAW_LAUNCH((k_map_assoc<32, 1>), dim3(8 * ((kStackCapCorner / qw + 7) / 8 + (kStackCapSurf / qw + 7) / 8), 1, 1), dim3(256), 0, st, stack[0], stack[1],
+                  m->tab[0], m->tab[1], m->inv_leaf[0], m->inv_leaf[1], ms, fr, L->nbr, outer, L->cbox, L->ccand, (long long*)nullptr, (size_t)0);
+    VL_RAW_LAUNCH(k_map_fit, dim3(kMapFactorCap / 256, 1, 1), dim3(256), 0, st, stack[0], stack[1], m->tab[0], m->tab[1], ms, fr, L->nbr, L->F[outer], outer,
+                  (size_t)0);
+    lm_launch(st, se, L->F[outer], kStackCapCorner, ms->parameters, L->rec + outer, 4, 0.1, true, &ms->do_optimize, nullptr);
+  }
+  map_loc_finish_launch(st, m, d_result);
   return hipGetLastError() == hipSuccess ? VLOAM_OK : VLOAM_ERR_HIP;
 }
 

@@ -359,4 +359,15 @@ vloam_status map_stack_enqueue(MapContext* m, hipStream_t st, const SRBuffers& c
   return hipGetLastError() == hipSuccess ? VLOAM_OK : VLOAM_ERR_HIP;
 }
 
+// The same two launches for a localisation's foreign clouds (vloam_map_localize): into the scratch stack pair, with the scratch's own
+// DsScratch, StackInfo and generation counter; L->S holds the clouds' counts and bounding boxes (k_sr_adopt).  One sequence, no session stride.
+void map_stack_enqueue_loc(MapContext* m, hipStream_t st, const float4* corner, const float4* surf) {
+  MapLocalize* L = m->loc;
+  L->ds_gen++;
+  VL_RAW_LAUNCH(k_map_ds_bin, dim3(32, 2, 1), dim3(256), 0, st, corner, surf, L->S, L->ds[0], L->ds[1], m->inv_leaf[0], m->inv_leaf[1], L->stack[0],
+                L->stack[1], L->si, (size_t)0);
+  VL_RAW_LAUNCH(k_map_ds_reduce, dim3(kDsReduceGrid, 2, 1), dim3(256), 0, st, corner, surf, L->S, L->ds[0], L->ds[1], m->inv_leaf[0], m->inv_leaf[1],
+                L->stack[0], L->stack[1], L->si, L->ds_gen, (size_t)0);
+}
+
 }  // namespace vloam
