@@ -709,6 +709,60 @@ vloam_status vloam_map_localize(vloam_handle* h, const vloam_localize_options* o
 vloam_status vloam_map_localize_device(vloam_handle* h, const vloam_localize_options* o, const void* d_corner, int n_corner, const void* d_surf,
                                        int n_surf, const double q[4], const double t[3], void* d_result);
 
+/* Map import: a FRESH handle is given two point clouds in the map frame — the corner map and the surf map, packed (x, y, z, intensity), e.g. what
+ * vloam_get_map_kind(h, 0 / 1) of any build of the library returned — and the map<-odometry transform the sequence starts with.  Afterwards it
+ * behaves like a handle that built that map itself: vloam_map_query, vloam_map_localize, the publications, checkpoints and ordinary sweeps work.
+ * Opt-in by calling: a handle that never imports allocates and launches nothing of this, and no kernel of a sweep changes.
+ *   1. The 21 x 21 x 11 cube window is placed for a sensor at t_wmap_wodom by the six shift loops of LaserMapping::solveMapping
+ *      (laser_mapping.cpp:207-402); every cube is still empty, so only laserCloudCen{Width,Height,Depth} and the centre cube change.
+ *   2. q_wmap_wodom / t_wmap_wodom are set, and the mapping's pose to that transform composed with the identity odometry pose
+ *      (laser_mapping.cpp:182-195).  The sweep count, vloam_frame_count and the trajectory stay at zero: the first sweep is sweep 0, its
+ *      odometry pose the identity, its mapping guess the imported transform.
+ *   3. Every point whose four floats are finite gets the cube and the voxel the mapping's own insert would give that map-frame point at its
+ *      kind's leaf (mapping_line_resolution / mapping_plane_resolution; laser_mapping.cpp:643-659).  A point whose cube lies outside the placed
+ *      window (or outside the voxel key's range) is dropped and counted in n_outside_window.
+ *   4. All points of a kind that share a voxel become ONE map point: their f32 sum in INPUT order, every component divided by (float)n — per
+ *      cube, what the reference holds after appending the points and running that cube's VoxelGrid filter once (laser_mapping.cpp:689-702).
+ *      Every cube is filtered, inside the valid 5 x 5 x 3 block or not: an import leaves no un-merged points.  A cloud with one point per voxel
+ *      (a vloam_get_map_kind export whose points do not sit on a voxel face) comes back from vloam_get_map_kind bit for bit, in order.
+ *   5. The per-cube point counts, the occupancy blocks and the table counters are what a handle holds that inserted those points itself.
+ *   The result is a function of the two arrays and the options alone, bit for bit from run to run (no floating-point atomics).
+ * Both forms run on the mapping stream with temporary allocations only, wait for that stream, and free them before they return.  The device form
+ *   takes device addresses (clouds and a vloam_map_import_result) and drops non-finite points, counted in n_nonfinite, where the host form refuses them.
+ * Refusals, options first and before the handle is looked at (VLOAM_ERR_INVALID, each with its own vloam_last_error()): null options,
+ *   struct_size, reserved != 0, a non-finite component of q or t, a quaternion whose norm is off 1 by more than 1e-6, a negative count, more
+ *   than 16777216 points of a kind, a null cloud with a positive count, a null result, host form only: a non-finite float in a cloud.  Then the
+ *   handle: with_mapping == 0 (VLOAM_ERR_ORDER); n_sessions > 1 (VLOAM_ERR_INVALID); not fresh — vloam_frame_count != 0, a sweep handed over, a
+ *   stage-wise sweep in progress, a checkpoint loaded or an earlier import (VLOAM_ERR_ORDER).  On every such refusal the handle stays fresh and
+ *   usable.  Both clouds empty: VLOAM_OK, only the window and the start pose are set.
+ * Capacity: a growable handle (vloam_map_options::grow) first steps its empty tables to the size its growth bound asks for with the point count
+ *   of each kind as the bound on records, as vloam_checkpoint_load does.  A fixed handle cannot be refused up front — how many DISTINCT voxels
+ *   the clouds hold is known only after keying: when they exceed 60 % of a table's slots (or a probe chain reaches its bound) the call returns
+ *   VLOAM_ERR_CAPACITY naming the table, the handle carries the sticky map-full error a sweep would have raised (vloam_sync reports it) and is
+ *   finished, as after such a sweep.
+ * Not offered: batched handles; importing into a handle that has taken sweeps (merging into a live map); un-merged raw points (an export that
+ *   holds several points of one voxel comes back as their centroid); normals, covariances or any per-point attribute beyond intensity. */
+typedef struct vloam_map_import_options {
+  int struct_size;            /* sizeof as compiled */
+  int reserved[3];            /* 0 */
+  double q_wmap_wodom[4];     /* (x, y, z, w), unit within 1e-6; default identity */
+  double t_wmap_wodom[3];     /* default 0: where the odometry frame's origin (the first sweep) lies in the map */
+} vloam_map_import_options;
+typedef struct vloam_map_import_result {   /* 88 bytes: 8 long long, then 6 ints */
+  long long n_in[2], n_voxels[2];      /* [corner, surf]: points given, map points (voxel records) created */
+  long long n_outside_window[2];       /* dropped: cube outside the placed 21 x 21 x 11 window (or outside the key range) */
+  long long n_nonfinite[2];            /* dropped by the device form; the host form refuses instead */
+  int max_per_voxel[2];                /* most points merged into one map point */
+  int center_cube[3];                  /* laserCloudCen{Width,Height,Depth} after placing the window: cube (i, j, k) of the window holds the
+                                          points of [50 (i - center_cube[0]) - 25, ... + 50) m in x, likewise y and z */
+  int pad;
+} vloam_map_import_result;
+void vloam_default_map_import_options(vloam_map_import_options* o);   /* identity, zero */
+vloam_status vloam_map_import(vloam_handle* h, const vloam_map_import_options* o, const float* corner_xyzi4, long long n_corner,
+                              const float* surf_xyzi4, long long n_surf, vloam_map_import_result* out);
+vloam_status vloam_map_import_device(vloam_handle* h, const vloam_map_import_options* o, const void* d_corner, long long n_corner,
+                                     const void* d_surf, long long n_surf, void* d_result);
+
 /* Timing of the last vloam_sync()ed scans: HIP-event milliseconds accumulated per stage
  * {scanRegistration, laserOdometry, laserMapping, vo} and number of scans covered. */
 vloam_status vloam_get_stage_ms(vloam_handle* h, double ms4[4], int* scans);

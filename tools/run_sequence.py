@@ -82,15 +82,29 @@ def write_sweep_log(vl, hd, path):
     print("wrote %d sweep records to %s" % (rows.shape[0], path))
 
 
-def localize_only(vl, kio, tf, hd, a, load_sweep, n, start):
-    """--resume CKPT --localize-only: every sweep of the input against the restored map, each from the previous result; the first one from the
-    restored sequence's last map pose.  The feature clouds come from a second handle without mapping (scan registration only); the map is
-    never updated."""
+def read_start_pose(a):
+    """--load-map DIR: (q xyzw, t) the sequence starts with in the map — --start-pose, else DIR/start_pose.txt (the saving run's last mapped
+    pose: going on where it stopped), else the map's origin."""
+    path = os.path.join(a.load_map, "start_pose.txt")
+    if a.start_pose:
+        v = [float(x) for x in a.start_pose.split()]
+    elif os.path.exists(path):
+        v = [float(x) for x in open(path).read().split()]
+    else:
+        v = [0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0]
+    if len(v) != 7:
+        sys.exit("a start pose is seven numbers: qx qy qz qw tx ty tz")
+    q = np.array(v[:4])
+    return q / np.linalg.norm(q), np.array(v[4:])
+
+
+def localize_only(vl, kio, tf, hd, a, load_sweep, n, first, origin, what):
+    """--resume CKPT / --load-map DIR with --localize-only: every sweep of the input against the map, each from the previous result; the first
+    one from `first` (the restored sequence's last map pose / the start pose).  The feature clouds come from a second handle without mapping
+    (scan registration only); the map is never updated."""
     sr = vl.Handle(a.device, with_mapping=0, **({"max_ring_points": a.max_ring_points} if a.max_ring_points else {}))
-    row = hd.trajectory(start - 1, 1)[0]
-    q, t = row[7:11].copy(), row[11:14].copy()
-    row0 = hd.trajectory(0, 1)[0]
-    tf.MO2Cam0StartFrame(row0[7:11], row0[11:14], 0)   # rows are expressed in the start frame of the MAP's sequence, like MO0.txt of the saving run
+    q, t = first[0].copy(), first[1].copy()
+    tf.MO2Cam0StartFrame(origin[0], origin[1], 0)   # rows are expressed in the start frame of the MAP's sequence, like MO0.txt of the saving run
     rows, solved = [], 0
     for count in range(n):
         sr.reset_frame()
@@ -104,7 +118,7 @@ def localize_only(vl, kio, tf, hd, a, load_sweep, n, start):
     sr.close()
     os.makedirs(a.out, exist_ok=True)
     kio.write_trajectory(os.path.join(a.out, "LOC0.txt"), rows)
-    print("localised %d sweeps against the map of %d restored ones (%d solved), wrote %s/LOC0.txt" % (n, start, solved, a.out))
+    print("localised %d sweeps against %s (%d solved), wrote %s/LOC0.txt" % (n, what, solved, a.out))
 
 
 def main():
@@ -148,6 +162,12 @@ def main():
     ap.add_argument("--localize-only", action="store_true",
                     help="with --resume: localise EVERY sweep of the input against the restored map (vloam_map_localize, each from the previous result, "
                          "pose_frame = 1) and write LOC0.txt in the results-row format; the map is never updated, no sweep is added to the sequence")
+    ap.add_argument("--save-map", metavar="DIR", help="after the last sweep write the map as DIR/corner.npy and DIR/surf.npy (vloam_get_map_kind: float32 [n, 4], map frame) "
+                                                      "and the last mapped pose as DIR/start_pose.txt (qx qy qz qw tx ty tz): what --load-map takes, with any build of the library")
+    ap.add_argument("--load-map", metavar="DIR", help="import DIR/corner.npy and DIR/surf.npy as the map of the fresh handle before the first sweep (vloam_map_import); "
+                                                      "with --localize-only as --resume: every sweep is localised against the imported map, which is never updated")
+    ap.add_argument("--start-pose", metavar="\"qx qy qz qw tx ty tz\"", help="with --load-map: the map<-odometry transform the sequence starts with "
+                                                                           "(default: DIR/start_pose.txt if there is one, else the map's origin)")
     ap.add_argument("--imu-T-velo", help="16 numbers, row major (default: KITTI 2011_09_26 extrinsics, approx.)")
     ap.add_argument("--imu-T-cam0", help="16 numbers, row major")
     a = ap.parse_args()
@@ -183,10 +203,14 @@ def main():
         real_images = sorted(glob.glob(os.path.join(a.image_dir, "*.png")))
         if len(real_images) < n:
             sys.exit("%d sweeps but only %d images in %s" % (n, len(real_images), a.image_dir))
-    if a.localize_only and not a.resume:
-        sys.exit("--localize-only needs a map: add --resume CKPT")
-    if a.vloam and (a.save_checkpoint or a.resume):
-        sys.exit("--save-checkpoint / --resume are for sequences driven by sweeps only: the VO's previous-frame state is not saved")
+    if a.localize_only and not (a.resume or a.load_map):
+        sys.exit("--localize-only needs a map: add --resume CKPT or --load-map DIR")
+    if a.resume and a.load_map:
+        sys.exit("--resume and --load-map both fill a fresh handle: choose one")
+    if a.start_pose and not a.load_map:
+        sys.exit("--start-pose belongs to --load-map")
+    if a.vloam and (a.save_checkpoint or a.resume or a.load_map):
+        sys.exit("--save-checkpoint / --resume / --load-map are for sequences driven by sweeps only: the VO's previous-frame state is not saved")
     if a.at is not None and not (a.save_checkpoint and 0 < a.at <= n):
         sys.exit("--at FRAME belongs to --save-checkpoint, 1 <= FRAME <= %d" % n)
     if a.images and not a.vloam:
@@ -222,13 +246,22 @@ def main():
             hd.restore(f.read())
         start = hd.frame_count()
         if a.localize_only:
-            localize_only(vl, kio, tf, hd, a, load_sweep, n, start)
+            last, row0 = hd.trajectory(start - 1, 1)[0], hd.trajectory(0, 1)[0]
+            localize_only(vl, kio, tf, hd, a, load_sweep, n, (last[7:11], last[11:14]), (row0[7:11], row0[11:14]), "the map of %d restored sweeps" % start)
             return
         if not 0 < start < n:
             sys.exit("the checkpoint holds %d sweeps, the input %d: nothing to resume" % (start, n))
         row0 = hd.trajectory(0, 1)[0]   # the start frame of the written trajectories is the sequence's first sweep
         tf.LO2Cam0StartFrame(row0[0:4], row0[4:7], 0)
         tf.MO2Cam0StartFrame(row0[7:11], row0[11:14], 0)
+    if a.load_map:
+        q0, t0 = read_start_pose(a)
+        res = hd.map_import(np.load(os.path.join(a.load_map, "corner.npy")), np.load(os.path.join(a.load_map, "surf.npy")), q0, t0)
+        print("imported %d corner / %d surf map points from %s (%d / %d outside the window)" % (res["n_voxels"][0], res["n_voxels"][1], a.load_map,
+                                                                                              res["n_outside_window"][0], res["n_outside_window"][1]))
+        if a.localize_only:
+            localize_only(vl, kio, tf, hd, a, load_sweep, n, (q0, t0), (q0, t0), "the imported map")
+            return
     save_at = (a.at if a.at is not None else n) if a.save_checkpoint else -1
     for count in range(start, n):
         cloud = load_sweep(count)
@@ -320,6 +353,15 @@ def main():
     print("wrote %d rows to %s/{LO0,MO0%s}.txt" % (n - start, a.out, ",VO0" if vo_rows else ""))
     if a.map_pub_number:
         print("wrote %d published maps to %s/map_<frame>.npy" % (n_pub, a.out))
+    if a.save_map:
+        os.makedirs(a.save_map, exist_ok=True)
+        halves = [hd.get_map_kind(k) for k in (0, 1)]
+        np.save(os.path.join(a.save_map, "corner.npy"), halves[0])
+        np.save(os.path.join(a.save_map, "surf.npy"), halves[1])
+        row = hd.trajectory(n - 1, 1)[0]
+        with open(os.path.join(a.save_map, "start_pose.txt"), "w") as f:
+            f.write(" ".join("%.17g" % v for v in row[7:14]) + "\n")
+        print("wrote %d corner / %d surf map points to %s" % (halves[0].shape[0], halves[1].shape[0], a.save_map))
 
 
 if __name__ == "__main__":

@@ -79,6 +79,17 @@ LOCALIZE_RESULT_DTYPE = np.dtype([
 LOC_SOLVED, LOC_NOT_OPTIMIZED, LOC_WOULD_ROLL, LOC_DEGRADED = 1, 2, 4, 8
 
 
+class MapImportOptions(C.Structure):
+    """vloam_map_import_options (c_api.h; vloam_map_import / vloam_map_import_device)."""
+    _fields_ = [("struct_size", C.c_int), ("reserved", C.c_int * 3), ("q_wmap_wodom", C.c_double * 4), ("t_wmap_wodom", C.c_double * 3)]
+
+
+# vloam_map_import_result (c_api.h): 8 long long then 6 ints (the last one padding), 88 bytes
+MAP_IMPORT_RESULT_DTYPE = np.dtype([
+    ("n_in", "<i8", (2,)), ("n_voxels", "<i8", (2,)), ("n_outside_window", "<i8", (2,)), ("n_nonfinite", "<i8", (2,)),
+    ("max_per_voxel", "<i4", (2,)), ("center_cube", "<i4", (3,)), ("pad", "<i4")])
+
+
 # vloam_sweep_record (c_api.h): 32 ints then 8 doubles, 192 bytes
 SWEEP_RECORD_DTYPE = np.dtype([
     ("frame", "<i4"), ("error_bits", "<i4"), ("flags", "<i4"), ("n_in", "<i4"), ("n_cloud", "<i4"), ("n_sharp", "<i4"), ("n_less_sharp", "<i4"),
@@ -798,6 +809,44 @@ class Handle:
                 ptr[k], n[k] = C.c_void_p(c.data_ptr() or result.data_ptr()), int(c.shape[0])   # (an empty tensor has no address: any non-null one will do)
         self._chk(self.L.vloam_map_localize_device(self.h, C.byref(opt), ptr[0], n[0], ptr[1], n[1], None if q is None else _fp(q),
                                                    None if t is None else _fp(t), C.c_void_p(result.data_ptr())))
+
+    def _import_options(self, q_wmap_wodom, t_wmap_wodom):
+        opt = MapImportOptions()
+        self.L.vloam_default_map_import_options(C.byref(opt))
+        if q_wmap_wodom is not None:
+            opt.q_wmap_wodom[:] = [float(v) for v in q_wmap_wodom]
+        if t_wmap_wodom is not None:
+            opt.t_wmap_wodom[:] = [float(v) for v in t_wmap_wodom]
+        return opt
+
+    @staticmethod
+    def _import_result(out):
+        return {k: (out[0][k].copy() if out[0][k].ndim else out[0][k].item()) for k in MAP_IMPORT_RESULT_DTYPE.names if k != "pad"}
+
+    def map_import(self, corner, surf, q_wmap_wodom=None, t_wmap_wodom=None):
+        """vloam_map_import: on a fresh handle, corner / surf (float32 [n, 4]: x, y, z, intensity in the MAP frame, e.g. get_map_kind(0 / 1) of
+        another handle; None: empty) become the map, points of one voxel merged into their centroid in input order, and (q_wmap_wodom xyzw,
+        t_wmap_wodom) the map<-odometry transform the sequence starts with (None: identity / zero).  Returns the fields of
+        vloam_map_import_result as a dict."""
+        opt = self._import_options(q_wmap_wodom, t_wmap_wodom)
+        c, s = self._cloud_arg(corner), self._cloud_arg(surf)
+        out = np.zeros(1, dtype=MAP_IMPORT_RESULT_DTYPE)
+        self._chk(self.L.vloam_map_import(self.h, C.byref(opt), c[1], C.c_longlong(c[2]), s[1], C.c_longlong(s[2]), _fp(out)))
+        return self._import_result(out)
+
+    def map_import_device(self, corner, surf, q_wmap_wodom=None, t_wmap_wodom=None):
+        """vloam_map_import_device: the same with torch tensors on the device (float32 [n, 4], or None); points with a non-finite float are
+        dropped and counted in n_nonfinite, where map_import() refuses them.  Returns the result as a dict."""
+        import torch
+        opt = self._import_options(q_wmap_wodom, t_wmap_wodom)
+        ptr, n = [None, None], [0, 0]
+        for k, c in enumerate((corner, surf)):
+            if c is not None and c.shape[0] > 0:
+                assert c.is_cuda and c.is_contiguous() and c.dtype == torch.float32 and c.shape[-1] == 4
+                ptr[k], n[k] = C.c_void_p(c.data_ptr()), int(c.shape[0])
+        res = torch.zeros(MAP_IMPORT_RESULT_DTYPE.itemsize, dtype=torch.uint8, device=next((c.device for c in (corner, surf) if c is not None), "cuda"))
+        self._chk(self.L.vloam_map_import_device(self.h, C.byref(opt), ptr[0], C.c_longlong(n[0]), ptr[1], C.c_longlong(n[1]), C.c_void_p(res.data_ptr())))
+        return self._import_result(res.cpu().numpy().view(MAP_IMPORT_RESULT_DTYPE))
 
     def published_map(self):
         """The latest /laser_cloud_map the mapping stream published (vloam_limits::map_pub_number): (float32 [n, 4], 0-based sweep index),

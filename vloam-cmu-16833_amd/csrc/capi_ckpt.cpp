@@ -122,6 +122,7 @@ vloam_status vloam_checkpoint_load(vloam_handle* h, const void* buf, long long b
   if (!ckpt_parse(buf, bytes, ckpt_expect(), &hd, why, sizeof(why))) { set_err("vloam_checkpoint_load: %s", why); return VLOAM_ERR_INVALID; }
   if (!h) { set_err("vloam_checkpoint_load: null handle"); return VLOAM_ERR_INVALID; }
   if (h->se.B != 1) { set_err("vloam_checkpoint_load: a checkpoint holds one sequence: the handle has n_sessions = %d", h->se.B); return VLOAM_ERR_INVALID; }
+  if (h->map_imported) { set_err("vloam_checkpoint_load: the handle has imported a map (vloam_map_import): load works on a handle right after its creation"); return VLOAM_ERR_ORDER; }
   if (!is_fresh(h) || h->vo_used) {
     set_err("vloam_checkpoint_load: the handle is not fresh (%d sweeps taken, stage %d): load works on a handle right after its creation", handed_over(h), h->stage);
     return VLOAM_ERR_ORDER;

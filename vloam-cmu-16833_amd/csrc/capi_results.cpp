@@ -110,7 +110,7 @@ vloam_status vloam_sync(vloam_handle* h) {
   HIPCHK(hipSetDevice(h->device));
   TRY(sync_all(h));
   map_grow_release(&h->map);   // nothing of the handle is in flight: tables a finished growth step left behind are freed here
-  if (h->frame > 0) {
+  if (h->frame > 0 || h->map_imported) {   // (an import can fill a fixed table before the first sweep)
     // surface sticky device-side errors: scan-registration bits of ANY sweep since the last vloam_sync (k_sr_compact folds every
     // sweep's word into the handle's sticky word; reported once, then cleared), map / solver bits for good
     int merr = 0;

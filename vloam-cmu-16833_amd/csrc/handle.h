@@ -1,6 +1,6 @@
 // Host-only: the handle behind the C ABI and what the translation units of the host side share (c_api.cpp: creation and destruction;
 // capi_sweep.cpp: the sweep pipeline; capi_frame.cpp: coupled frames, images, VO; capi_results.cpp: getters and debug hooks; capi_rows.cpp: the
-// per-sweep row products; capi_ckpt.cpp: checkpoints; capi_query.cpp: map queries; capi_localize.cpp: localisation).  No .hip file includes this.  Helpers that cross files live in namespace vloam (mangled,
+// per-sweep row products; capi_ckpt.cpp: checkpoints; capi_query.cpp: map queries; capi_localize.cpp: localisation; capi_import.cpp: map import).  No .hip file includes this.  Helpers that cross files live in namespace vloam (mangled,
 // out of the C symbol list); a helper of one file is static there.
 #pragma once
 #include "../../include/vloam_hip/c_api.h"
@@ -178,6 +178,7 @@ struct vloam_handle {
   hipEvent_t ev_vo[kSets] = {};     // depth map + matches of the frame in set c are in HBM
   bool vo_frame[kSets] = {};        // the sweep in set c came through vloam_process_frame (its odometry is preceded by the VO solve)
   bool have_extrinsics = false;
+  bool map_imported = false;        // vloam_map_import* has filled the map: no second import, no checkpoint load
   bool vo_used = false;             // a VO, frame or image entry point was called: the sequence cannot be checkpointed (the VO's previous-frame state is not saved)
   ImgContext img;
   std::vector<unsigned char> img_pack;   // host scratch: a padded image packed to width-stride rows

@@ -273,6 +273,12 @@ void map_loc_prepare_launch(hipStream_t st, const MapContext* m, const StackInfo
 void map_loc_finish_launch(hipStream_t st, const MapContext* m, vloam_localize_result* d_result);
 // map_stack.hip: the scan-feature VoxelGrid of foreign clouds into the localisation scratch (the kernels and grids of map_stack_enqueue)
 void map_stack_enqueue_loc(MapContext* m, hipStream_t st, const float4* corner, const float4* surf);
+// ---- map_import.hip (a code object of its own): vloam_map_import.  On the empty tables of a fresh single-sequence handle, nothing in flight: the window
+// is placed for pose7 (q xyzw, t: the map<-odometry transform), cloud[kind] (n[kind] packed float4 in the map frame; host memory with host_clouds,
+// else device memory) is keyed, merged per voxel in input order and inserted.  Temporary allocations only; synchronises st and frees them.
+// h_result: host memory.  The sticky map-full error is the caller's to read (MapFrame::error).
+vloam_status map_import_run(MapContext* m, hipStream_t st, const double pose7[7], const void* const cloud[2], const int n[2], bool host_clouds,
+                            vloam_map_import_result* h_result);
 // ---- map_grow.hip: growable handles (m->grow != null).  map_force_grow: test hook, one doubling of both tables now (between two sweeps, on the mapping stream).
 // map_grow_release: frees retired buffers whose grow chain has finished (hipEventQuery); call with nothing of the handle in flight — hipFree
 // synchronises the device.

@@ -1,6 +1,6 @@
 // The voxel tables of the map as device code sees them: hash, voxel key, record access, occupancy blocks.  Shared by map_kernels.hip (the
-// sweep's kernels), map_output.hip (export and publication), map_grow.hip (the growable map's rehash), map_ckpt.hip and map_query.hip, which are
-// separate code objects.
+// sweep's kernels), map_output.hip (export and publication), map_grow.hip (the growable map's rehash), map_ckpt.hip, map_query.hip and map_import.hip,
+// which are separate code objects.
 #pragma once
 #include <hip/hip_runtime.h>
 #include "map_kernels.h"
