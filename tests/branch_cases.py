@@ -65,6 +65,28 @@ def tie_clouds():
     return tuple(np.array(a, np.float32) for a in (sc, ss, qc, qs))
 
 
+NEGATIVE_FACES = ((0, -75.0), (1, -75.0), (2, -25.0))   # (axis, cube face) that negative_face_tie_clouds straddles
+
+
+def negative_face_tie_clouds():
+    """tie_clouds three times over, its x axis (the one that crosses x = 25 m) laid along x, y and z and moved so that it crosses x = -75 m,
+    y = -75 m and z = -25 m: the same ties (all coordinates stay multiples of 2^-7, every d2 is exact in f32 in any order of summation), one
+    seed point per voxel, and the corner rows have a node EXACTLY on the face — on -75 m the reference's cube rule (int() truncation and the
+    "< 0" correction, laser_mapping.cpp:643-652) puts it into the lower cube, where floor would not.  The sensor stays at the origin: the
+    cubes on both sides of every face are inside the valid 5 x 5 x 3 block."""
+    base = tie_clouds()
+    out = []
+    for cloud in base:
+        parts = []
+        for axis, face in NEGATIVE_FACES:
+            c = cloud.copy()
+            c[:, [0, axis]] = c[:, [axis, 0]]
+            c[:, axis] += np.float32(face - 24.75)   # the node at 24.75 m lands on the face
+            parts.append(c)
+        out.append(np.concatenate(parts))
+    return tuple(out)
+
+
 def six_way_walk(step=55.0):
     """Offsets (metres, one per sweep) added to the odometry translation handed to LaserMapping::input so that the 21 x 21 x 11 cube window
     (50 m cubes, centre index kept inside [3, size - 3), laser_mapping.cpp:218-402) rolls along every axis in BOTH directions: out to -440 m in

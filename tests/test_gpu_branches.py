@@ -83,11 +83,12 @@ def map_seed_and_queries():
     return B.tie_clouds()
 
 
-def run_map_ties(x, seq, oracle=False):
+def run_map_ties(x, seq, oracle=False, clouds=None):
     """Sweep 0 seeds the map with one point per voxel on a lattice (identity pose); sweep 1's scan features sit in the middle of lattice cells:
-    eight map points at ONE f32 distance per query, across the cube face at x = 25 m."""
+    eight map points at ONE f32 distance per query, across the cube face at x = 25 m (clouds: another tie_clouds-style tuple, as
+    tests/test_gpu_voxel_faces.py hands over for the negative faces)."""
     st = OracleStages(x) if oracle else DeviceStages(x)
-    seed_c, seed_s, qc, qs = map_seed_and_queries()
+    seed_c, seed_s, qc, qs = clouds or map_seed_and_queries()
     ident_q, ident_t = np.array([0.0, 0.0, 0.0, 1.0]), np.zeros(3)
     st.sr(seq.sweep(0)); st.lo(); st.map(corner=seed_c, surf=seed_s, q=ident_q, t=ident_t)
     st.sr(seq.sweep(1)); st.lo()

@@ -1,5 +1,8 @@
 """-m gpu: map import (vloam_map_import / vloam_map_import_device) — two map-frame clouds and a start transform into a fresh handle.
 
+This file is about the MERGE paths, not the keys: its clouds keep away from every voxel and cube face (points on faces, where the f32 voxel
+key differs from the f64 floor used here, are tests/test_gpu_voxel_faces.py's).
+
 What is checked: the per-voxel merge against a numpy model (f32 sums in input order, divided by f32(n)) and the CPU oracle's per-cube VoxelGrid,
 bit for bit, on a cloud that takes all three ordering paths; an exported map comes back bit for bit in a handle of another capacity and a growable
 one, and answers localisations and queries like the handle that built it; the first real mapping in an imported map is the builder's dry run;
@@ -9,6 +12,7 @@ import numpy as np
 import pytest
 
 from test_gpu_localize import bits, qmul, qrot, rot_z, same_record, staged_sweep
+from voxel_key_model import cube_abs
 
 pytestmark = pytest.mark.gpu
 
@@ -26,13 +30,6 @@ def torch_first():
 
 
 # ---------------------------------------------------------------------------------------------- the independent model
-def cube_abs(v):
-    """laser_mapping.cpp:207-216 / 643-652: C int() truncation plus the "< 0" correction, on f64"""
-    v = np.asarray(v, dtype=np.float64)
-    c = np.trunc((v + 25.0) / 50.0).astype(np.int64)
-    return c - (v + 25.0 < 0)
-
-
 def place_window(t):
     """laser_mapping.cpp:207-402 on an empty grid: the centre offsets laserCloudCen{Width,Height,Depth} for a sensor at t"""
     cen = CEN0.copy()

@@ -30,7 +30,7 @@ def test_save_map_then_localize_against_the_loaded_map(tmp_path):
                        capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stdout + r.stderr
     m = re.search(r"imported (\d+) corner / (\d+) surf map points", r.stdout)
-    assert m and 0 < int(m.group(1)) <= corner.shape[0] and 0 < int(m.group(2)) <= surf.shape[0], r.stdout   # (a centroid on a voxel face may merge with its neighbour)
+    assert m and 0 < int(m.group(1)) <= corner.shape[0] and 0 < int(m.group(2)) <= surf.shape[0], r.stdout   # (a centroid on a voxel face may merge with its neighbour: tests/test_gpu_voxel_faces.py keys such points)
     m = re.search(r"localised (\d+) sweeps against the imported map \((\d+) solved\)", r.stdout)
     assert m and int(m.group(1)) == n and int(m.group(2)) == n, r.stdout
     loc = kio.read_trajectory(tmp_path / "b" / "LOC0.txt")

@@ -136,3 +136,33 @@ def test_pipeline_cases_take_their_branches(orc, synth):
     assert ci.size + si.size > 50, "the tied neighbourhoods must still produce factors"
     G.run_map_empty_and_single_cell(o, seq, oracle=True)
     assert o.cloud(7).shape[0] == 0 and o.cloud(8).shape[0] == 1
+
+
+def test_knn_ties_across_the_negative_cube_faces(orc, sweeps):
+    """tests/branch_cases.py::negative_face_tie_clouds keeps tie_clouds' ties, and in the oracle's mapping stage (seeded on frame 0, queried on
+    frame 1, identity pose) the five neighbours of some query come from BOTH cubes of each of the faces x = -75 m, y = -75 m and z = -25 m,
+    the node exactly on -75 m out of the lower one."""
+    from voxel_key_model import cube_abs
+    seed_c, seed_s, qc, qs = B.negative_face_tie_clouds()
+    o = orc.Oracle(scan_line=16, with_mapping=True)
+    ident = dict(q=[0.0, 0.0, 0.0, 1.0], t=[0.0, 0.0, 0.0])
+    for k, (corner, surf) in enumerate(((seed_c, seed_s), (qc, qs))):
+        assert o.stage_sr(sweeps(16, 256, k)) == 0
+        o.stage_lo()
+        if k == 1:   # the map the queries meet: the seed points themselves, cube by cube
+            maps = [np.concatenate([p for p in (o.map_cube(kind, c) for c in range(21 * 21 * 11)) if p.shape[0]]) for kind in (0, 1)]
+        assert o.stage_map(corner=corner, surf=surf, **ident) == 0
+    assert o.map_num_outer() == 2
+    s = o.map_solve(0)
+    assert s["corner_num"] == qc.shape[0] and s["surf_num"] == qs.shape[0], "every query gives a factor"
+    for pts, seed, qq in ((maps[0], seed_c, qc), (maps[1], seed_s, qs)):
+        assert sorted(map(bytes, pts)) == sorted(map(bytes, seed))
+        idx, d2 = orc.knn(pts, qq[:, :3], 5, use_tree=True)
+        assert np.all(d2[:, 0] == d2[:, 1]) and np.all(d2[:, 2] == d2[:, 4]) and np.all(d2[:, 4] < 1.0)
+        for axis, face in B.NEGATIVE_FACES:
+            A = cube_abs(pts[idx, axis])                                  # [queries, 5]
+            both = A.min(axis=1) < A.max(axis=1)
+            near = np.abs(qq[:, axis] - face) < 1.0
+            assert (both & near).sum() >= 2, (axis, face)
+    on = seed_c[seed_c[:, 0] == np.float32(-75.0)]
+    assert on.shape[0] == 6 and np.all(cube_abs(on[:, 0]) == -2)
