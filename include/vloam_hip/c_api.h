@@ -679,7 +679,8 @@ vloam_status vloam_get_map_kind(vloam_handle* h, int kind, float* xyzi4, long lo
  *   the large stack tier (VLOAM_ERR_INVALID, "not offered"); more surf points than max_points (VLOAM_ERR_CAPACITY); null clouds outside the
  *   odometry-to-mapping window of a stage-wise, mapped sweep (VLOAM_ERR_ORDER).
  * Not offered: batched handles, the large stack tier, raw sweeps as input (run vloam_scan_registration on a second handle with
- *   with_mapping == 0 and take vloam_get_features(h, 2) / (h, 4)), several hypotheses per launch, information matrices of a localisation. */
+ *   with_mapping == 0 and take vloam_get_features(h, 2) / (h, 4)), information matrices of a localisation.  Several hypotheses per launch:
+ *   vloam_map_score_poses scores them, vloam_map_relocalize refines the best few with this chain (below). */
 enum {
   VLOAM_LOC_SOLVED = 1,          /* both outer rounds ran their solve */
   VLOAM_LOC_NOT_OPTIMIZED = 2,   /* "Map corner and surf num are not enough" (laser_mapping.cpp:448,631-635): q_map / t_map == q_guess / t_guess */
@@ -708,6 +709,74 @@ vloam_status vloam_map_localize(vloam_handle* h, const vloam_localize_options* o
                                 int n_surf, const double q[4], const double t[3], vloam_localize_result* out);
 vloam_status vloam_map_localize_device(vloam_handle* h, const vloam_localize_options* o, const void* d_corner, int n_corner, const void* d_surf,
                                        int n_surf, const double q[4], const double t[3], void* d_result);
+
+/* Pose scores: M candidate poses of one sweep's feature clouds scored against the map in one launch, and on top of them a coarse-to-fine
+ * relocalisation — for a caller who knows only roughly where the sensor is.  Opt-in by calling: a handle that never scores allocates and
+ * launches nothing of this, and no kernel of a sweep changes.
+ *   Clouds: what vloam_map_localize takes — packed (x, y, z, intensity) in the SENSOR frame, at most 7680 corner and 16777216 surf points.
+ *   Poses: q4t3[m] = (q xyzw, t) in the MAP frame, f64.  Per kind (0 corner, 1 surf) a radius and a point stride s >= 1: points 0, s, 2s, ...
+ *   Per pose m, kind and used point i: p = q_m * point_i + t_m as pointAssociateToMap computes it (Eigen q * v in f64, + t, each component
+ *   rounded to f32); the searched set is vloam_get_map_kind(h, kind) at that moment (corner points against the corner map, surf points
+ *   against the surf map); d2 = (dx*dx + dy*dy) + dz*dz in f32, every product and sum rounded on its own, as vloam_map_query defines it; dmin
+ *   the smallest d2 over the set; the point is a HIT when dmin <= radius*radius (f32 product).  A p with a non-finite component, or one beyond
+ *   +-1e6, is no hit and no error.  Record m: n_hit[kind], n_used[kind] (points of the kind that were scored, the same for every pose) and
+ *   sum_d2_q24[kind], the sum over the hits of (unsigned long long)(dmin * 16777216.0f) — an exact scaling and a truncation.  Hits and sums
+ *   are integers and accumulate as integers: a record is a function of the inputs alone, bit for bit from run to run.
+ *   Ranking, wherever a best pose is chosen: more hits (both kinds added) first, then the smaller sum (both kinds added), then the smaller index.
+ * Ordering: as vloam_map_query — both calls first enqueue what the handle still owes and run on the mapping stream behind the last mapping
+ *   (and any growth step).  vloam_map_score_poses works with temporary allocations, waits for that stream only and then returns a sticky map
+ *   error of the handle instead of VLOAM_OK; vloam_map_score_poses_device enqueues and returns: the four addresses are device memory (d_out: M
+ *   records), complete after vloam_sync, valid until then.
+ * Refusals, before the handle is looked at (VLOAM_ERR_INVALID, each with its own vloam_last_error()): null options or struct_size,
+ *   reserved != 0, a stride < 1, a radius that is <= 0 or not finite, a negative count, M < 0 or M > 65536, more than 7680 corner or 16777216
+ *   surf points, a null buffer with a positive count; host form only: a non-finite float in a cloud, a non-finite pose component, a quaternion
+ *   whose norm is off 1 by more than 1e-6 (the device form trusts its caller).  Then the handle: a radius above 16 leaves of its kind
+ *   (VLOAM_ERR_INVALID naming the bound in metres); with_mapping == 0 (VLOAM_ERR_ORDER); n_sessions > 1 (VLOAM_ERR_INVALID).  M == 0:
+ *   VLOAM_OK, nothing launched; both clouds empty: records of zeros.
+ * vloam_map_relocalize: candidates on a grid around (q_center, t_center) — index m = ix + n_xy[0]*(iy + n_xy[1]*(iz + n_z*iyaw)); the offset
+ *   along an axis with n steps and half extent e is -e + 2*e*i/(n-1) (0 when n == 1); t = t_center + (dx, dy, dz) along the map's axes,
+ *   q = q_yaw * q_center with q_yaw = (0, 0, sin(a/2), cos(a/2)), all f64 on the host; 1 <= n_candidates <= 65536.  The call scores every
+ *   candidate (coarse), takes the top_k by the ranking (candidate[j], coarse[j]), runs vloam_map_localize with pose_frame 1 from each
+ *   (refined[j] is what that call returns for that guess), scores the refined poses once more (fine[j]) and sets best to the first of the
+ *   ranking of fine[].  Synchronous, host clouds only; every refusal of vloam_map_localize and of vloam_map_score_poses applies (a handle of
+ *   the large stack tier can score but not relocalise).  Nothing the sequence can see changes, as with vloam_map_localize.
+ * Not offered: batched handles, scores in the odometry frame, roll and pitch in the grid, scores weighted by fit quality, a search with no
+ *   centre, starting a live sequence from the result in one call (vloam_map_import with the refined pose does that on a fresh handle). */
+typedef struct vloam_score_options {
+  int struct_size;     /* sizeof as compiled */
+  int stride[2];       /* [corner, surf] every stride-th point is scored, >= 1 */
+  int reserved;        /* 0 */
+  float radius[2];     /* [corner, surf] metres, > 0, finite; <= 16 leaves of the kind */
+} vloam_score_options;
+typedef struct vloam_pose_score {   /* 32 bytes */
+  int n_hit[2];                       /* [corner, surf] */
+  int n_used[2];                      /* points scored per kind */
+  unsigned long long sum_d2_q24[2];   /* sum over the hits of (unsigned long long)(dmin * 2^24) */
+} vloam_pose_score;
+void vloam_default_score_options(vloam_score_options* o);   /* stride 1, 1; radius 1.0, 1.0 */
+vloam_status vloam_map_score_poses(vloam_handle* h, const vloam_score_options* o, const float* corner_xyzi4, int n_corner, const float* surf_xyzi4,
+                                   int n_surf, const double* q4t3, int M, vloam_pose_score* out);
+vloam_status vloam_map_score_poses_device(vloam_handle* h, const vloam_score_options* o, const void* d_corner, int n_corner, const void* d_surf,
+                                          int n_surf, const void* d_q4t3, int M, void* d_out);
+typedef struct vloam_relocalize_options {   /* 88 bytes */
+  int struct_size;          /* sizeof as compiled */
+  int n_xy[2], n_z, n_yaw;  /* steps per axis, >= 1; their product is 1 .. 65536 */
+  int top_k;                /* 1 .. 8 candidates refined */
+  int reserved[2];          /* 0 */
+  double half_extent[3];    /* metres, >= 0: the grid spans t_center -+ half_extent */
+  double half_yaw;          /* radians, 0 .. pi */
+  vloam_score_options score;
+} vloam_relocalize_options;
+typedef struct vloam_relocalize_result {   /* 2288 bytes */
+  int n_candidates, n_refined, best /* index into the arrays below */, pad;
+  int candidate[8];                    /* grid index of the j-th best candidate */
+  vloam_pose_score coarse[8];          /* its score */
+  vloam_localize_result refined[8];    /* vloam_map_localize from it (q_guess / t_guess: the candidate) */
+  vloam_pose_score fine[8];            /* the score of refined[j].q_map / t_map */
+} vloam_relocalize_result;
+void vloam_default_relocalize_options(vloam_relocalize_options* o);   /* 9 x 9 x 1 x 9 steps over +-2 m, +-10 degrees; top_k 4; default score options */
+vloam_status vloam_map_relocalize(vloam_handle* h, const vloam_relocalize_options* o, const float* corner_xyzi4, int n_corner, const float* surf_xyzi4,
+                                  int n_surf, const double q_center[4], const double t_center[3], vloam_relocalize_result* out);
 
 /* Map import: a FRESH handle is given two point clouds in the map frame — the corner map and the surf map, packed (x, y, z, intensity), e.g. what
  * vloam_get_map_kind(h, 0 / 1) of any build of the library returned — and the map<-odometry transform the sequence starts with.  Afterwards it

@@ -98,23 +98,65 @@ def read_start_pose(a):
     return q / np.linalg.norm(q), np.array(v[4:])
 
 
+def parse_relocalize(arg):
+    """--relocalize "EXT_XY STEP_XY YAW_DEG STEP_DEG [TOP_K]" -> keyword arguments of Handle.map_relocalize: a grid of +-EXT_XY metres in x and y
+    in steps of STEP_XY, +-YAW_DEG degrees of yaw in steps of STEP_DEG, the TOP_K (default 4) best candidates refined."""
+    v = arg.split()
+    if len(v) not in (4, 5):
+        sys.exit("--relocalize takes \"EXT_XY STEP_XY YAW_DEG STEP_DEG [TOP_K]\"")
+    ext, step, yaw, dstep = (float(x) for x in v[:4])
+    if ext < 0 or yaw < 0 or yaw > 180 or (ext > 0 and step <= 0) or (yaw > 0 and dstep <= 0):
+        sys.exit("--relocalize: extents are >= 0 (yaw at most 180 degrees), steps > 0")
+    n_xy = int(round(2.0 * ext / step)) + 1 if ext > 0 else 1
+    n_yaw = int(round(2.0 * yaw / dstep)) + 1 if yaw > 0 else 1
+    return dict(n_xy=(n_xy, n_xy), n_z=1, n_yaw=n_yaw, half_extent=(ext, ext, 0.0), half_yaw=float(np.deg2rad(yaw)), top_k=int(v[4]) if len(v) == 5 else 4)
+
+
+def score_json(s):
+    return {"n_hit": s["n_hit"].tolist(), "n_used": s["n_used"].tolist(), "sum_d2_q24": [int(x) for x in s["sum_d2_q24"]]}
+
+
 def localize_only(vl, kio, tf, hd, a, load_sweep, n, first, origin, what):
     """--resume CKPT / --load-map DIR with --localize-only: every sweep of the input against the map, each from the previous result; the first
-    one from `first` (the restored sequence's last map pose / the start pose).  The feature clouds come from a second handle without mapping
-    (scan registration only); the map is never updated."""
+    one from `first` (the restored sequence's last map pose / the start pose) — or, with --relocalize, relocalised on a grid of candidates
+    around it (vloam_map_relocalize).  The feature clouds come from a second handle without mapping (scan registration only); the map is
+    never updated.  --metrics: one JSON line per sweep (flags, factors, the localised pose); the first line of a relocalised run also carries
+    the winning candidate, its coarse and fine scores and the refined pose."""
     sr = vl.Handle(a.device, with_mapping=0, **({"max_ring_points": a.max_ring_points} if a.max_ring_points else {}))
     q, t = first[0].copy(), first[1].copy()
     tf.MO2Cam0StartFrame(origin[0], origin[1], 0)   # rows are expressed in the start frame of the MAP's sequence, like MO0.txt of the saving run
     rows, solved = [], 0
+    mf = open(a.metrics, "w") if a.metrics else None
     for count in range(n):
         sr.reset_frame()
         sr.scan_registration(load_sweep(count))
-        r = hd.map_localize(sr.features(2), sr.features(4), q / np.linalg.norm(q), t, pose_frame=1)
+        corner, surf = sr.features(2), sr.features(4)
+        reloc = None
+        if count == 0 and a.relocalize:
+            grid = parse_relocalize(a.relocalize)
+            rr = hd.map_relocalize(corner, surf, q / np.linalg.norm(q), t, **grid)
+            b = rr["best"]
+            r = rr["refined"][b]
+            reloc = {"n_candidates": rr["n_candidates"], "n_refined": rr["n_refined"], "best": b, "candidate": int(rr["candidate"][b]),
+                     "candidates": rr["candidate"].tolist(), "guess": [float(x) for x in list(r["q_guess"]) + list(r["t_guess"])],
+                     "coarse": score_json(rr["coarse"][b]), "fine": score_json(rr["fine"][b]),
+                     "refined_pose": [float(x) for x in list(r["q_map"]) + list(r["t_map"])]}
+            print("relocalised sweep 0: candidate %d of %d, start pose \"%s\"" % (reloc["candidate"], reloc["n_candidates"], " ".join("%.17g" % x for x in reloc["refined_pose"])))
+        else:
+            r = hd.map_localize(corner, surf, q / np.linalg.norm(q), t, pose_frame=1)
         if r["error_bits"]:
             print("sweep %d: error bits %d" % (count, r["error_bits"]), file=sys.stderr)
         solved += 1 if r["flags"] & vl.LOC_SOLVED else 0
         q, t = r["q_map"], r["t_map"]
         rows.append(tf.MO2Cam0StartFrame(q, t, count + 1))
+        if mf:
+            rec = {"frame": count, "flags": int(r["flags"]), "error_bits": int(r["error_bits"]), "n_factors": np.asarray(r["n_factors"]).tolist(),
+                   "loc_pose": [float(x) for x in list(q) + list(t)]}
+            if reloc:
+                rec["relocalize"] = reloc
+            mf.write(json.dumps(rec) + "\n")
+    if mf:
+        mf.close()
     sr.close()
     os.makedirs(a.out, exist_ok=True)
     kio.write_trajectory(os.path.join(a.out, "LOC0.txt"), rows)
@@ -168,6 +210,10 @@ def main():
                                                       "with --localize-only as --resume: every sweep is localised against the imported map, which is never updated")
     ap.add_argument("--start-pose", metavar="\"qx qy qz qw tx ty tz\"", help="with --load-map: the map<-odometry transform the sequence starts with "
                                                                            "(default: DIR/start_pose.txt if there is one, else the map's origin)")
+    ap.add_argument("--relocalize", metavar="\"EXT_XY STEP_XY YAW_DEG STEP_DEG [TOP_K]\"",
+                    help="with --load-map / --resume and --localize-only: the first sweep is relocalised around the start pose instead of localised from it "
+                         "(vloam_map_relocalize: candidates every STEP_XY metres within +-EXT_XY in x and y and every STEP_DEG degrees within +-YAW_DEG of yaw, "
+                         "the TOP_K best — default 4 — refined); the first --metrics line carries the winning candidate, its scores and the refined pose")
     ap.add_argument("--imu-T-velo", help="16 numbers, row major (default: KITTI 2011_09_26 extrinsics, approx.)")
     ap.add_argument("--imu-T-cam0", help="16 numbers, row major")
     a = ap.parse_args()
@@ -205,6 +251,11 @@ def main():
             sys.exit("%d sweeps but only %d images in %s" % (n, len(real_images), a.image_dir))
     if a.localize_only and not (a.resume or a.load_map):
         sys.exit("--localize-only needs a map: add --resume CKPT or --load-map DIR")
+    if a.relocalize and not a.localize_only:
+        sys.exit("--relocalize goes with --localize-only: an import fixes the start transform before any sweep arrives, so a SEQUENCE cannot start from a "
+                 "relocalised pose in one run; relocalise with --localize-only, then start the sequence with --load-map DIR --start-pose and the pose it printed")
+    if a.relocalize:
+        parse_relocalize(a.relocalize)
     if a.resume and a.load_map:
         sys.exit("--resume and --load-map both fill a fresh handle: choose one")
     if a.start_pose and not a.load_map:

@@ -79,6 +79,33 @@ LOCALIZE_RESULT_DTYPE = np.dtype([
 LOC_SOLVED, LOC_NOT_OPTIMIZED, LOC_WOULD_ROLL, LOC_DEGRADED = 1, 2, 4, 8
 
 
+class ScoreOptions(C.Structure):
+    """vloam_score_options (c_api.h; vloam_map_score_poses / vloam_map_score_poses_device)."""
+    _fields_ = [("struct_size", C.c_int), ("stride", C.c_int * 2), ("reserved", C.c_int), ("radius", C.c_float * 2)]
+
+
+class RelocalizeOptions(C.Structure):
+    """vloam_relocalize_options (c_api.h; vloam_map_relocalize)."""
+    _fields_ = [("struct_size", C.c_int), ("n_xy", C.c_int * 2), ("n_z", C.c_int), ("n_yaw", C.c_int), ("top_k", C.c_int), ("reserved", C.c_int * 2),
+                ("half_extent", C.c_double * 3), ("half_yaw", C.c_double), ("score", ScoreOptions)]
+
+
+# vloam_pose_score (c_api.h): 4 ints then 2 unsigned 64-bit sums, 32 bytes
+POSE_SCORE_DTYPE = np.dtype([("n_hit", "<i4", (2,)), ("n_used", "<i4", (2,)), ("sum_d2_q24", "<u8", (2,))])
+# vloam_relocalize_result (c_api.h): 12 ints, 8 scores, 8 localisation records, 8 scores, 2288 bytes
+RELOCALIZE_RESULT_DTYPE = np.dtype([
+    ("n_candidates", "<i4"), ("n_refined", "<i4"), ("best", "<i4"), ("pad", "<i4"), ("candidate", "<i4", (8,)),
+    ("coarse", POSE_SCORE_DTYPE, (8,)), ("refined", LOCALIZE_RESULT_DTYPE, (8,)), ("fine", POSE_SCORE_DTYPE, (8,))])
+assert C.sizeof(ScoreOptions) == 24 and C.sizeof(RelocalizeOptions) == 88 and POSE_SCORE_DTYPE.itemsize == 32 and RELOCALIZE_RESULT_DTYPE.itemsize == 2288
+SCORE_MAX_POSES = 65536
+
+
+def score_rank(scores):
+    """The ranking of c_api.h over POSE_SCORE_DTYPE records: indices, best first (more hits, then the smaller sum, then the smaller index)."""
+    s = np.asarray(scores)
+    return np.lexsort((np.arange(s.shape[0]), s["sum_d2_q24"].sum(axis=1, dtype=np.uint64), -s["n_hit"].sum(axis=1, dtype=np.int64)))
+
+
 class MapImportOptions(C.Structure):
     """vloam_map_import_options (c_api.h; vloam_map_import / vloam_map_import_device)."""
     _fields_ = [("struct_size", C.c_int), ("reserved", C.c_int * 3), ("q_wmap_wodom", C.c_double * 4), ("t_wmap_wodom", C.c_double * 3)]
@@ -809,6 +836,63 @@ class Handle:
                 ptr[k], n[k] = C.c_void_p(c.data_ptr() or result.data_ptr()), int(c.shape[0])   # (an empty tensor has no address: any non-null one will do)
         self._chk(self.L.vloam_map_localize_device(self.h, C.byref(opt), ptr[0], n[0], ptr[1], n[1], None if q is None else _fp(q),
                                                    None if t is None else _fp(t), C.c_void_p(result.data_ptr())))
+
+    def _score_options(self, stride, radius):
+        opt = ScoreOptions()
+        self.L.vloam_default_score_options(C.byref(opt))
+        opt.stride[:] = [int(v) for v in stride]
+        opt.radius[:] = [float(v) for v in radius]
+        return opt
+
+    def map_score_poses(self, corner, surf, poses, stride=(1, 1), radius=(1.0, 1.0)):
+        """vloam_map_score_poses: corner / surf (float32 [n, 4], sensor frame, what map_localize takes; None: empty) under every row of poses
+        (float64 [M, 7]: q xyzw, t in the map frame) against the corner / surf map — per pose the points of each kind whose nearest map point
+        lies within radius[kind] (every stride[kind]-th point is scored) and the quantised sum of their squared distances, as an array of
+        POSE_SCORE_DTYPE [M].  Runs behind everything handed over so far and waits for the mapping stream only."""
+        opt = self._score_options(stride, radius)
+        c, s = self._cloud_arg(corner), self._cloud_arg(surf)
+        p = np.ascontiguousarray(poses, dtype=np.float64).reshape(-1, 7)
+        out = np.zeros(max(p.shape[0], 1), dtype=POSE_SCORE_DTYPE)
+        self._chk(self.L.vloam_map_score_poses(self.h, C.byref(opt), c[1], c[2], s[1], s[2], _fp(p), int(p.shape[0]), _fp(out)))
+        return out[:p.shape[0]]
+
+    def map_score_poses_device(self, corner, surf, poses, out, stride=(1, 1), radius=(1.0, 1.0)):
+        """vloam_map_score_poses_device: the same with torch tensors on the device — corner / surf float32 [n, 4] (or None), poses float64 [M, 7],
+        out a uint8 tensor of M * POSE_SCORE_DTYPE.itemsize bytes.  Enqueues and returns: the records are complete after sync(), the tensors
+        must stay alive until then."""
+        opt = self._score_options(stride, radius)
+        M = int(poses.shape[0])
+        assert poses.is_cuda and poses.is_contiguous() and poses.element_size() == 8 and poses.dtype.is_floating_point and poses.shape[-1] == 7
+        assert out.is_cuda and out.is_contiguous() and out.numel() * out.element_size() >= M * POSE_SCORE_DTYPE.itemsize
+        ptr, n = [None, None], [0, 0]
+        for k, c in enumerate((corner, surf)):
+            if c is not None and c.shape[0] > 0:
+                assert c.is_cuda and c.is_contiguous() and c.dtype.is_floating_point and c.element_size() == 4 and c.shape[-1] == 4
+                ptr[k], n[k] = C.c_void_p(c.data_ptr()), int(c.shape[0])
+        self._chk(self.L.vloam_map_score_poses_device(self.h, C.byref(opt), ptr[0], n[0], ptr[1], n[1], C.c_void_p(poses.data_ptr()) if M else None, M,
+                                                      C.c_void_p(out.data_ptr()) if M else None))
+
+    def map_relocalize(self, corner, surf, q_center, t_center, n_xy=(9, 9), n_z=1, n_yaw=9, half_extent=(2.0, 2.0, 0.0), half_yaw=np.deg2rad(10.0),
+                       top_k=4, stride=(1, 1), radius=(1.0, 1.0)):
+        """vloam_map_relocalize: a grid of n_xy[0] x n_xy[1] x n_z x n_yaw candidate poses around (q_center, t_center) — t_center -+ half_extent
+        along the map's axes, -+ half_yaw about its +z — scored against the map, the top_k refined by map_localize (pose_frame 1) and scored
+        again.  Returns the fields of vloam_relocalize_result as a dict: candidate / coarse / fine arrays of n_refined entries, refined a list
+        of map_localize dicts, best the index of the winner in them.  Nothing of the sequence changes."""
+        opt = RelocalizeOptions()
+        self.L.vloam_default_relocalize_options(C.byref(opt))
+        opt.n_xy[:] = [int(v) for v in n_xy]
+        opt.n_z, opt.n_yaw, opt.top_k, opt.half_yaw = int(n_z), int(n_yaw), int(top_k), float(half_yaw)
+        opt.half_extent[:] = [float(v) for v in half_extent]
+        opt.score = self._score_options(stride, radius)
+        c, s = self._cloud_arg(corner), self._cloud_arg(surf)
+        q, t = np.ascontiguousarray(q_center, dtype=np.float64), np.ascontiguousarray(t_center, dtype=np.float64)
+        out = np.zeros(1, dtype=RELOCALIZE_RESULT_DTYPE)
+        self._chk(self.L.vloam_map_relocalize(self.h, C.byref(opt), c[1], c[2], s[1], s[2], _fp(q), _fp(t), _fp(out)))
+        r, k = out[0], int(out[0]["n_refined"])
+        refined = [{f: (r["refined"][j][f].copy() if r["refined"][j][f].ndim else r["refined"][j][f].item()) for f in LOCALIZE_RESULT_DTYPE.names if f != "pad"}
+                   for j in range(k)]
+        return dict(n_candidates=int(r["n_candidates"]), n_refined=k, best=int(r["best"]), candidate=r["candidate"][:k].copy(), coarse=r["coarse"][:k].copy(),
+                    refined=refined, fine=r["fine"][:k].copy())
 
     def _import_options(self, q_wmap_wodom, t_wmap_wodom):
         opt = MapImportOptions()

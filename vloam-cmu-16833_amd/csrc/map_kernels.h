@@ -260,6 +260,11 @@ vloam_status map_counts(MapContext* m, long long c[16]);
 // selected session, kind 0 corner map / 1 surf map / 2 both.  Enqueue only, no allocation: d_xyzi4 [n][k] float4, d_d2 [n][k], d_count [n].
 vloam_status map_query_enqueue(MapContext* m, hipStream_t st, int kind, int k, float radius, const void* d_xyz_pad4, int n, void* d_xyzi4, void* d_d2,
                                void* d_count);
+// ---- map_score.hip (a code object of its own): hits and quantised nearest-neighbour distances of n_corner / n_surf sensor-frame points (device
+// addresses, every stride[kind]-th point) under M poses (device address, [M][7] f64: q xyzw, t) against the corner / surf map of a single-sequence
+// handle.  Enqueue only, no allocation: d_out [M] vloam_pose_score, zeroed and filled on st.
+vloam_status map_score_enqueue(MapContext* m, hipStream_t st, const void* d_corner, int n_corner, const void* d_surf, int n_surf, const int stride[2],
+                               const float radius[2], const double* d_q4t3, int M, void* d_out);
 // ---- map_localize.hip (a code object of its own) + map_localize_enqueue in map_kernels.hip, beside map_enqueue: a dry run of the mapping chain
 // on scratch state (vloam_map_localize).  Single-sequence handles of the default stack tier.  corner / surf: device clouds (sensor frame), or both
 // null: stack set `set` as map_stack_enqueue left it, read-only.  row7: device address of an odometry pose (q xyzw, t), or null: pose7 (host

@@ -1,5 +1,5 @@
 // The voxel tables of the map as device code sees them: hash, voxel key, record access, occupancy blocks.  Shared by map_kernels.hip (the
-// sweep's kernels), map_output.hip (export and publication), map_grow.hip (the growable map's rehash), map_ckpt.hip, map_query.hip and map_import.hip,
+// sweep's kernels), map_output.hip (export and publication), map_grow.hip (the growable map's rehash), map_ckpt.hip, map_query.hip, map_score.hip and map_import.hip,
 // which are separate code objects.
 #pragma once
 #include <hip/hip_runtime.h>
