@@ -9,7 +9,10 @@ import pytest
 
 import branch_cases
 import pose_score_model as model
+import test_gpu_voxel_faces as voxel_faces     # the window placements of test 6: ENDS
 import test_gpu_window_rolls as window_rolls   # the drive of test 3: its walk and its sweep sizes
+import voxel_key_model as V
+from test_gpu_map_import import place_window
 
 pytestmark = pytest.mark.gpu
 F32 = np.float32
@@ -304,3 +307,62 @@ def test_scores_and_relocalisations_leave_the_sequence_alone(vl, scene):
     a, b = drive(True), drive(False)
     assert a[0].shape == (6, 14) and bits(a[0]) == bits(b[0]), "the sweep behind a score and a relocalisation: its pose"
     assert bits(a[1]) == bits(b[1]), "... and the map"
+
+
+# ------------------------------------------------------------------------------------------------ 6. the ends of the key range
+END_CUBES = {"x+511": (511, 0, 0), "y-512,z-128": (0, -512, -128)}   # the last cubes the voxel key holds, where voxel_faces.ENDS put the window's edge
+
+
+def end_cube_case(end):
+    """Pure numpy: per kind ten points to import — eight in the end cube, of which three lie 0.3, 0.6 and 2 m inside its outer faces and one
+    0.3 m inside the opposite ones, and one 0.4 m beyond those, in the neighbouring cube —, per kind a cloud of 16 (those points seen from the
+    cube's centre and six strays) and 13 poses that put the cloud on the points, 0.3 to 1.1 m off them (towards and across the outer faces
+    too), turn it about the centre, and move it past the end of the range and into the neighbouring cube."""
+    rng = np.random.default_rng(24)
+    A = np.array(END_CUBES[end], np.float64)
+    centre, out = 50.0 * A, np.sign(A)   # out: towards the end of the range on the axes that have one here, 0 on the others
+    local, cloud = [], []
+    for kind in (0, 1):
+        s = rng.uniform(-20.0, 20.0, (10, 3))
+        for j, d in enumerate((0.3, 0.6, 2.0)):
+            s[j] = np.where(out != 0, out * (25.0 - d), s[j])
+        s[3] = np.where(out != 0, -out * (25.0 - 0.3), s[3])
+        s[4] = np.where(out != 0, -out * (25.0 + 0.4), s[3])
+        s = s.astype(F32).astype(np.float64)
+        local.append(s)
+        c = np.concatenate([s, rng.uniform(-20.0, 20.0, (6, 3))])
+        cloud.append(np.concatenate([c, np.arange(16.0)[:, None]], axis=1).astype(F32))
+    pts = [np.concatenate([(centre + s).astype(F32), np.arange(10, dtype=F32)[:, None]], axis=1) for s in local]
+    offs = [(0, 0, 0), (0.3, 0, 0), (0, -0.6, 0), (0, 0, 0.9), (0.6, 0.6, 0.4), (0.6, 0.6, 0.6), (1.1, 0, 0), 0.5 * out, -0.5 * out]
+    poses = [np.concatenate([IDENT[:4], centre + np.asarray(o, np.float64)]) for o in offs]
+    poses += [np.concatenate([model.yaw_quat(np.deg2rad(a)), centre]) for a in (2.0, 3.5)]
+    poses += [np.concatenate([IDENT[:4], centre + 60.0 * out]), np.concatenate([IDENT[:4], centre - 50.0 * out])]
+    return pts, cloud, np.ascontiguousarray(poses)
+
+
+@pytest.mark.parametrize("end", sorted(voxel_faces.ENDS))
+def test_scores_at_the_ends_of_the_key_range(vl, end):
+    """Scores in the last cubes the voxel key holds (absolute cube +511 on x; -512 on y and -128 on z), which are the window's last here, so
+    every cube beyond the key's range is outside the window too: this checks the keys, boxes and cube ranges at the extreme cube numbers, not
+    the walk's key-range bound by itself (that takes a window that reaches past the range, as in
+    tests/test_gpu_voxel_faces.py::test_points_beyond_the_key_range).  Built with map_import, as there."""
+    t = voxel_faces.ENDS[end]
+    pts, cloud, poses = end_cube_case(end)
+    assert poses.shape[0] < 16
+    h = vl.Handle(0, with_mapping=1, max_frames=4)
+    h.map_import(pts[0], pts[1], t_wmap_wodom=t)
+    assert list(h.map_state()["cen"]) == list(place_window(t))
+    maps = (h.get_map_kind(0), h.get_map_kind(1))
+    for k in (0, 1):
+        assert maps[k].shape[0] == 10, "every imported point is inside the window and a map point of its own"
+        assert (V.cube_abs(maps[k][:, :3]) == END_CUBES[end]).all(axis=1).sum() >= 8, "the last cube holds map points"
+    want = model.score_poses(maps, cloud[0], cloud[1], poses)
+    print("%s: model hits per pose %s of %s" % (end, want["n_hit"].tolist(), want["n_used"][0].tolist()))
+    # the model itself tells the poses apart: everything on the points, partial hits off them, nothing beyond the end of the range
+    assert (want["n_hit"][0] >= 10).all() and not want["n_hit"][11].any() and want["n_hit"][7].sum() >= 16
+    assert (want["n_hit"] < want["n_used"]).all() and len(set(want["n_hit"].sum(axis=1).tolist())) >= 4
+    got = h.map_score_poses(cloud[0], cloud[1], poses)
+    assert bits(got) == bits(want), "device %s model %s" % (got, want)
+    assert bits(device_scores(vl, h, cloud[0], cloud[1], poses)) == bits(want), "device form"
+    h.sync()
+    h.close()

@@ -26,30 +26,30 @@ __global__ void k_map_register(const float4* __restrict__ cloud, const FrameScal
 // was outside the valid block follow un-merged, in arrival order (sweep, then stack order) — the raw point records of k_map_finalize; a
 // centroid that became raw point number one (stamp 0) keeps its place in the voxel-ordered part.  The device compacts the live records
 // with their order key; the final ordering of this OUTPUT path is a host sort of the compacted list.
+
+// Is the record at a table slot a point of /laser_cloud_map (the window's centre cube at cW, cH, cD), and then its order key and the point:
+// the export's and the publication's one rule
+__device__ __forceinline__ bool pub_row(const RecVal& v, int cW, int cH, int cD, int kind, u64* okey, float4* p) {
+  if (v.key == 0ull || v.count == 0) return false;
+  if (key_seq(v.key) == 0 && rec_raw(v.count)) return false;   // a raw voxel is published through its point records
+  int Ai, Aj, Ak;
+  unpack_cube(v.key, &Ai, &Aj, &Ak);
+  const int i = Ai + cW, j = Aj + cH, k = Ak + cD;
+  if (i < 0 || i >= kCubeW || j < 0 || j >= kCubeH || k < 0 || k >= kCubeD) return false;
+  *okey = rec_order_key(v, i + kCubeW * j + kCubeW * kCubeH * k, kind);
+  *p = rec_point(v);
+  return true;
+}
+
 struct ExportRow { u64 okey; float x, y, z, w; };
 __global__ __launch_bounds__(256) void k_map_export(VoxelTable T, const MapState* __restrict__ ms, int kind, ExportRow* __restrict__ out, long long cap,
                                                     unsigned long long* n_out) {
   const int cW = ms->cenW, cH = ms->cenH, cD = ms->cenD;
   for (unsigned s = blockIdx.x * 256 + threadIdx.x; s <= T.mask; s += gridDim.x * 256) {
-    const RecVal v = rec_load(&T.rec[s]);
-    if (v.key == 0ull || v.count == 0) continue;
-    const int seq = key_seq(v.key);
-    if (seq == 0 && rec_raw(v.count)) continue;   // a raw voxel is published through its point records
-    int Ai, Aj, Ak;
-    unpack_cube(v.key, &Ai, &Aj, &Ak);
-    const int i = Ai + cW, j = Aj + cH, k = Ak + cD;
-    if (i < 0 || i >= kCubeW || j < 0 || j >= kCubeH || k < 0 || k >= kCubeD) continue;
-    const u64 cube = (u64)(i + kCubeW * j + kCubeW * kCubeH * k);
-    const u64 lx = (u64)key_lx(v.key), ly = (u64)key_ly(v.key), lz = (u64)key_lz(v.key);
-    const bool tail = seq != 0 && v.pend_cnt != 0;   // an un-merged arrival: behind the voxel-ordered part, by arrival stamp
-    ExportRow r;
-    r.okey = (cube << 50) | ((u64)kind << 49) | ((u64)(tail ? 1 : 0) << 48) | (tail ? (u64)(unsigned)v.pend_cnt : ((lz << (2 * kVoxBits)) | (ly << kVoxBits) | lx));
-    const int n = seq ? 1 : rec_n(v.count);
-    const float nn = (float)n;
-    r.x = n > 1 ? v.sum.x / nn : v.sum.x; r.y = n > 1 ? v.sum.y / nn : v.sum.y; r.z = n > 1 ? v.sum.z / nn : v.sum.z;
-    r.w = n > 1 ? v.sum.w / nn : v.sum.w;
+    u64 okey; float4 p;
+    if (!pub_row(rec_load(&T.rec[s]), cW, cH, cD, kind, &okey, &p)) continue;
     const unsigned long long o = atomicAdd(n_out, 1ull);
-    if ((long long)o < cap) out[o] = r;
+    if ((long long)o < cap) out[o] = ExportRow{okey, p.x, p.y, p.z, p.w};
   }
 }
 
@@ -109,7 +109,7 @@ vloam_status map_get_cloud(MapContext* m0, hipStream_t st, int which, const SRBu
 
 // ---------------------------------------------------------------------------------------------- published clouds (MapPub, map_kernels.h)
 // /laser_cloud_map ordered on the device, on the mapping stream, behind k_map_finalize of the publishing sweep.  The order key is
-// k_map_export's: | cube 13 | kind 1 | tail 1 | 16 zero bits | voxel (lz, ly, lx) or arrival stamp, 32 |; its top 14 bits name the bucket.
+// k_map_export's (pub_row; rec_order_key of map_table.h); its top 14 bits, cube and kind, name the bucket.
 //   k_map_pub_count    both tables: live records per bucket
 //   k_map_pub_scan     exclusive scan of the 9 702 counts, the publication's header (count, overflow), cursors cleared
 //   k_map_pub_scatter  both tables again: every record into its bucket's segment (place inside the segment: arrival, fixed up next)
@@ -117,24 +117,6 @@ vloam_status map_get_cloud(MapContext* m0, hipStream_t st, int which, const SRBu
 //   k_map_pub_rank     the longer segments: a record's place is the number of smaller keys in its segment
 // Keys are unique (one record per cube, kind and voxel, one per arrival stamp), so the result is the host sort's of map_export, byte for byte.
 // A publication that does not fit the capacity writes the header only.
-__device__ __forceinline__ bool pub_row(const RecVal& v, int cW, int cH, int cD, int kind, u64* okey, float4* p) {
-  if (v.key == 0ull || v.count == 0) return false;
-  const int seq = key_seq(v.key);
-  if (seq == 0 && rec_raw(v.count)) return false;   // a raw voxel is published through its point records
-  int Ai, Aj, Ak;
-  unpack_cube(v.key, &Ai, &Aj, &Ak);
-  const int i = Ai + cW, j = Aj + cH, k = Ak + cD;
-  if (i < 0 || i >= kCubeW || j < 0 || j >= kCubeH || k < 0 || k >= kCubeD) return false;
-  const u64 cube = (u64)(i + kCubeW * j + kCubeW * kCubeH * k);
-  const u64 lx = (u64)key_lx(v.key), ly = (u64)key_ly(v.key), lz = (u64)key_lz(v.key);
-  const bool tail = seq != 0 && v.pend_cnt != 0;
-  *okey = (cube << 50) | ((u64)kind << 49) | ((u64)(tail ? 1 : 0) << 48) | (tail ? (u64)(unsigned)v.pend_cnt : ((lz << (2 * kVoxBits)) | (ly << kVoxBits) | lx));
-  const int n = seq ? 1 : rec_n(v.count);
-  const float nn = (float)n;
-  p->x = n > 1 ? v.sum.x / nn : v.sum.x; p->y = n > 1 ? v.sum.y / nn : v.sum.y; p->z = n > 1 ? v.sum.z / nn : v.sum.z;
-  p->w = n > 1 ? v.sum.w / nn : v.sum.w;
-  return true;
-}
 __device__ __forceinline__ int pub_bucket(u64 okey) { return (int)(okey >> 49); }   // cube * 2 + kind < kPubBuckets
 
 __global__ __launch_bounds__(256) void k_map_pub_count(VoxelTable T0, VoxelTable T1, const MapState* __restrict__ ms, int* __restrict__ cnt, size_t ss) {

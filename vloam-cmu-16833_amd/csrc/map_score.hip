@@ -1,10 +1,9 @@
 // Pose scoring on gfx950: M candidate poses x N feature points x one nearest-neighbour lookup in the map (vloam_map_score_poses /
-// vloam_map_score_poses_device; the first step of vloam_map_relocalize).  A code object of its own, with its own text of the walk through the
-// occupancy-block index (map_table.h and map_device.h are all it shares with the sweep's kernels, following map_query.hip): a handle that never
-// scores launches nothing of this, and no kernel of a sweep changes.
+// vloam_map_score_poses_device; the first step of vloam_map_relocalize).  A code object of its own (map_table.h and map_device.h are all it
+// shares with the sweep's kernels): a handle that never scores launches nothing of this, and no kernel of a sweep changes.
 //
 // Per pose m, kind and used point i (points 0, s, 2s, ... of the kind's cloud): p = associate_to_map(point_i, q_m, t_m), the searched set is
-// k_map_export's for that kind (map_query.hip), d2 = (dx*dx + dy*dy) + dz*dz in f32 with every product and sum rounded on its own, dmin the
+// k_map_export's for that kind (map_walk.h), d2 = (dx*dx + dy*dy) + dz*dz in f32 with every product and sum rounded on its own, dmin the
 // smallest d2; a hit when dmin <= r*r.  A record counts the hits and sums (u64)(dmin * 2^24) over them: integers, accumulated in registers,
 // over the wave by shuffles and into the record by integer atomics, so a record is a function of the inputs alone whatever the launch geometry.
 //
@@ -12,12 +11,11 @@
 // tile's points in LDS once, and each of its four waves takes every fourth pose of the tile into registers.  A group of kScG = 8 lanes covers
 // one point's boxes (at radius 1 m and the default leaves a box is 27 blocks: three to four rounds of eight busy lanes, where 32 lanes would
 // idle), so a wave scores eight points of one pose at a time and issues one 64-bit and one 32-bit atomic per pose and tile.
-// The box has one voxel of slack on every side, one piece per cube for voxels that straddle a 50 m cube face, and every block of it is
-// visited: enumerating too much is harmless (a candidate counts by its distance), nothing the box can hold is left out.
+// The walk through the occupancy-block index — the box as per-axis pieces, the blocks, the voxel records, and why nothing the box can hold is
+// left out — is map_walk.h's, shared with map_query.hip; every block of the box is visited (no early-out).
 #include <hip/hip_runtime.h>
 #include <math.h>
-#include "map_table.h"
-#include "map_device.h"
+#include "map_walk.h"
 
 namespace vloam {
 
@@ -27,29 +25,7 @@ constexpr int kScG = 8;                    // lanes per (pose, point) pair
 constexpr int kScGroups = 256 / kScG;      // 32 groups per workgroup, 8 per wave
 constexpr int kScPoints = 64;              // points per tile (one kind)
 constexpr int kScPoses = 16;               // poses per tile: four per wave
-constexpr int kScPieces = 32;              // (cube, block) pieces per axis: 16 leaves of radius are <= 36 voxels = 10 blocks (+ 2 per cube face crossed)
 constexpr int kScMaxGrid = 4096;
-
-// the point a live record stands for: k_map_export's arithmetic (map_output.hip), coordinates only
-__device__ __forceinline__ float3 sc_point(const RecVal& v) {
-  const int n = key_seq(v.key) ? 1 : rec_n(v.count);
-  const float nn = (float)n;
-  float3 p;
-  p.x = n > 1 ? v.sum.x / nn : v.sum.x; p.y = n > 1 ? v.sum.y / nn : v.sum.y; p.z = n > 1 ? v.sum.z / nn : v.sum.z;
-  return p;
-}
-
-// bounded lookup of one record; a chain of kMaxProbe slots counts as absent and is reported
-__device__ __forceinline__ bool sc_find(const VoxelTable& T, u64 key, RecVal* out, bool* chain_too_long) {
-  unsigned s = (unsigned)mix64(key) & T.mask;
-  for (int probe = 0; probe < kMaxProbe; probe++, s = (s + 1) & T.mask) {
-    const RecVal v = rec_load(&T.rec[s]);
-    if (v.key == 0ull) return false;
-    if (v.key == key) { *out = v; return true; }
-  }
-  *chain_too_long = true;
-  return false;
-}
 
 }  // namespace
 
@@ -68,7 +44,7 @@ __global__ __launch_bounds__(256) void k_map_score(VoxelTable T0, VoxelTable T1,
                                                    int stride0, int stride1, float radius0, float radius1, float r2_0, float r2_1,
                                                    const double* __restrict__ poses, int M, vloam_pose_score* __restrict__ out) {
   __shared__ float4 s_pt[kScPoints];
-  __shared__ int s_piece[kScGroups][3][kScPieces];
+  __shared__ int s_piece[kScGroups][3][kWalkPieces];
   __shared__ int s_np[kScGroups][4];   // pieces per axis | more pieces than the table holds
   const int lane = threadIdx.x & 63, gl = lane & (kScG - 1), gi = threadIdx.x / kScG, wave = threadIdx.x >> 6, gw = lane / kScG;
   const int cen0 = ms->cenW, cen1 = ms->cenH, cen2 = ms->cenD;
@@ -109,30 +85,9 @@ __global__ __launch_bounds__(256) void k_map_score(VoxelTable T0, VoxelTable T1,
         if (search && gl < 3) {
           const float qa = gl == 0 ? qp.x : (gl == 1 ? qp.y : qp.z);
           const int cen = gl == 0 ? cen0 : (gl == 1 ? cen1 : cen2), wdim = gl == 0 ? kCubeW : (gl == 1 ? kCubeH : kCubeD);
-          const int lo = (int)floorf((qa - radius) * inv) - 1, hi = (int)floorf((qa + radius) * inv) + 1;
-          const double leaf = 1.0 / (double)inv;
-          // cube A holds the voxel indices [base(A), base(A + 1) + 2] (k_map_insert: index = floorf(p * inv), cube by the f64 test)
-          const int Amin = (int)floor(((double)(lo - 3) * leaf + 25.0) * 0.02) - 1, Amax = (int)floor(((double)(hi + 3) * leaf + 25.0) * 0.02) + 1;
-          int np = 0;
-          bool ovf = false;
-          for (int A = Amin; A <= Amax && !ovf; A++) {
-            const int wv = A + cen;
-            if (wv < 0 || wv >= wdim) continue;   // outside the window: not part of the map (k_map_export)
-            const int base = cube_voxel_base(A, inv);
-            const int top_i = cube_voxel_base(A + 1, inv) + 2;
-            const int ia = max(lo, base), ib = min(min(hi, top_i), base + kVoxMax);
-            if (ia > ib) continue;
-            for (int blk = (ia - base) >> 2; blk <= ((ib - base) >> 2); blk++) {
-              if (np >= kScPieces) { ovf = true; break; }
-              int m4 = 0;
-#pragma unroll
-              for (int b = 0; b < 4; b++) { const int iv = base + (blk << 2) + b; if (iv >= ia && iv <= ib) m4 |= 1 << b; }
-              s_piece[gi][gl][np] = ((A + 8192) << 11) | (blk << 4) | m4;
-              np++;
-            }
-          }
+          const int np = walk_axis_pieces(qa, radius, inv, cen, wdim, gl == 2 ? kCubeOffZ : kCubeOffXY, s_piece[gi][gl]);
           s_np[gi][gl] = np;
-          if (ovf) s_np[gi][3] = 1;
+          if (np < 0) s_np[gi][3] = 1;
         }
         __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
         __builtin_amdgcn_wave_barrier();
@@ -145,47 +100,12 @@ __global__ __launch_bounds__(256) void k_map_score(VoxelTable T0, VoxelTable T1,
         for (int bb = gl; bb < nblocks; bb += kScG) {
           const int n01 = np0 * np1;
           const int ez = bb / n01, rem = bb - ez * n01, ey = rem / np0, ex = rem - ey * np0;
-          const int w0 = s_piece[gi][0][ex], w1 = s_piece[gi][1][ey], w2 = s_piece[gi][2][ez];
-          const int A0 = (w0 >> 11) - 8192, A1 = (w1 >> 11) - 8192, A2 = (w2 >> 11) - 8192;
-          const int b0 = (w0 >> 4) & 127, b1 = (w1 >> 4) & 127, b2 = (w2 >> 4) & 127;
-          const int mx = w0 & 15, my = w1 & 15, mz = w2 & 15;
-          if (!cube_in_key_range(A0, A1, A2)) continue;   // no key: nothing was ever stored there
-          const u64 bkey = pack_key(A0, A1, A2, b0, b1, b2) | (1ull << 63);
-          u64 occ = 0ull;
-          {
-            unsigned bs = (unsigned)mix64(bkey) & T.bslots_mask;
-            int probe = 0;
-            for (; probe < kMaxProbe; probe++, bs = (bs + 1) & T.bslots_mask) {
-              const ulonglong2 e = T.blk[bs];
-              if (e.x == 0ull) break;
-              if (e.x == bkey) { occ = e.y; break; }
-            }
-            if (probe == kMaxProbe) chain_too_long = true;
-          }
-          // voxels of the block inside the box: bit = z * 16 + y * 4 + x
-          const u64 ex4 = (u64)mx * 0x1111111111111111ull;
-          const u64 ey4 = ((u64)((my & 1) * 0xF) | ((u64)(((my >> 1) & 1) * 0xF) << 4) | ((u64)(((my >> 2) & 1) * 0xF) << 8) | ((u64)(((my >> 3) & 1) * 0xF) << 12)) * 0x0001000100010001ull;
-          const u64 ez4 = ((mz & 1) ? 0xFFFFull : 0ull) | ((mz & 2) ? 0xFFFFull << 16 : 0ull) | ((mz & 4) ? 0xFFFFull << 32 : 0ull) | ((mz & 8) ? 0xFFFFull << 48 : 0ull);
-          occ &= ex4 & ey4 & ez4;
-          auto consider = [&](const RecVal& v) {
-            const float3 c = sc_point(v);
+          walk_block(T, s_piece[gi][0][ex], s_piece[gi][1][ey], s_piece[gi][2][ez], &chain_too_long, [&](const RecVal& v, unsigned) {
+            const float4 c = rec_point(v);
             const float dx = qp.x - c.x, dy = qp.y - c.y, dz = qp.z - c.z;
             const float d2 = __fadd_rn(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)), __fmul_rn(dz, dz));
             if (d2 < dmin) dmin = d2;
-          };
-          while (occ) {
-            const int bit = __ffsll((long long)occ) - 1;
-            occ &= occ - 1;
-            const u64 key = pack_key(A0, A1, A2, (b0 << 2) | (bit & 3), (b1 << 2) | ((bit >> 2) & 3), (b2 << 2) | (bit >> 4));
-            RecVal v;
-            if (!sc_find(T, key, &v, &chain_too_long) || v.count == 0) continue;   // never finalized, or purged
-            if (!rec_raw(v.count)) { consider(v); continue; }
-            const int nr = min(rec_n(v.count), 255);   // a raw voxel: its points, one record each
-            for (int seq = 1; seq <= nr; seq++) {
-              RecVal pv;
-              if (sc_find(T, key_with_seq(key, seq), &pv, &chain_too_long) && pv.count != 0) consider(pv);
-            }
-          }
+          });
         }
         // ---- the group's minimum; its first lane counts the point
 #pragma unroll
@@ -211,7 +131,7 @@ __global__ __launch_bounds__(256) void k_map_score(VoxelTable T0, VoxelTable T1,
     }
   }
   // piece_overflow shares the map-full word with a probe chain at its bound, as in map_query.hip.  It cannot happen for a radius the entry points
-  // accept: 16 leaves are at most 36 voxel indices per axis, 10 blocks, plus 2 per cube face crossed — about 12 of the kScPieces slots.
+  // accept: 16 leaves are at most 36 voxel indices per axis, 10 blocks, plus 2 per cube face crossed — about 12 of the kWalkPieces slots.
   if (__ballot(chain_too_long || piece_overflow) != 0ull && lane == 0) atomicOr(&fr->error, kErrMapFull);
 }
 

@@ -1,6 +1,7 @@
 // The voxel tables of the map as device code sees them: hash, voxel key, record access, occupancy blocks.  Shared by map_kernels.hip (the
-// sweep's kernels), map_output.hip (export and publication), map_grow.hip (the growable map's rehash), map_ckpt.hip, map_query.hip, map_score.hip and map_import.hip,
-// which are separate code objects.
+// sweep's kernels), map_output.hip (export and publication), map_grow.hip (the growable map's rehash), map_ckpt.hip, map_import.hip and, through
+// map_walk.h, map_query.hip and map_score.hip, which are separate code objects.  rec_find, rec_point and rec_order_key serve the map's readers
+// only (map_output.hip, map_walk.h and its two kernels): the sweep's kernels keep their own lookups.
 #pragma once
 #include <hip/hip_runtime.h>
 #include "map_kernels.h"
@@ -58,6 +59,33 @@ __device__ __forceinline__ RecVal rec_load(const VoxelRec* r) {
 __device__ __forceinline__ void rec_store_value(VoxelRec* r, float4 sum, int count, int pend_cnt) {
   reinterpret_cast<float2*>(r)[1] = make_float2(sum.x, sum.y);
   reinterpret_cast<uint4*>(r)[1] = make_uint4(__float_as_uint(sum.z), __float_as_uint(sum.w), (unsigned)count, (unsigned)pend_cnt);
+}
+
+// bounded lookup of one record; a chain of kMaxProbe slots counts as absent and is reported.  slot (may be null): where the record was found
+__device__ __forceinline__ bool rec_find(const VoxelTable& T, u64 key, RecVal* out, unsigned* slot, bool* chain_too_long) {
+  unsigned s = (unsigned)mix64(key) & T.mask;
+  for (int probe = 0; probe < kMaxProbe; probe++, s = (s + 1) & T.mask) {
+    const RecVal v = rec_load(&T.rec[s]);
+    if (v.key == 0ull) return false;
+    if (v.key == key) { *out = v; if (slot) *slot = s; return true; }
+  }
+  *chain_too_long = true;
+  return false;
+}
+
+// What the map's readers (export, publication, queries, scores) make of a live record that is not a raw voxel's running sum; they are compared
+// bit for bit with each other, so this is the only text of it.  The point: a centroid is sum / n in f32, a point record (seq != 0) the point itself.
+__device__ __forceinline__ float4 rec_point(const RecVal& v) {
+  const int n = key_seq(v.key) ? 1 : rec_n(v.count);
+  const float nn = (float)n;
+  return make_float4(n > 1 ? v.sum.x / nn : v.sum.x, n > 1 ? v.sum.y / nn : v.sum.y, n > 1 ? v.sum.z / nn : v.sum.z, n > 1 ? v.sum.w / nn : v.sum.w);
+}
+// Its place in /laser_cloud_map: | window cube index 13 | kind 1 | tail 1 | 16 zero bits | voxel (lz, ly, lx) or arrival stamp, 32 |.  tail: an
+// un-merged arrival, behind the cube's voxel-ordered part by arrival stamp (a centroid that became raw point number one has stamp 0 and stays)
+__device__ __forceinline__ u64 rec_order_key(const RecVal& v, int cube_index, int kind) {
+  const u64 lx = (u64)key_lx(v.key), ly = (u64)key_ly(v.key), lz = (u64)key_lz(v.key);
+  const bool tail = key_seq(v.key) != 0 && v.pend_cnt != 0;
+  return ((u64)cube_index << 50) | ((u64)kind << 49) | ((u64)(tail ? 1 : 0) << 48) | (tail ? (u64)(unsigned)v.pend_cnt : ((lz << (2 * kVoxBits)) | (ly << kVoxBits) | lx));
 }
 
 // set the voxel's bit in its 4 x 4 x 4 block's occupancy mask (find-or-insert of the block entry)
