@@ -1,4 +1,5 @@
-// ORACLE — TEST INFRASTRUCTURE ONLY (see orc_math.h header).  PARITY UNPINNED.
+// ORACLE — TEST INFRASTRUCTURE ONLY (see orc_math.h header).  Pinned to the reference's own point_cloud_util.cpp / visual_odometry.cpp by
+// tests/test_ref_visual_odometry.py (the 3 x 3 QR and the minimizer excepted: they stand behind the reference's text there too).
 // Line references are into /root/reference/src/visual_odometry/.
 #include "orc_vo.h"
 #include <algorithm>

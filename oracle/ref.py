@@ -1,4 +1,5 @@
-"""ctypes driver for the reference's own scan registration and cost functors (oracle/_ref/libref.so, oracle/ref_harness.cpp).
+"""ctypes driver for the reference's own scan registration and cost functors (oracle/_ref/libref.so, oracle/ref_harness.cpp), laser
+odometry and mapping (libref_loam.so, ref_loam_harness.cpp) and depth-enhanced visual odometry (libref_vo.so, ref_vo_harness.cpp).
 
 TEST INFRASTRUCTURE ONLY.  libref.so is the reference's scan_registration.cpp / lidarFactor.hpp / ceres_cost_function.h compiled
 unmodified against the stand-in headers of oracle/ref_shim/.  It is built from a checkout of the reference and is never committed; on a
@@ -274,3 +275,117 @@ class Loam:
         assert self.L.ref_loam_get_solve_blocks(self.h, stage, k, _vp(types), _vp(nres), _vp(payload), _vp(raw)) == 0
         return dict(q_in=b[:4], t_in=b[4:], q_out=a[:4], t_out=a[4:], max_num_iterations=int(cnt[2]), types=types[:nb], nres=nres[:nb],
                     payload=payload[:nb], residuals0=raw[:nr])
+
+
+# ---------------------------------------------------------------- visual odometry (oracle/_ref/libref_vo.so, ref_vo_harness.cpp)
+VO_LIB = "libref_vo.so"
+
+
+def vo_available():
+    return reference_dir() is not None or os.path.exists(os.path.join(REF_OUT, VO_LIB))
+
+
+def vo_lib():
+    if VO_LIB not in _libs:
+        if build() is None or not os.path.exists(os.path.join(REF_OUT, VO_LIB)):
+            raise RuntimeError(SKIP_REASON)
+        L = C.CDLL(os.path.join(REF_OUT, VO_LIB))
+        L.ref_vo_create.restype = _P
+        L.ref_vo_create.argtypes = [_P, _P, _P, I, I, I]
+        L.ref_vo_destroy.argtypes = [_P]
+        L.ref_vo_frame.argtypes = [_P, _P, I]
+        L.ref_vo_count.argtypes = [_P]
+        L.ref_vo_get_points2d.argtypes = [_P, I, _P, I]
+        L.ref_vo_get_dnsp.argtypes = [_P, I, _P, I]
+        L.ref_vo_get_buckets.argtypes = [_P, I, _P, _P, _P, _P, I, _P]
+        L.ref_vo_query_depth.argtypes = [_P, I, _P, I, _P, _P]
+        L.ref_vo_solve.argtypes = [_P, _P, I, _P, I, _P, _P, _P, I, _P, _P]
+        L.ref_vo_get_result.argtypes = [_P, _P, _P, _P]
+        L.ref_vo_get_match_rows.argtypes = [_P, _P, I]
+        _libs[VO_LIB] = L
+    return _libs[VO_LIB]
+
+
+class VO:
+    """The reference's VisualOdometry object with its two PointCloudUtil objects; mirrors orc.VOOracle.  which_map: 0 the current frame's
+    depth map (point_cloud_utils[i]), 1 the previous frame's.  optical_flow_match chooses which match containers solveNlsAll reads."""
+    N_BUCKETS = 249 * 75
+
+    def __init__(self, cam_T_velo, rect0_T_cam, P_rect0, remove_outlier=100, reset_to_identity=True, optical_flow_match=False):
+        self.L = vo_lib()
+        a = np.ascontiguousarray(cam_T_velo, dtype=np.float32)
+        b = np.ascontiguousarray(rect0_T_cam, dtype=np.float32)
+        c = np.ascontiguousarray(P_rect0, dtype=np.float32)
+        assert a.shape == (4, 4) and b.shape == (4, 4) and c.shape == (3, 4)
+        self.optical_flow_match = bool(optical_flow_match)
+        self.h = _P(self.L.ref_vo_create(_vp(a), _vp(b), _vp(c), int(remove_outlier), int(reset_to_identity), int(optical_flow_match)))
+
+    def __del__(self):
+        try:
+            self.L.ref_vo_destroy(self.h)
+        except Exception:
+            pass
+
+    def frame(self, cloud):
+        """VisualOdometry::reset, then processPointCloud on the sweep [n, 4] (x, y, z, anything)."""
+        c = np.ascontiguousarray(cloud, dtype=np.float32)
+        assert c.ndim == 2 and c.shape[1] == 4
+        self.L.ref_vo_frame(self.h, _vp(c), c.shape[0])
+
+    def count(self):
+        return self.L.ref_vo_count(self.h)
+
+    def _rows3(self, fn, which_map):
+        n = fn(self.h, which_map, None, 0)
+        buf = np.zeros((max(n, 1), 3), dtype=np.float32)
+        fn(self.h, which_map, _vp(buf), n)
+        return buf[:n]
+
+    def points2d(self, which_map=0):
+        return self._rows3(self.L.ref_vo_get_points2d, which_map)
+
+    def dnsp(self, which_map=0):
+        return self._rows3(self.L.ref_vo_get_dnsp, which_map)
+
+    def buckets(self, which_map=0):
+        """(bucket_x, bucket_y, bucket_depth, bucket_count), each flattened index_x * new_height + index_y like orc.VOOracle.buckets."""
+        nb = self.N_BUCKETS
+        bx, by, bd = [np.zeros(nb, dtype=np.float32) for _ in range(3)]
+        bc = np.zeros(nb, dtype=np.int32)
+        dims = np.zeros(2, dtype=np.int32)
+        n = self.L.ref_vo_get_buckets(self.h, which_map, _vp(bx), _vp(by), _vp(bd), _vp(bc), nb, _vp(dims))
+        assert n == nb and tuple(dims) == (249, 75), (n, dims)
+        return bx, by, bd, bc
+
+    def query_depth(self, which_map, xy):
+        """(queryDepth per pixel of xy [n, 2] f32, tie flags: the third and fourth smallest neighbour distance are equal)."""
+        p = np.ascontiguousarray(xy, dtype=np.float32).reshape(-1, 2)
+        d, tie = np.zeros(p.shape[0], dtype=np.float32), np.zeros(p.shape[0], dtype=np.uint8)
+        self.L.ref_vo_query_depth(self.h, which_map, _vp(p), p.shape[0], _vp(d), _vp(tie))
+        return d, tie.astype(bool)
+
+    def solve(self, kp_prev, kp_curr, query_idx=None, train_idx=None, status=None, prior_q=None, prior_t=None):
+        """solveNlsAll.  ORB configuration: keypoints of both images [n, 2] f32 and (query_idx, train_idx); optical-flow configuration: the
+        two point lists of equal length and status.  match_rows [n_match, 11]: kind (32 / 22; 0 skipped by the outlier gate; -1 no match:
+        status != 1), depth0, obs[5], and the integer pixel pair the reference derived (prev x, y, curr x, y)."""
+        a = np.ascontiguousarray(kp_prev, dtype=np.float32).reshape(-1, 2)
+        b = np.ascontiguousarray(kp_curr, dtype=np.float32).reshape(-1, 2)
+        if self.optical_flow_match:
+            st = np.ascontiguousarray(status, dtype=np.uint8)
+            assert a.shape == b.shape and st.shape == (a.shape[0],)
+            n, q, t = a.shape[0], None, None
+        else:
+            q = np.ascontiguousarray(query_idx, dtype=np.int32)
+            t = np.ascontiguousarray(train_idx, dtype=np.int32)
+            assert q.shape == t.shape and (q.size == 0 or (q.min() >= 0 and q.max() < a.shape[0] and t.min() >= 0 and t.max() < b.shape[0]))
+            n, st = q.shape[0], None
+        pq = None if prior_q is None else np.ascontiguousarray(prior_q, dtype=np.float64)
+        pt = None if prior_t is None else np.ascontiguousarray(prior_t, dtype=np.float64)
+        rc = self.L.ref_vo_solve(self.h, _vp(a), a.shape[0], _vp(b), b.shape[0], None if q is None else _vp(q), None if t is None else _vp(t),
+                                 None if st is None else _vp(st), n, None if pq is None else _vp(pq), None if pt is None else _vp(pt))
+        assert rc == 0, "ref_vo_solve: %d (the residual blocks could not be attributed to the matches)" % rc
+        out, inn, cnt = np.zeros(6), np.zeros(6), np.zeros(2, dtype=np.int32)
+        self.L.ref_vo_get_result(self.h, _vp(out), _vp(inn), _vp(cnt))
+        rows = np.zeros((max(n, 1), 11))
+        assert self.L.ref_vo_get_match_rows(self.h, _vp(rows), n) == n
+        return dict(angles=out[:3], t=out[3:], angles_in=inn[:3], t_in=inn[3:], counter32=int(cnt[0]), counter22=int(cnt[1]), match_rows=rows[:n])

@@ -6,11 +6,22 @@
 // reference's own cost function (its AutoDiffCostFunction around its own functor): the oracle's solver only calls Evaluate on it.
 // Checked rather than assumed: two parameter blocks of sizes (4 with a quaternion parameterization | 3, 3), every residual block on
 // exactly those two in that order, one HuberLoss shared by all (or none).  Anything else aborts: it would mean the reference drives
-// Ceres in a way this bridge does not express.
+// Ceres in a way this bridge does not express.  A problem without any block (VisualOdometry::solveNlsAll on a frame without a usable
+// match) is left alone, as Ceres leaves it: no parameter block, nothing to minimise, the parameters keep their values.
+//
+// Also here: Eigen::refshim::qr3_f32, what the stand-in Eigen's colPivHouseholderQr().solve on a 3 x 3 f32 block delegates to — the
+// oracle's own f32 restatement (orc::solve3x3_colpiv_qr_f32, orc_vo.cpp).  Eigen's QR is not pinned either.
 #include <cstdio>
 #include <cstdlib>
 #include <ceres/ceres.h>
 #include "orc_ceres.h"
+#include "orc_vo.h"
+
+namespace Eigen {
+namespace refshim {
+void qr3_f32(const float A_row_major[9], const float b[3], float x[3]) { orc::solve3x3_colpiv_qr_f32(A_row_major, b, x); }
+}  // namespace refshim
+}  // namespace Eigen
 
 namespace {
 
@@ -35,6 +46,14 @@ namespace ceres {
 void Solve(const Solver::Options& options, Problem* problem, Solver::Summary* summary) {
   const std::vector<Problem::ParameterBlock>& pb = problem->parameter_blocks();
   const std::vector<Problem::ResidualBlock>& rb = problem->residual_blocks();
+  if (pb.empty() && rb.empty()) {
+    refshim::SolveRecord rec;
+    rec.problem = problem;
+    rec.max_num_iterations = options.max_num_iterations;
+    if (summary) *summary = Solver::Summary();
+    if (refshim::observer()) refshim::observer()(rec);
+    return;
+  }
   require(pb.size() == 2 && pb[1].size == 3 && !pb[1].parameterization, "expected two parameter blocks, the second a plain 3-vector");
   const bool quat = dynamic_cast<EigenQuaternionParameterization*>(pb[0].parameterization) != nullptr;
   require(quat ? pb[0].size == 4 : (pb[0].size == 3 && !pb[0].parameterization), "first block: 4 with EigenQuaternionParameterization, or a plain 3");

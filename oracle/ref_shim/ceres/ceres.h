@@ -8,7 +8,11 @@
 //
 // Problem / Solve, as laser_odometry.cpp:217-221,257-258,347,440,458-463 and laser_mapping.cpp:461-467,514,578,610-617 drive them:
 // Problem(Options), AddParameterBlock(values, size[, parameterization]), AddResidualBlock(cost, loss, block0, block1),
-// Solver::Options / Summary, Solve.  The Problem owns what it is given, like Ceres' default Options.  The MINIMIZER IS NOT RESTATED
+// Solver::Options / Summary, Solve.  visual_odometry.cpp:258-259,366,413,423 adds no parameter block of its own: like Ceres,
+// AddResidualBlock then registers the two blocks it is given, with the sizes the cost function states (parameter_block_size), in the
+// order it first sees them.  Every AddResidualBlock is also reported to ceres::refshim::add_observer(), at the moment of the call, so
+// that a harness can read what the reference holds in its public members right then (VisualOdometry::depth0, point_3d_image0_0 / _1).
+// The Problem owns what it is given, like Ceres' default Options.  The MINIMIZER IS NOT RESTATED
 // HERE: Solve (oracle/ref_bridge.cpp) hands the residual blocks, in AddResidualBlock order, to the oracle's restatement of Ceres'
 // trust-region loop (orc::Problem::Solve, oracle/orc_ceres.cpp, linked into the reference library) — pinning Ceres is not the aim.
 // What is pinned is what the reference PUTS INTO the problem: which blocks, in which order, from which points, at which parameters.
@@ -28,7 +32,12 @@ class CostFunction {
   virtual ~CostFunction() {}
   virtual bool Evaluate(double const* const* parameters, double* residuals, double** jacobians) const = 0;
   virtual int num_residuals() const = 0;
+  virtual int parameter_block_size(int k) const = 0;
 };
+
+namespace refshim {
+inline std::function<void(const CostFunction*)>& add_observer() { static std::function<void(const CostFunction*)> f; return f; }
+}  // namespace refshim
 
 template <class Functor, int kNumResiduals, int N0, int N1>
 class AutoDiffCostFunction : public CostFunction {
@@ -36,6 +45,7 @@ class AutoDiffCostFunction : public CostFunction {
   explicit AutoDiffCostFunction(Functor* f) : f_(f) {}
   ~AutoDiffCostFunction() override { delete f_; }
   int num_residuals() const override { return kNumResiduals; }
+  int parameter_block_size(int k) const override { return k == 0 ? N0 : N1; }
   const Functor& functor() const { return *f_; }
   bool Evaluate(double const* const* parameters, double* residuals, double** jacobians) const override {
     if (!jacobians) return (*f_)(parameters[0], parameters[1], residuals);
@@ -102,7 +112,16 @@ class Problem {
   void AddParameterBlock(double* values, int size, LocalParameterization* parameterization = nullptr) {
     parameter_blocks_.push_back({values, size, parameterization});
   }
-  void AddResidualBlock(CostFunction* cost, LossFunction* loss, double* p0, double* p1) { residual_blocks_.push_back({cost, loss, p0, p1}); }
+  void AddResidualBlock(CostFunction* cost, LossFunction* loss, double* p0, double* p1) {
+    double* const p[2] = {p0, p1};
+    for (int k = 0; k < 2; k++) {
+      bool known = false;
+      for (const ParameterBlock& b : parameter_blocks_) known = known || b.values == p[k];
+      if (!known) parameter_blocks_.push_back({p[k], cost->parameter_block_size(k), nullptr});
+    }
+    residual_blocks_.push_back({cost, loss, p0, p1});
+    if (refshim::add_observer()) refshim::add_observer()(cost);
+  }
   const std::vector<ParameterBlock>& parameter_blocks() const { return parameter_blocks_; }
   const std::vector<ResidualBlock>& residual_blocks() const { return residual_blocks_; }
 

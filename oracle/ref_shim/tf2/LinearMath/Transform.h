@@ -7,7 +7,13 @@
 // largest diagonal element leads) — what the reference reads back from velo_last_VOT_velo_curr is therefore NOT bit for bit what was
 // stored, and the harness hands the oracle the read-back values.  inverse() = (basis^T, basis^T * -origin); a * b = (basis_a basis_b,
 // basis_a origin_b + origin_a).  Unlike tf2, a default-constructed Transform is the identity rather than uninitialised memory.
+//
+// For visual_odometry.cpp:272-280, :426-430 (tf2/LinearMath/Quaternion.h): getAngle() = 2 acos(w) with w clamped to [-1, 1] (tf2Acos);
+// getAxis() = (x, y, z) / sqrt(1 - w^2), or (1, 0, 0) when 1 - w^2 < 10 DBL_EPSILON; setRotation(axis, angle) = (axis sin(angle / 2) /
+// |axis|, cos(angle / 2)); getX() ... of Vector3 and Quaternion; the nine-scalar Matrix3x3 constructor and Transform::setBasis; the
+// conversion to const double* through which Eigen::Quaterniond / Vector3d are built from them (visual_odometry.cpp:457-458).
 #pragma once
+#include <cfloat>
 #include <cmath>
 
 namespace tf2 {
@@ -19,6 +25,11 @@ class Vector3 {
   double x() const { return v_[0]; }
   double y() const { return v_[1]; }
   double z() const { return v_[2]; }
+  double getX() const { return v_[0]; }
+  double getY() const { return v_[1]; }
+  double getZ() const { return v_[2]; }
+  double length() const { return std::sqrt(dot(*this)); }
+  operator const double*() const { return v_; }
   double dot(const Vector3& o) const { return v_[0] * o.v_[0] + v_[1] * o.v_[1] + v_[2] * o.v_[2]; }
   Vector3 operator-() const { return Vector3(-v_[0], -v_[1], -v_[2]); }
   Vector3 operator+(const Vector3& o) const { return Vector3(v_[0] + o.v_[0], v_[1] + o.v_[1], v_[2] + o.v_[2]); }
@@ -36,7 +47,29 @@ class Quaternion {
   double y() const { return q_[1]; }
   double z() const { return q_[2]; }
   double w() const { return q_[3]; }
+  double getX() const { return q_[0]; }
+  double getY() const { return q_[1]; }
+  double getZ() const { return q_[2]; }
+  double getW() const { return q_[3]; }
+  operator const double*() const { return q_; }
   double length2() const { return q_[0] * q_[0] + q_[1] * q_[1] + q_[2] * q_[2] + q_[3] * q_[3]; }
+  void setRotation(const Vector3& axis, double angle) {
+    const double d = axis.length();
+    const double s = std::sin(angle * 0.5) / d;
+    q_[0] = axis.x() * s; q_[1] = axis.y() * s; q_[2] = axis.z() * s; q_[3] = std::cos(angle * 0.5);
+  }
+  double getAngle() const {
+    double w = q_[3];
+    if (w < -1.0) w = -1.0;
+    if (w > 1.0) w = 1.0;
+    return 2.0 * std::acos(w);
+  }
+  Vector3 getAxis() const {
+    const double s_squared = 1.0 - std::pow(q_[3], 2.0);
+    if (s_squared < 10.0 * DBL_EPSILON) return Vector3(1.0, 0.0, 0.0);
+    const double s = std::sqrt(s_squared);
+    return Vector3(q_[0] / s, q_[1] / s, q_[2] / s);
+  }
 
  private:
   double q_[4];
@@ -45,6 +78,7 @@ class Quaternion {
 class Matrix3x3 {
  public:
   Matrix3x3() { setIdentity(); }
+  Matrix3x3(double xx, double xy, double xz, double yx, double yy, double yz, double zx, double zy, double zz) { setValue(xx, xy, xz, yx, yy, yz, zx, zy, zz); }
   void setIdentity() { r_[0] = Vector3(1, 0, 0); r_[1] = Vector3(0, 1, 0); r_[2] = Vector3(0, 0, 1); }
   void setValue(double xx, double xy, double xz, double yx, double yy, double yz, double zx, double zy, double zz) {
     r_[0] = Vector3(xx, xy, xz); r_[1] = Vector3(yx, yy, yz); r_[2] = Vector3(zx, zy, zz);
@@ -106,6 +140,7 @@ class Transform {
   void setIdentity() { basis_.setIdentity(); origin_ = Vector3(0, 0, 0); }
   void setOrigin(const Vector3& o) { origin_ = o; }
   void setRotation(const Quaternion& q) { basis_.setRotation(q); }
+  void setBasis(const Matrix3x3& b) { basis_ = b; }
   const Vector3& getOrigin() const { return origin_; }
   Quaternion getRotation() const { Quaternion q; basis_.getRotation(q); return q; }
   const Matrix3x3& getBasis() const { return basis_; }

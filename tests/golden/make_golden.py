@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Generate tests/golden/*.npz (run in the dev container: `python tests/golden/make_golden.py`; `... make_golden.py ref` for ref_sr_* / ref_lo_* / ref_map_* only).
+"""Generate tests/golden/*.npz (run in the dev container: `python tests/golden/make_golden.py`; `... make_golden.py ref` for ref_sr_* / ref_lo_* / ref_map_* / ref_vo_* only; `... vo` for ref_vo_* only).
 
 ref_sr_*.npz are outputs of the reference's own scan_registration.cpp (see run_ref_sr_cases).  The reference has no tests and no golden
 vectors and the rest of it cannot be built here, so the other fixtures pin the ORACLE's outputs (regression vectors): the CPU tests check the oracle still reproduces them,
@@ -140,16 +140,39 @@ def run_ref_loam_cases():
             for stem, (params, sweeps, priors, with_mapping) in sorted(ref_cases.loam_golden_cases().items())}
 
 
+def run_ref_vo_cases():
+    """tests/golden/ref_vo_<case>.npz: what the REFERENCE'S OWN point_cloud_util.cpp / visual_odometry.cpp::solveNlsAll computed
+    (oracle/_ref/libref_vo.so) for the scenarios of tests/ref_vo_cases.py — inputs and recorded results, data only; layout:
+    ref_vo_cases.record.  A scenario in which more than 1 % of the queried pixels tie on the third / fourth neighbour distance (std::sort
+    leaves their order open) is refused."""
+    import ref
+    import ref_vo_cases
+    out = {}
+    for stem, sc in sorted(ref_vo_cases.scenarios().items()):
+        d = ref_vo_cases.record(ref, sc)
+        ties, n = ref_vo_cases.tie_share(d)
+        print("%s: %d of %d queried pixels tie (%.3f %%)" % (stem, ties, n, 100.0 * ties / max(n, 1)))
+        assert ties <= 0.01 * n, "%s: more than 1 %% of the queried pixels tie; choose other seeds" % stem
+        out[stem] = d
+    return out
+
+
 def write_ref_sr_cases():
     for name, d in run_ref_sr_cases().items():
         np.savez_compressed(os.path.join(HERE, "ref_sr_%s.npz" % name), **d)
     for stem, d in run_ref_loam_cases().items():
+        np.savez_compressed(os.path.join(HERE, stem + ".npz"), **d)
+    for stem, d in run_ref_vo_cases().items():
         np.savez_compressed(os.path.join(HERE, stem + ".npz"), **d)
 
 
 if __name__ == "__main__":
     if len(sys.argv) > 1 and sys.argv[1] == "ref":   # only the reference recordings (needs the reference checkout or a built oracle/_ref/)
         write_ref_sr_cases()
+        sys.exit(0)
+    if len(sys.argv) > 1 and sys.argv[1] == "vo":
+        for stem, d in run_ref_vo_cases().items():
+            np.savez_compressed(os.path.join(HERE, stem + ".npz"), **d)
         sys.exit(0)
     import ref
     if ref.available():
