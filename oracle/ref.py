@@ -1,5 +1,6 @@
 """ctypes driver for the reference's own scan registration and cost functors (oracle/_ref/libref.so, oracle/ref_harness.cpp), laser
-odometry and mapping (libref_loam.so, ref_loam_harness.cpp) and depth-enhanced visual odometry (libref_vo.so, ref_vo_harness.cpp).
+odometry and mapping (libref_loam.so, ref_loam_harness.cpp), depth-enhanced visual odometry (libref_vo.so, ref_vo_harness.cpp) and the coupled
+frame loop over vloam_tf.cpp and lidar_odometry_mapping.cpp (libref_vloam.so, ref_vloam_harness.cpp).
 
 TEST INFRASTRUCTURE ONLY.  libref.so is the reference's scan_registration.cpp / lidarFactor.hpp / ceres_cost_function.h compiled
 unmodified against the stand-in headers of oracle/ref_shim/.  It is built from a checkout of the reference and is never committed; on a
@@ -389,3 +390,167 @@ class VO:
         rows = np.zeros((max(n, 1), 11))
         assert self.L.ref_vo_get_match_rows(self.h, _vp(rows), n) == n
         return dict(angles=out[:3], t=out[3:], angles_in=inn[:3], t_in=inn[3:], counter32=int(cnt[0]), counter22=int(cnt[1]), match_rows=rows[:n])
+
+
+# ---------------------------------------------------------------- the coupled frame loop (oracle/_ref/libref_vloam.so, ref_vloam_harness.cpp)
+VLOAM_LIB = "libref_vloam.so"
+TF_NAMES = ("imu_T_velo", "imu_T_cam0", "base_T_imu", "base_T_cam0", "velo_T_cam0", "world_VOT_base_last", "base_last_VOT_base_curr",
+            "cam0_curr_VOT_cam0_last", "velo_last_VOT_velo_curr", "cam0_init_VOT_cam0_last", "cam0_init_VOT_cam0_start", "cam0_start_VOT_cam0_last",
+            "world_LOT_base_last", "cam0_init_LOT_cam0_last", "cam0_init_LOT_cam0_start", "cam0_start_LOT_cam0_last", "base_prev_LOT_base_curr",
+            "cam0_curr_LOT_cam0_prev", "world_MOT_base_last", "cam0_init_MOT_cam0_last", "cam0_init_MOT_cam0_start", "cam0_start_MOT_cam0_last",
+            "VO.cam0_curr_T_cam0_last")
+
+
+def vloam_available():
+    return reference_dir() is not None or os.path.exists(os.path.join(REF_OUT, VLOAM_LIB))
+
+
+def vloam_lib():
+    if VLOAM_LIB not in _libs:
+        if build() is None or not os.path.exists(os.path.join(REF_OUT, VLOAM_LIB)):
+            raise RuntimeError(SKIP_REASON)
+        L = C.CDLL(os.path.join(REF_OUT, VLOAM_LIB))
+        L.ref_vloam_create.restype = _P
+        L.ref_vloam_create.argtypes = [_P, _P, _P, _P, _P, D, D, D]
+        L.ref_vloam_destroy.argtypes = [_P]
+        L.ref_vloam_frame.argtypes = [_P, _P, I, _P, _P, I]
+        L.ref_vloam_count.argtypes = [_P]
+        L.ref_vloam_get_tfs.argtypes = [_P, _P]
+        L.ref_vloam_get_tf_rotation.argtypes = [_P, I, _P]
+        L.ref_vloam_get_eigen_statics.argtypes = [_P, _P]
+        L.ref_vloam_get_vo.argtypes = [_P, _P, _P, _P]
+        L.ref_vloam_get_vo_rows.argtypes = [_P, _P, I]
+        L.ref_vloam_get_cloud.argtypes = [_P, I, _P, I]
+        L.ref_vloam_get_buckets.argtypes = [_P, _P, _P, _P, _P, I, _P]
+        L.ref_vloam_skip_frame.argtypes = [_P]
+        L.ref_vloam_map_ran.argtypes = [_P]
+        L.ref_vloam_get_lo_pose.argtypes = [_P, _P, _P]
+        L.ref_vloam_get_published_pose.argtypes = [_P, I, _P, _P]
+        L.ref_vloam_num_solves.argtypes = [_P]
+        L.ref_vloam_get_solve.argtypes = [_P, I, _P, _P, _P]
+        L.ref_vloam_get_solve_blocks.argtypes = [_P, I, _P, _P, _P, _P]
+        L.ref_vloam_get_rows_text.restype = C.c_long
+        L.ref_vloam_get_rows_text.argtypes = [_P, I, _P, C.c_long]
+        _libs[VLOAM_LIB] = L
+    return _libs[VLOAM_LIB]
+
+
+class Vloam:
+    """The reference's VloamTF, VisualOdometry and LidarOdometryMapping objects wired and driven like vloam_main_node.cpp's init() and
+    callback(); mirrors orc_vloam.VloamOracle.  statics: (imu_T_velo, imu_T_cam0, base_T_imu), each (q xyzw, t) as tf's lookups hand them
+    out.  frame() returns 0 or the harness's status (ref_vloam_harness.cpp: -1 / -2 / -5 close the session before the reference would run
+    into undefined behaviour; -5 after laserOdometryIO, so everything but the mapping can still be read)."""
+    VO, ODOMETRY, MAPPING = 0, 1, 2
+
+    def __init__(self, cam_T_velo, rect0_T_cam, P_rect0, statics, scan_line=64, minimum_range=5.0, line_res=0.4, plane_res=0.8, mapping_skip_frame=1,
+                 detach_VO_LO=False, reset_VO_to_identity=False, remove_VO_outlier=100, save_traj=False, start_frame=0, end_frame=-1, voxel_stable=True):
+        self.L = vloam_lib()
+        self.voxel_stable = voxel_stable
+        a = np.ascontiguousarray(cam_T_velo, dtype=np.float32)
+        b = np.ascontiguousarray(rect0_T_cam, dtype=np.float32)
+        c = np.ascontiguousarray(P_rect0, dtype=np.float32)
+        st = np.ascontiguousarray(np.concatenate([np.concatenate([np.asarray(q, dtype=np.float64), np.asarray(t, dtype=np.float64)]) for q, t in statics]))
+        assert a.shape == (4, 4) and b.shape == (4, 4) and c.shape == (3, 4) and st.shape == (21,)
+        ints = np.array([scan_line, mapping_skip_frame, int(detach_VO_LO), int(reset_VO_to_identity), remove_VO_outlier, int(save_traj), start_frame, end_frame],
+                        dtype=np.int32)
+        self.h = _P(self.L.ref_vloam_create(_vp(a), _vp(b), _vp(c), _vp(st), _vp(ints), minimum_range, float(np.float32(line_res)), float(np.float32(plane_res))))
+
+    def __del__(self):
+        try:
+            self.L.ref_vloam_destroy(self.h)
+        except Exception:
+            pass
+
+    def frame(self, cloud, prev_uv=None, curr_uv=None):
+        c = np.ascontiguousarray(cloud, dtype=np.float32)
+        assert c.ndim == 2 and c.shape[1] == 4
+        p = np.zeros((0, 2), np.int32) if prev_uv is None else np.ascontiguousarray(prev_uv, dtype=np.int32).reshape(-1, 2)
+        q = np.zeros((0, 2), np.int32) if curr_uv is None else np.ascontiguousarray(curr_uv, dtype=np.int32).reshape(-1, 2)
+        assert p.shape == q.shape
+        self.L.ref_set_voxel_stable_order(int(self.voxel_stable))
+        return self.L.ref_vloam_frame(self.h, _vp(c), c.shape[0], _vp(p), _vp(q), p.shape[0])
+
+    def count(self):
+        return self.L.ref_vloam_count(self.h)
+
+    def tfs(self):
+        """[23, 12]: the transforms TF_NAMES, each its basis row-major and its origin."""
+        out = np.zeros((len(TF_NAMES), 12))
+        assert self.L.ref_vloam_get_tfs(self.h, _vp(out)) == len(TF_NAMES)
+        return out
+
+    def tf_rotation(self, which):
+        q = np.zeros(4)
+        self.L.ref_vloam_get_tf_rotation(self.h, which, _vp(q))
+        return q
+
+    def eigen_statics(self):
+        out = np.zeros((2, 4, 4), dtype=np.float32)
+        self.L.ref_vloam_get_eigen_statics(self.h, _vp(out))
+        return out
+
+    def vo(self, n_match):
+        """None when solveNlsAll did not run in the last frame (count 0); else x_in / x_out (angles, t), counters, match_rows [n_match, 11]."""
+        a, b, cnt = np.zeros(6), np.zeros(6), np.zeros(2, dtype=np.int32)
+        if not self.L.ref_vloam_get_vo(self.h, _vp(a), _vp(b), _vp(cnt)):
+            return None
+        rows = np.zeros((max(n_match, 1), 11))
+        assert self.L.ref_vloam_get_vo_rows(self.h, _vp(rows), n_match) == n_match
+        return dict(x_in=a, x_out=b, counter32=int(cnt[0]), counter22=int(cnt[1]), match_rows=rows[:n_match])
+
+    def buckets(self):
+        """(bucket_x, bucket_y, bucket_depth, bucket_count) of the current frame's depth map, flattened like VO.buckets."""
+        nb = VO.N_BUCKETS
+        bx, by, bd = [np.zeros(nb, dtype=np.float32) for _ in range(3)]
+        bc = np.zeros(nb, dtype=np.int32)
+        dims = np.zeros(2, dtype=np.int32)
+        n = self.L.ref_vloam_get_buckets(self.h, _vp(bx), _vp(by), _vp(bd), _vp(bc), nb, _vp(dims))
+        assert n == nb and tuple(dims) == (249, 75), (n, dims)
+        return bx, by, bd, bc
+
+    def cloud(self, which):
+        n = self.L.ref_vloam_get_cloud(self.h, which, None, 0)
+        if n < 0:
+            return None
+        buf = np.zeros((max(n, 1), 4), dtype=np.float32)
+        self.L.ref_vloam_get_cloud(self.h, which, _vp(buf), n)
+        return buf[:n]
+
+    def skip_frame(self):
+        return bool(self.L.ref_vloam_skip_frame(self.h))
+
+    def map_ran(self):
+        return bool(self.L.ref_vloam_map_ran(self.h))
+
+    def lo_pose(self):
+        q, t = np.zeros(4), np.zeros(3)
+        self.L.ref_vloam_get_lo_pose(self.h, _vp(q), _vp(t))
+        return q, t
+
+    def published_pose(self, topic):
+        q, t = np.zeros(4), np.zeros(3)
+        return (q, t) if self.L.ref_vloam_get_published_pose(self.h, topic, _vp(q), _vp(t)) == 0 else None
+
+    def solves(self):
+        """Every ceres::Solve of the last frame in call order: stage (VO / ODOMETRY / MAPPING), x_in, x_out, max_num_iterations, types, nres,
+        payload [blocks, 13], residuals0."""
+        out = []
+        for k in range(self.L.ref_vloam_num_solves(self.h)):
+            b, a, info = np.zeros(7), np.zeros(7), np.zeros(5, dtype=np.int32)
+            assert self.L.ref_vloam_get_solve(self.h, k, _vp(b), _vp(a), _vp(info)) == 0
+            nb, nr, npar = int(info[1]), int(info[2]), int(info[4])
+            types, nres = np.zeros(max(nb, 1), dtype=np.int32), np.zeros(max(nb, 1), dtype=np.int32)
+            payload, raw = np.zeros((max(nb, 1), 13)), np.zeros(max(nr, 1))
+            assert self.L.ref_vloam_get_solve_blocks(self.h, k, _vp(types), _vp(nres), _vp(payload), _vp(raw)) == 0
+            out.append(dict(stage=int(info[0]), x_in=b[:npar].copy(), x_out=a[:npar].copy(), max_num_iterations=int(info[3]), types=types[:nb], nres=nres[:nb],
+                            payload=payload[:nb], residuals0=raw[:nr]))
+        return out
+
+    def rows_text(self, which):
+        """The bytes written so far by VO2Cam0StartFrame (0), LO2Cam0StartFrame (1), MO2Cam0StartFrame (2); None when save_traj is off."""
+        n = self.L.ref_vloam_get_rows_text(self.h, which, None, 0)
+        if n < 0:
+            return None
+        buf = C.create_string_buffer(max(n, 1))
+        self.L.ref_vloam_get_rows_text(self.h, which, buf, n)
+        return buf.raw[:n]

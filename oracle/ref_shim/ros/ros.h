@@ -3,7 +3,7 @@
 //  * ros::param::get(name, value) — the parameter server is a map the harness fills (ros::param::shim_store()); like roscpp it returns
 //    false and leaves `value` untouched when the name is unknown, and converts a stored number to the requested type;
 //  * NodeHandle / Publisher — advertise(topic) hands out a Publisher bound to the topic; publish(msg) keeps a copy of the LAST message per
-//    topic in ros::shim_topics(), where the harness reads it back (ros::shim_last<M>(topic)); Time — always zero;
+//    topic in ros::shim_topics(), where the harness reads it back (ros::shim_last<M>(topic)); Time — always zero; Duration — a number;
 //  * ROS_INFO / ROS_WARN / ROS_ERROR / ROS_DEBUG — no-ops; ROS_BREAK — aborts, as ros/assert.h does.
 // No math header is included and no math function is declared here on purpose: see tf/LinearMath/Scalar.h.
 #pragma once
@@ -44,8 +44,15 @@ inline bool get(const std::string& key, bool& v) {
 
 struct Time {
   double sec = 0.0;
+  Time() {}
+  explicit Time(double s) : sec(s) {}
   static Time now() { return Time(); }
   double toSec() const { return sec; }
+};
+struct Duration {
+  double sec = 0.0;
+  Duration() {}
+  explicit Duration(double s) : sec(s) {}
 };
 
 inline std::map<std::string, std::shared_ptr<const void>>& shim_topics() { static std::map<std::string, std::shared_ptr<const void>> m; return m; }

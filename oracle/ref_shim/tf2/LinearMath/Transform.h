@@ -12,6 +12,9 @@
 // getAxis() = (x, y, z) / sqrt(1 - w^2), or (1, 0, 0) when 1 - w^2 < 10 DBL_EPSILON; setRotation(axis, angle) = (axis sin(angle / 2) /
 // |axis|, cos(angle / 2)); getX() ... of Vector3 and Quaternion; the nine-scalar Matrix3x3 constructor and Transform::setBasis; the
 // conversion to const double* through which Eigen::Quaterniond / Vector3d are built from them (visual_odometry.cpp:457-458).
+//
+// For vloam_tf.cpp: Transform(q, origin) builds the basis by setRotation(q); a *= b is origin += basis * b.origin, THEN basis *= b.basis
+// (tf2's order: the origin is moved with the basis as it was before the product).
 #pragma once
 #include <cfloat>
 #include <cmath>
@@ -137,6 +140,8 @@ class Transform {
  public:
   Transform() {}
   Transform(const Matrix3x3& b, const Vector3& o) : basis_(b), origin_(o) {}
+  Transform(const Quaternion& q, const Vector3& o) : origin_(o) { basis_.setRotation(q); }   // Matrix3x3(q) = setRotation(q)
+  Transform& operator*=(const Transform& t) { origin_ = (*this)(t.origin_); basis_ = basis_ * t.basis_; return *this; }   // origin first, as tf2
   void setIdentity() { basis_.setIdentity(); origin_ = Vector3(0, 0, 0); }
   void setOrigin(const Vector3& o) { origin_ = o; }
   void setRotation(const Quaternion& q) { basis_.setRotation(q); }

@@ -1,5 +1,9 @@
-// REFERENCE-BUILD STAND-IN — TEST INFRASTRUCTURE ONLY (our own text).  VloamTF holds one by value; it broadcasts nothing here.
+// REFERENCE-BUILD STAND-IN — TEST INFRASTRUCTURE ONLY (our own text).  VloamTF holds one by value; sendTransform broadcasts nothing here.
 #pragma once
+#include <geometry_msgs/TransformStamped.h>
 namespace tf2_ros {
-class TransformBroadcaster {};
+class TransformBroadcaster {
+ public:
+  void sendTransform(const geometry_msgs::TransformStamped&) {}
+};
 }  // namespace tf2_ros

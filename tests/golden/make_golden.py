@@ -157,12 +157,22 @@ def run_ref_vo_cases():
     return out
 
 
+def run_ref_vloam_cases():
+    """tests/golden/ref_vloam_*.npz: the coupled frame loop through the reference's own vloam_tf.cpp / lidar_odometry_mapping.cpp and everything
+    below them (oracle/_ref/libref_vloam.so; scenarios and layout: tests/ref_vloam_cases.py)."""
+    import ref
+    import ref_vloam_cases
+    return {"ref_vloam_" + name: ref_vloam_cases.record(ref, sc) for name, sc in sorted(ref_vloam_cases.scenarios().items())}
+
+
 def write_ref_sr_cases():
     for name, d in run_ref_sr_cases().items():
         np.savez_compressed(os.path.join(HERE, "ref_sr_%s.npz" % name), **d)
     for stem, d in run_ref_loam_cases().items():
         np.savez_compressed(os.path.join(HERE, stem + ".npz"), **d)
     for stem, d in run_ref_vo_cases().items():
+        np.savez_compressed(os.path.join(HERE, stem + ".npz"), **d)
+    for stem, d in run_ref_vloam_cases().items():
         np.savez_compressed(os.path.join(HERE, stem + ".npz"), **d)
 
 
@@ -172,6 +182,10 @@ if __name__ == "__main__":
         sys.exit(0)
     if len(sys.argv) > 1 and sys.argv[1] == "vo":
         for stem, d in run_ref_vo_cases().items():
+            np.savez_compressed(os.path.join(HERE, stem + ".npz"), **d)
+        sys.exit(0)
+    if len(sys.argv) > 1 and sys.argv[1] == "vloam":
+        for stem, d in run_ref_vloam_cases().items():
             np.savez_compressed(os.path.join(HERE, stem + ".npz"), **d)
         sys.exit(0)
     import ref

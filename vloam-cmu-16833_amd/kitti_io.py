@@ -192,6 +192,40 @@ def angle_axis_to_T(aa, t):
     return make_T(q, t)
 
 
+def tf2_rotation_of(R):
+    """tf2::Matrix3x3::getRotation: the quaternion (x, y, z, w) tf2::toMsg puts into a message — not normalised afterwards."""
+    tr = R[0, 0] + R[1, 1] + R[2, 2]
+    q = np.zeros(4)
+    if tr > 0.0:
+        s = np.sqrt(tr + 1.0)
+        q[3] = s * 0.5
+        s = 0.5 / s
+        q[0], q[1], q[2] = (R[2, 1] - R[1, 2]) * s, (R[0, 2] - R[2, 0]) * s, (R[1, 0] - R[0, 1]) * s
+    else:
+        i = (2 if R[1, 1] < R[2, 2] else 1) if R[0, 0] < R[1, 1] else (2 if R[0, 0] < R[2, 2] else 0)
+        j, k = (i + 1) % 3, (i + 2) % 3
+        s = np.sqrt(R[i, i] - R[j, j] - R[k, k] + 1.0)
+        q[i] = s * 0.5
+        s = 0.5 / s
+        q[3], q[j], q[k] = (R[k, j] - R[j, k]) * s, (R[j, i] + R[i, j]) * s, (R[k, i] + R[i, k]) * s
+    return q
+
+
+def transform_to_eigen_f32(T):
+    """tf2::transformToEigen(tf2::toMsg(T)).cast<float>() (vloam_tf.cpp:89): the basis goes through tf2's quaternion and comes back through
+    Eigen's Quaternion::toRotationMatrix (no normalisation), then every coefficient is rounded to f32.  The round trip matters for the
+    printed rows: an entry that the matrix product leaves at -1e-17 comes back as +0 or a tiny positive number, so the reference prints
+    "0.000000" where the product itself would print "-0.000000"."""
+    x, y, z, w = tf2_rotation_of(np.asarray(T, dtype=np.float64)[:3, :3])
+    tx, ty, tz = 2.0 * x, 2.0 * y, 2.0 * z
+    twx, twy, twz = tx * w, ty * w, tz * w
+    txx, txy, txz, tyy, tyz, tzz = tx * x, ty * x, tz * x, ty * y, tz * y, tz * z
+    out = np.eye(4)
+    out[:3, :3] = [[1.0 - (tyy + tzz), txy - twz, txz + twy], [txy + twz, 1.0 - (txx + tzz), tyz - twx], [txz - twy, tyz + twx, 1.0 - (txx + tyy)]]
+    out[:3, 3] = np.asarray(T, dtype=np.float64)[:3, 3]
+    return out.astype(np.float32)
+
+
 class VloamTF:
     """The transform blackboard of src/vloam_tf (static extrinsics + the VO / LO / MO chains), ROS-free."""
 
@@ -226,7 +260,7 @@ class VloamTF:
         cam0_init_T_cam0_last = inv_T(self.base_T_cam0) @ world_T_base_last @ self.base_T_cam0
         if count == 0:
             self._start[key] = cam0_init_T_cam0_last
-        return (inv_T(self._start[key]) @ cam0_init_T_cam0_last).astype(np.float32)  # .cast<float>() before printing
+        return transform_to_eigen_f32(inv_T(self._start[key]) @ cam0_init_T_cam0_last)   # toMsg -> transformToEigen -> cast<float>() before printing
 
     def VO2Cam0StartFrame(self, count):
         return self._to_cam0_start("VO", self.world_VOT_base_last, count)
