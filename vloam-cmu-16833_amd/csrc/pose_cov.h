@@ -16,13 +16,9 @@ namespace vloam {
 constexpr int kPcThreads = 256;        // the VO reduction's workgroup
 constexpr int kPcSlotsPerBlock = 512;  // VO table slots a workgroup takes per trip (2 per lane: the dual-number evaluation is long)
 constexpr int kPcMaxBlocks = 16;       // workgroups of the VO reduction at most (their partials are added in workgroup order)
-constexpr int kPcAcc = 24;             // cost, 21 upper-triangle sums of J^T J, CostFunctor32 blocks, CostFunctor22 blocks
-// per session: the ticket the workgroups of a VO launch draw and their partial sums
-struct PoseCovScratch {
-  int ticket;
-  int pad[15];
-  double part[kPcMaxBlocks][kPcAcc];
-};
+// per session: the ticket the workgroups of a VO launch draw and their partial sums (pose_rows_dev.h, which only the kernels' units see)
+template <int MaxBlocks> struct PoseRowsScratch;
+using PoseCovScratch = PoseRowsScratch<kPcMaxBlocks>;
 
 struct PoseCov {   // device memory of the product, one allocation each, not in the arenas
   vloam_pose_cov_record* rows = nullptr;   // [B][max_frames]
@@ -33,6 +29,7 @@ struct PoseCov {   // device memory of the product, one allocation each, not in 
 
 inline int pose_cov_vo_blocks(int cap) { const int g = (cap + kPcSlotsPerBlock - 1) / kPcSlotsPerBlock; return g < 1 ? 1 : (g > kPcMaxBlocks ? kPcMaxBlocks : g); }
 
+size_t pose_cov_scratch_bytes(int n_sessions);
 // rows of a fresh product: zero, frame = -1 (all sessions); scratch zero
 hipError_t pose_cov_init(hipStream_t st, const PoseCov& P, int n_sessions);
 // stage 0 (odometry) / 1 (mapping) of sweep `frame`, on that stage's stream directly behind pose_info_launch of the same stage and sweep.

@@ -10,12 +10,11 @@
 // the matrix and of the accumulated rotations V in registers, neighbours are fetched by cross-lane shuffles, and the three disjoint rotations of
 // a step are applied to all 36 elements at once (A <- J^T A J in one pass of four products per element, V <- V J) — five dependent steps per
 // sweep instead of the fifteen rotations' worth of work one lane does there.  Same stopping rule.
-// This unit keeps its OWN text of the few shared lines (the rotation, the Huber weight, the two VO functors), for the reason pose_info.hip and
-// map_grow.hip keep theirs: the code objects of the solver, of k_pose_info_* and of the sweep kernels stay what they are.
+// The sums, their reduction and ticket, the Huber weight, the rotation and the rows' init are pose_rows_dev.h's, one text with pose_info.hip.  This
+// unit keeps its OWN text of the two VO functors, for the reason pose_info.hip and map_grow.hip keep theirs: the code objects of
+// the solver and of the sweep kernels stay what they are.
 #include "pose_cov.h"
-#include <float.h>
-#include <stddef.h>
-#include <algorithm>
+#include "pose_rows_dev.h"
 
 namespace vloam {
 
@@ -23,22 +22,10 @@ static_assert(sizeof(vloam_pose_cov_record) == 2288 && offsetof(vloam_pose_cov_r
                   offsetof(vloam_pose_cov_record, map_eig) == 688 && offsetof(vloam_pose_cov_record, vo_x) == 1312 &&
                   offsetof(vloam_pose_cov_record, vo_eig) == 1664,
               "8 ints, 4 doubles, two halves of 78 doubles (eig[6], V[36], cov[36], contiguous), the VO half of 122");
+static_assert(sizeof(PoseCovScratch) == 64 + sizeof(double) * kPcMaxBlocks * kPoseAcc && offsetof(PoseCovScratch, part) == 64,
+              "the partials on a line of their own behind the ticket");
 
 // ---------------------------------------------------------------------------------------------- lane-parallel Jacobi
-// Rotation in the (p, q) plane, p < q: d = (a_qq - a_pp) / 2, b = a_pq, t = tan(theta) = b sign(d) / (|d| + sqrt(d^2 + b^2)) (|theta| <= pi / 4),
-// c = 1 / sqrt(1 + t^2), s = t c.  J has J_pp = J_qq = c, J_pq = s, J_qp = -s; A <- J^T A J zeroes a_pq.
-struct PcRot { double c, s; };
-__device__ __forceinline__ PcRot pc_rot(double app, double aqq, double apq) {
-  const double d = 0.5 * (aqq - app), b = apq;
-  const double r2 = d * d + b * b;
-  const double r = r2 * rsqrt(fmax(r2, DBL_MIN));
-  const double tt = (d < 0.0 ? -b : b) / (fabs(d) + r);
-  const double t = b == 0.0 ? 0.0 : tt;
-  PcRot R;
-  R.c = rsqrt(1.0 + t * t);
-  R.s = t * R.c;
-  return R;
-}
 // the partner of every index in the five steps of the round robin over six indices, 3 bits each:
 // (0,5)(1,4)(2,3) | (0,4)(3,5)(1,2) | (0,3)(2,4)(1,5) | (0,2)(1,3)(4,5) | (0,1)(2,5)(3,4)
 constexpr unsigned pc_pack(unsigned a, unsigned b, unsigned c, unsigned d, unsigned e, unsigned f) {
@@ -74,14 +61,14 @@ __device__ __forceinline__ void pc_jacobi6(double& a, double& v, int r, int c) {
       const int rp = (int)((tab >> (3 * ar)) & 7u), cp = (int)((tab >> (3 * ac)) & 7u), vp = (int)((tab >> (3 * c)) & 7u);
       // the rotations of the row index's pair and of the column index's pair, from the elements as they are before the step
       const int rP = ar < rp ? ar : rp, rQ = ar < rp ? rp : ar, cP = ac < cp ? ac : cp, cQ = ac < cp ? cp : ac;
-      const PcRot Rr = pc_rot(__shfl(a, rP * 7), __shfl(a, rQ * 7), __shfl(a, rP * 6 + rQ));
-      const PcRot Rc = pc_rot(__shfl(a, cP * 7), __shfl(a, cQ * 7), __shfl(a, cP * 6 + cQ));
+      const PoseRot Rr = pose_rot(__shfl(a, rP * 7), __shfl(a, rQ * 7), __shfl(a, rP * 6 + rQ));
+      const PoseRot Rc = pose_rot(__shfl(a, cP * 7), __shfl(a, cQ * 7), __shfl(a, cP * 6 + cQ));
       const double sr = ar < rp ? -Rr.s : Rr.s, sc = ac < cp ? -Rc.s : Rc.s;   // J[rp][ar], J[cp][ac]
       // A'[r][c] = sum over i in {r, r'}, j in {c, c'} of J[i][r] A[i][j] J[j][c]
       const double a_rcp = __shfl(a, ar * 6 + cp), a_rpc = __shfl(a, rp * 6 + ac), a_rpcp = __shfl(a, rp * 6 + cp);
       const double an = Rr.c * (Rc.c * a + sc * a_rcp) + sr * (Rc.c * a_rpc + sc * a_rpcp);
       // V'[r][c] = V[r][c] J[c][c] + V[r][c'] J[c'][c]  (c's own pair: the same rotation as one of the two above)
-      const PcRot Rv = c == ac ? Rc : Rr;
+      const PoseRot Rv = c == ac ? Rc : Rr;
       const double sv = c < vp ? -Rv.s : Rv.s;
       const double v_p = __shfl(v, r * 6 + vp);
       v = Rv.c * v + sv * v_p;
@@ -205,25 +192,6 @@ __device__ __forceinline__ void pc_rotate(const PcDual (&w_)[3], const double (&
     for (int k = 0; k < 3; k++) out[k] = pc_const(pt[k]) + wxp[k];
   }
 }
-__device__ __forceinline__ void pc_add_row(double (&acc)[kPcAcc], const double (&J)[6], double w) {
-  int h = 1;
-#pragma unroll
-  for (int a = 0; a < 6; a++) {
-    const double wj = w * J[a];
-#pragma unroll
-    for (int b = a; b < 6; b++) acc[h++] += wj * J[b];
-  }
-}
-// ceres::HuberLoss(a) on s = |r|^2: rho (added to the cost as rho / 2) and rho'.  rho'' <= 0: the Gauss-Newton matrix of the block is rho' J^T J.
-__device__ __forceinline__ double pc_huber(double s, double a, double* cost) {
-  if (s > a * a) {
-    const double r = sqrt(s);
-    *cost += 0.5 * (2.0 * a * r - a * a);
-    return a / r;
-  }
-  *cost += 0.5 * s;
-  return 1.0;
-}
 
 __global__ __launch_bounds__(kPcThreads) void k_pose_cov_vo(const int* __restrict__ type, const double* __restrict__ p, const double* __restrict__ A, int cap,
                                                             const double* __restrict__ x_, vloam_pose_cov_record* rows, PoseCovScratch* scratch,
@@ -233,10 +201,8 @@ __global__ __launch_bounds__(kPcThreads) void k_pose_cov_vo(const int* __restric
   const int z = (int)blockIdx.z, G = (int)gridDim.x, wg = (int)blockIdx.x, tid = threadIdx.x;
   vloam_pose_cov_record* row = rows + (size_t)z * (size_t)max_frames + frame;
   PoseCovScratch* sc = scratch + z;
-  __shared__ double s_w[kPcThreads / 64][kPcAcc];
-  __shared__ double s_tot[kPcAcc];
+  __shared__ double s_tot[kPoseAcc];
   __shared__ double s_H[36], s_e[6], s_V[36];
-  __shared__ int s_last;
   double x[6];
 #pragma unroll
   for (int i = 0; i < 6; i++) x[i] = x_[i];
@@ -244,9 +210,9 @@ __global__ __launch_bounds__(kPcThreads) void k_pose_cov_vo(const int* __restric
   // the half stays zero, VO_VALID clear.  Uniform over the launch: every workgroup leaves before the ticket
   const double angle = sqrt((x[0] * x[0] + x[1] * x[1]) + x[2] * x[2]);
   if (!(angle > 0.0) || !(angle <= DBL_MAX) || !(fabs(x[3]) <= DBL_MAX) || !(fabs(x[4]) <= DBL_MAX) || !(fabs(x[5]) <= DBL_MAX)) return;
-  double acc[kPcAcc];
+  double acc[kPoseAcc];
 #pragma unroll
-  for (int i = 0; i < kPcAcc; i++) acc[i] = 0.0;
+  for (int i = 0; i < kPoseAcc; i++) acc[i] = 0.0;
   const PcDual w[3] = {pc_var(x[0], 0), pc_var(x[1], 1), pc_var(x[2], 2)};
   const PcDual t[3] = {pc_var(x[3], 3), pc_var(x[4], 4), pc_var(x[5], 5)};
   const double huber_a = 0.1;
@@ -261,9 +227,9 @@ __global__ __launch_bounds__(kPcThreads) void k_pose_cov_vo(const int* __restric
       pc_rotate(w, X0, X1);
       for (int k = 0; k < 3; k++) X1[k] = X1[k] + t[k];
       const PcDual q0 = X1[0] - X1[2] * ox, q1 = X1[1] - X1[2] * oy;
-      const double wt = pc_huber(q0.a * q0.a + q1.a * q1.a, huber_a, &acc[0]);
-      pc_add_row(acc, q0.v, wt);
-      pc_add_row(acc, q1.v, wt);
+      const double wt = pose_huber(q0.a * q0.a + q1.a * q1.a, huber_a, &acc[0]);
+      pose_add_row(acc, q0.v, wt);
+      pose_add_row(acc, q1.v, wt);
       acc[22] += 1.0;
     } else {
       // CostFunctor22 (:159-174): r = (x1_bar, y1_bar, 1) . (t x R (x0_bar, y0_bar, 1))
@@ -272,46 +238,14 @@ __global__ __launch_bounds__(kPcThreads) void k_pose_cov_vo(const int* __restric
       pc_rotate(w, X0, RX);
       const PcDual c0 = t[1] * RX[2] - t[2] * RX[1], c1 = t[2] * RX[0] - t[0] * RX[2], c2 = t[0] * RX[1] - t[1] * RX[0];
       const PcDual q0 = c0 * ox + c1 * oy + c2;
-      const double wt = pc_huber(q0.a * q0.a, huber_a, &acc[0]);
-      pc_add_row(acc, q0.v, wt);
+      const double wt = pose_huber(q0.a * q0.a, huber_a, &acc[0]);
+      pose_add_row(acc, q0.v, wt);
       acc[23] += 1.0;
     }
   }
-  // lanes -> wavefront (cross-lane), wavefronts -> workgroup (LDS, wavefront order), workgroup -> HBM
-#pragma unroll
-  for (int i = 0; i < kPcAcc; i++) {
-    double v = acc[i];
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) v += __shfl_xor(v, d);
-    acc[i] = v;
-  }
-  if ((tid & 63) == 0) {
-#pragma unroll
-    for (int i = 0; i < kPcAcc; i++) s_w[tid >> 6][i] = acc[i];
-  }
-  __syncthreads();
-  if (tid < kPcAcc) {
-    double v = s_w[0][tid];
-    for (int k = 1; k < kPcThreads / 64; k++) v += s_w[k][tid];
-    sc->part[wg][tid] = v;
-  }
-  // the ticket: every workgroup publishes its partial (device-scope fence), then draws; the last one finishes the half
-  __threadfence();
-  __syncthreads();
-  if (tid == 0) s_last = atomicAdd(&sc->ticket, 1) == G - 1 ? 1 : 0;
-  __syncthreads();
-  if (!s_last) return;
-  __threadfence();
-  if (tid < kPcAcc) {
-    double v = 0.0;
-    for (int k = 0; k < G; k++) v += __hip_atomic_load(&sc->part[k][tid], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // workgroup order
-    s_tot[tid] = v;
-  }
-  if (tid == 0) sc->ticket = 0;   // for the next frame's launch (same stream, behind this one)
-  __syncthreads();
-  if (tid < 36) {   // mirror the upper triangle: element (r, c) sits at 1 + r (13 - r) / 2 + (c - r) of the sums
-    const int r = tid / 6, c = tid % 6, lo = r < c ? r : c, hi = r < c ? c : r;
-    const double v = s_tot[1 + lo * (13 - lo) / 2 + (hi - lo)];
+  if (!pose_rows_reduce<kPcThreads>(acc, sc, s_tot)) return;   // the workgroup with the last ticket finishes the half
+  if (tid < 36) {   // mirror the upper triangle
+    const double v = pose_rows_H(s_tot, tid);
     s_H[tid] = v;
     row->vo_H[tid] = v;
   }
@@ -325,20 +259,9 @@ __global__ __launch_bounds__(kPcThreads) void k_pose_cov_vo(const int* __restric
   pc_decompose(s_H, s_e, s_V, row->vo_eig, row, 2, s_tot[0], 2 * (int)s_tot[22] + (int)s_tot[23], min_eig, tid);
 }
 
-__global__ __launch_bounds__(64) void k_pose_cov_init(vloam_pose_cov_record* rows, long long n_rows) {
-  for (long long r = (long long)blockIdx.x * 64 + threadIdx.x; r < n_rows; r += (long long)gridDim.x * 64) {
-    int* w = reinterpret_cast<int*>(rows + r);
-    for (int k = 0; k < (int)(sizeof(vloam_pose_cov_record) / sizeof(int)); k++) w[k] = 0;
-    rows[r].frame = -1;
-  }
-}
-
+size_t pose_cov_scratch_bytes(int n_sessions) { return sizeof(PoseCovScratch) * (size_t)n_sessions; }
 hipError_t pose_cov_init(hipStream_t st, const PoseCov& P, int n_sessions) {
-  const long long n = (long long)P.max_frames * n_sessions;
-  hipLaunchKernelGGL(k_pose_cov_init, vl_hw_grid(dim3((unsigned)std::min<long long>((n + 63) / 64, 1024), 1, 1)), dim3(64), 0, st, P.rows, n);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return e;
-  return hipMemsetAsync(P.scratch, 0, sizeof(PoseCovScratch) * (size_t)n_sessions, st);
+  return pose_rows_init(st, P.rows, (long long)P.max_frames * n_sessions, P.scratch, pose_cov_scratch_bytes(n_sessions));
 }
 
 // (the kernels of this unit carry no id of the per-kernel event timer: its table ends with k_pose_info_map, and the pose information launch in

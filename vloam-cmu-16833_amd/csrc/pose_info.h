@@ -13,13 +13,9 @@ namespace vloam {
 constexpr int kPiThreads = 256;
 constexpr int kPiMaxBlocks = 64;       // workgroups of one reduce launch at most (their partials are added in workgroup order)
 constexpr int kPiSlotsPerBlock = 2048; // table slots a workgroup takes per trip (8 per lane)
-constexpr int kPiAcc = 24;             // cost, 21 upper-triangle sums of J^T J, edge blocks, plane blocks
-// per (stage, session): the ticket the workgroups of a launch draw and their partial sums
-struct PoseInfoScratch {
-  int ticket;
-  int pad[15];
-  double part[kPiMaxBlocks][kPiAcc];
-};
+// per (stage, session): the ticket the workgroups of a launch draw and their partial sums (pose_rows_dev.h, which only the kernels' units see)
+template <int MaxBlocks> struct PoseRowsScratch;
+using PoseInfoScratch = PoseRowsScratch<kPiMaxBlocks>;
 
 struct PoseInfo {   // device memory of the product, one allocation each, not in the arenas
   vloam_pose_info_record* rows = nullptr;   // [B][max_frames]
@@ -30,6 +26,7 @@ struct PoseInfo {   // device memory of the product, one allocation each, not in
 
 inline int pose_info_blocks(int cap) { const int g = (cap + kPiSlotsPerBlock - 1) / kPiSlotsPerBlock; return g < 1 ? 1 : (g > kPiMaxBlocks ? kPiMaxBlocks : g); }
 
+size_t pose_info_scratch_bytes(int n_sessions);
 // rows of a fresh product: zero, frame = -1 (all sessions); scratch zero
 hipError_t pose_info_init(hipStream_t st, const PoseInfo& P, int n_sessions);
 // stage 0 (odometry) / 1 (mapping) of sweep `frame`, on that stage's stream behind its last solve.  F: the table of the last outer round (read by

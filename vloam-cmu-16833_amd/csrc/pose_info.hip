@@ -8,61 +8,27 @@
 //            a row is bit-identical from run to run), mirrors the 6 x 6, runs cyclic Jacobi on it in f64 to convergence (one lane, the matrix in registers), sorts the eigenvalues,
 //            sets the flags and writes its half of the row with plain vector stores.
 // This unit keeps its OWN text of the three LiDAR factor evaluations (edge, plane, plane-norm at s = 1), for the reason k_map_grow keeps its own
-// (DESIGN.md §8): the code objects of the solver and of the association kernels stay what they are.
+// (DESIGN.md §8): the code objects of the solver and of the association kernels stay what they are.  The sums, their reduction and ticket, the
+// Huber weight, the rotation and the rows' init are pose_rows_dev.h's, one text with pose_cov.hip.
 #include "pose_info.h"
-#include <float.h>
-#include <stddef.h>
-#include <algorithm>
+#include "pose_rows_dev.h"
 
 namespace vloam {
 
 static_assert(sizeof(vloam_pose_info_record) == 832 && offsetof(vloam_pose_info_record, lo_x) == 32 && offsetof(vloam_pose_info_record, map_x) == 432,
               "8 ints, then two halves of 50 doubles");
+static_assert(sizeof(PoseInfoScratch) == 64 + sizeof(double) * kPiMaxBlocks * kPoseAcc && offsetof(PoseInfoScratch, part) == 64,
+              "the partials on a line of their own behind the ticket");
 constexpr int kPiHalf = 50;   // doubles per stage: x[7], cost, H[36], eig[6]
-
-__device__ __forceinline__ void pi_add_row(double (&acc)[kPiAcc], const double (&J)[6], double w) {
-  int h = 1;
-#pragma unroll
-  for (int a = 0; a < 6; a++) {
-    const double wj = w * J[a];
-#pragma unroll
-    for (int b = a; b < 6; b++) acc[h++] += wj * J[b];
-  }
-}
-
-// ceres::HuberLoss(a) on s = |r|^2: rho (added to the cost as rho / 2) and rho'.  rho'' <= 0, so ceres' Corrector scales residual and Jacobian
-// by sqrt(rho') and the Gauss-Newton matrix of the block is rho' J^T J.
-__device__ __forceinline__ double pi_huber(double s, double a, double* cost) {
-  if (s > a * a) {
-    const double r = sqrt(s);
-    *cost += 0.5 * (2.0 * a * r - a * a);
-    return a / r;
-  }
-  *cost += 0.5 * s;
-  return 1.0;
-}
 
 // Eigenvalues of the symmetric 6 x 6 A (row-major in LDS) -> d[6] ascending.  Cyclic Jacobi in the parallel (round-robin) ordering: a sweep is five
 // steps of three rotations in disjoint planes, 15 pairs in all; the matrix sits in the registers of ONE lane with every index a compile-time
 // constant, and the three rotations of a step are written side by side so that their dependent f64 chains (one division, two reciprocal
-// square roots each) overlap.  Rotation in the (p, q) plane: d = (a_qq - a_pp) / 2, b = a_pq, t = tan(theta) = b sign(d) / (|d| + sqrt(d^2 + b^2))
-// (the smaller root: |theta| <= pi / 4), c = 1 / sqrt(1 + t^2), s = t c; A <- J^T A J zeroes a_pq.  Converged when every off-diagonal element
+// square roots each) overlap.  The rotation is pose_rot (pose_rows_dev.h).  Converged when every off-diagonal element
 // is below half an ulp of the largest diagonal element (the eigenvalues are then the diagonal to ~1e-16 |A|; the convergence is quadratic,
 // four to six sweeps); a matrix with a NaN runs into the sweep cap.
-struct PiRot { double c, s; };
-__device__ __forceinline__ PiRot pi_rot(double app, double aqq, double apq) {
-  const double d = 0.5 * (aqq - app), b = apq;
-  const double r2 = d * d + b * b;
-  const double r = r2 * rsqrt(fmax(r2, DBL_MIN));
-  const double tt = (d < 0.0 ? -b : b) / (fabs(d) + r);
-  const double t = b == 0.0 ? 0.0 : tt;
-  PiRot R;
-  R.c = rsqrt(1.0 + t * t);
-  R.s = t * R.c;
-  return R;
-}
 template <int P, int Q>
-__device__ __forceinline__ void pi_apply(double (&a)[6][6], PiRot R) {
+__device__ __forceinline__ void pi_apply(double (&a)[6][6], PoseRot R) {
 #pragma unroll
   for (int i = 0; i < 6; i++) {   // columns p, q
     const double x = a[i][P], y = a[i][Q];
@@ -79,7 +45,7 @@ __device__ __forceinline__ void pi_apply(double (&a)[6][6], PiRot R) {
 }
 template <int P0, int Q0, int P1, int Q1, int P2, int Q2>
 __device__ __forceinline__ void pi_step(double (&a)[6][6]) {
-  const PiRot R0 = pi_rot(a[P0][P0], a[Q0][Q0], a[P0][Q0]), R1 = pi_rot(a[P1][P1], a[Q1][Q1], a[P1][Q1]), R2 = pi_rot(a[P2][P2], a[Q2][Q2], a[P2][Q2]);
+  const PoseRot R0 = pose_rot(a[P0][P0], a[Q0][Q0], a[P0][Q0]), R1 = pose_rot(a[P1][P1], a[Q1][Q1], a[P1][Q1]), R2 = pose_rot(a[P2][P2], a[Q2][Q2], a[P2][Q2]);
   pi_apply<P0, Q0>(a, R0);   // disjoint planes: the three rotations commute
   pi_apply<P1, Q1>(a, R1);
   pi_apply<P2, Q2>(a, R2);
@@ -128,17 +94,15 @@ __device__ __forceinline__ void pose_info_body(const int* __restrict__ type, con
   const int z = (int)blockIdx.z, G = (int)gridDim.x, wg = (int)blockIdx.x, tid = threadIdx.x;
   vloam_pose_info_record* row = rows + (size_t)z * (size_t)max_frames + frame;
   PoseInfoScratch* sc = scratch + (size_t)stage * gridDim.z + z;
-  __shared__ double s_w[kPiThreads / 64][kPiAcc];
-  __shared__ double s_tot[kPiAcc];
+  __shared__ double s_tot[kPoseAcc];
   __shared__ double s_half[kPiHalf];
   __shared__ double s_a[36];
-  __shared__ int s_last;
   // the solve ran: the host's knowledge (first sweep, skipped sweep) and the device's gate (MapState::do_optimize).  Otherwise neither the table
   // nor the record is this sweep's, and neither is read
   const int on = (ran && (enable ? *enable : 1)) ? 1 : 0;
-  double acc[kPiAcc];
+  double acc[kPoseAcc];
 #pragma unroll
-  for (int i = 0; i < kPiAcc; i++) acc[i] = 0.0;
+  for (int i = 0; i < kPoseAcc; i++) acc[i] = 0.0;
   if (on) {
     double x[7];
 #pragma unroll
@@ -168,63 +132,31 @@ __device__ __forceinline__ void pose_info_body(const int* __restrict__ type, con
 #pragma unroll
         for (int q = 0; q < 8; q++) e[q] = dg[q * cap + slot];
         const double c1 = (e[0] * lx + e[1] * ly + e[2] * lz) + e[6], c2 = (e[3] * lx + e[4] * ly + e[5] * lz) + e[7];
-        const double w = pi_huber(c1 * c1 + c2 * c2, huber_a, &acc[0]);
+        const double w = pose_huber(c1 * c1 + c2 * c2, huber_a, &acc[0]);
         const double J1[6] = {-2.0 * (e[1] * rz - e[2] * ry), -2.0 * (e[2] * rx - e[0] * rz), -2.0 * (e[0] * ry - e[1] * rx), e[0], e[1], e[2]};
         const double J2[6] = {-2.0 * (e[4] * rz - e[5] * ry), -2.0 * (e[5] * rx - e[3] * rz), -2.0 * (e[3] * ry - e[4] * rx), e[3], e[4], e[5]};
-        pi_add_row(acc, J1, w);
-        pi_add_row(acc, J2, w);
+        pose_add_row(acc, J1, w);
+        pose_add_row(acc, J2, w);
         acc[22] += 1.0;
       } else {
         // LidarPlaneFactor (:72-93, (lp - j) . n) and LidarPlaneNormFactor (:115-127, n . lp + negative_OA_dot_norm) in the common form
         // r = n . lp + d
         const double nx = dg[slot], ny = dg[cap + slot], nz = dg[2 * cap + slot], d = dg[3 * cap + slot];
         const double r0 = (nx * lx + ny * ly + nz * lz) + d;
-        const double w = pi_huber(r0 * r0, huber_a, &acc[0]);
+        const double w = pose_huber(r0 * r0, huber_a, &acc[0]);
         const double J[6] = {-2.0 * (ny * rz - nz * ry), -2.0 * (nz * rx - nx * rz), -2.0 * (nx * ry - ny * rx), nx, ny, nz};
-        pi_add_row(acc, J, w);
+        pose_add_row(acc, J, w);
         acc[23] += 1.0;
       }
     }
   }
-  // lanes -> wavefront (cross-lane), wavefronts -> workgroup (LDS, wavefront order), workgroup -> HBM
-#pragma unroll
-  for (int i = 0; i < kPiAcc; i++) {
-    double v = acc[i];
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) v += __shfl_xor(v, d);
-    acc[i] = v;
-  }
-  if ((tid & 63) == 0) {
-#pragma unroll
-    for (int i = 0; i < kPiAcc; i++) s_w[tid >> 6][i] = acc[i];
-  }
-  __syncthreads();
-  if (tid < kPiAcc) {
-    double v = s_w[0][tid];
-    for (int w = 1; w < kPiThreads / 64; w++) v += s_w[w][tid];
-    sc->part[wg][tid] = v;
-  }
-  // the ticket: every workgroup publishes its partial (device-scope fence), then draws; the last one finishes the row
-  __threadfence();
-  __syncthreads();
-  if (tid == 0) s_last = atomicAdd(&sc->ticket, 1) == G - 1 ? 1 : 0;
-  __syncthreads();
-  if (!s_last) return;
-  __threadfence();
-  if (tid < kPiAcc) {
-    double v = 0.0;
-    for (int w = 0; w < G; w++) v += __hip_atomic_load(&sc->part[w][tid], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // workgroup order
-    s_tot[tid] = v;
-  }
-  if (tid == 0) sc->ticket = 0;   // for the stage's next launch (same stream, behind this one)
-  if (tid < kPiHalf) s_half[tid] = 0.0;
-  __syncthreads();
+  if (tid < kPiHalf) s_half[tid] = 0.0;   // (the barriers of the reduction stand between this and the next store)
+  if (!pose_rows_reduce<kPiThreads>(acc, sc, s_tot)) return;   // the workgroup with the last ticket finishes the row
   if (on) {
     if (tid < 7) s_half[tid] = rec->x_out[tid];
     if (tid == 7) s_half[7] = s_tot[0];
-    if (tid < 36) {   // mirror the upper triangle: element (r, c) sits at 1 + r (13 - r) / 2 + (c - r) of the sums
-      const int r = tid / 6, c = tid % 6, lo = r < c ? r : c, hi = r < c ? c : r;
-      const double v = s_tot[1 + lo * (13 - lo) / 2 + (hi - lo)];
+    if (tid < 36) {   // mirror the upper triangle
+      const double v = pose_rows_H(s_tot, tid);
       s_half[8 + tid] = v;
       s_a[tid] = v;
     }
@@ -257,20 +189,9 @@ __global__ __launch_bounds__(kPiThreads) void k_pose_info_map(POSE_INFO_ARGS) {
 }
 #undef POSE_INFO_ARGS
 
-__global__ __launch_bounds__(64) void k_pose_info_init(vloam_pose_info_record* rows, long long n_rows) {
-  for (long long r = (long long)blockIdx.x * 64 + threadIdx.x; r < n_rows; r += (long long)gridDim.x * 64) {
-    int* w = reinterpret_cast<int*>(rows + r);
-    for (int k = 0; k < (int)(sizeof(vloam_pose_info_record) / sizeof(int)); k++) w[k] = 0;
-    rows[r].frame = -1;
-  }
-}
-
+size_t pose_info_scratch_bytes(int n_sessions) { return sizeof(PoseInfoScratch) * 2 * (size_t)n_sessions; }
 hipError_t pose_info_init(hipStream_t st, const PoseInfo& P, int n_sessions) {
-  const long long n = (long long)P.max_frames * n_sessions;
-  hipLaunchKernelGGL(k_pose_info_init, vl_hw_grid(dim3((unsigned)std::min<long long>((n + 63) / 64, 1024), 1, 1)), dim3(64), 0, st, P.rows, n);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return e;
-  return hipMemsetAsync(P.scratch, 0, sizeof(PoseInfoScratch) * 2 * (size_t)n_sessions, st);
+  return pose_rows_init(st, P.rows, (long long)P.max_frames * n_sessions, P.scratch, pose_info_scratch_bytes(n_sessions));
 }
 
 void pose_info_launch(hipStream_t st, Sess se, const PoseInfo& P, int stage, int frame, const FactorTable& F, const LMRecord* rec, bool ran,
