@@ -616,7 +616,8 @@ vloam_status vloam_get_health(vloam_handle* h, long long out8[8]);
  * (VLOAM_ERR_ORDER); a handle whose vloam_sync reports a sticky error (size / save return that error).
  * What does not travel: the publication buffers (after load it is "before the first publication": *n = 0, *frame = -1; the map_pub_number
  * schedule continues from the restored mapped-sweep count); the health counters (out8[0..3] start at 0); vloam_get_features(0 .. 4, 11) of the
- * last sweep; sweep-log rows 0 .. frames - 1 travel when both handles keep a log, otherwise the rows of restored sweeps read frame == -1. */
+ * last sweep; sweep-log rows 0 .. frames - 1 travel when both handles keep a log, otherwise the rows of restored sweeps read frame == -1;
+ * the place database (vloam_place_enable: a restored handle is not enabled and holds no rows — carry them with vloam_place_get / _load). */
 vloam_status vloam_checkpoint_size(vloam_handle* h, long long* bytes);
 vloam_status vloam_checkpoint_save(vloam_handle* h, void* buf, long long cap, long long* bytes);
 vloam_status vloam_checkpoint_load(vloam_handle* h, const void* buf, long long bytes);
@@ -741,7 +742,7 @@ vloam_status vloam_map_localize_device(vloam_handle* h, const vloam_localize_opt
  *   ranking of fine[].  Synchronous, host clouds only; every refusal of vloam_map_localize and of vloam_map_score_poses applies (a handle of
  *   the large stack tier can score but not relocalise).  Nothing the sequence can see changes, as with vloam_map_localize.
  * Not offered: batched handles, scores in the odometry frame, roll and pitch in the grid, scores weighted by fit quality, a search with no
- *   centre, starting a live sequence from the result in one call (vloam_map_import with the refined pose does that on a fresh handle). */
+ *   centre (vloam_place_query below supplies one), starting a live sequence from the result in one call (vloam_map_import with the refined pose does that on a fresh handle). */
 typedef struct vloam_score_options {
   int struct_size;     /* sizeof as compiled */
   int stride[2];       /* [corner, surf] every stride-th point is scored, >= 1 */
@@ -777,6 +778,83 @@ typedef struct vloam_relocalize_result {   /* 2288 bytes */
 void vloam_default_relocalize_options(vloam_relocalize_options* o);   /* 9 x 9 x 1 x 9 steps over +-2 m, +-10 degrees; top_k 4; default score options */
 vloam_status vloam_map_relocalize(vloam_handle* h, const vloam_relocalize_options* o, const float* corner_xyzi4, int n_corner, const float* surf_xyzi4,
                                   int n_surf, const double q_center[4], const double t_center[3], vloam_relocalize_result* out);
+
+/* Place recognition: a rotation-tolerant descriptor of one sweep, a database of such descriptors kept on the device, and a match of one
+ * descriptor against every row at every yaw shift in one launch — the centre vloam_map_relocalize asks for when the caller has none, and
+ * loop detection's "have I been here before, and at which sweep?".  Opt-in: a handle that never calls vloam_place_enable allocates and
+ * launches nothing of this, and no kernel of a sweep changes; nothing here reads or writes what a sequence owns (works with
+ * with_mapping == 0 as well).  Everything is enqueued on the handle's scan-registration stream; no stream is created.
+ *   Descriptor (geometry: vloam_place_options).  Input: a sweep as vloam_process_scan_device takes it — packed float4 in the SENSOR frame, w
+ *   ignored, n <= 16777216.  A point is used when x, y, z are finite and min_range^2 <= r2 < max_range^2, r2 = x*x + y*y in f32 with every
+ *   operation rounded on its own, the two squares f32 products.  Ring: the number of i in 1 .. R-1 with r2 >= edge2[i], edge2[i] the f32
+ *   square of (float)((float)i * w), w = max_range / (float)R (a host table: no square root on the device).  Sector:
+ *   min(S-1, (int)floorf((atan2f(y, x) + PI_F) * k)), atan2f glibc's, PI_F = 0x40490fdb, k = (float)S / (2 * PI_F) in f32.  Height:
+ *   q = min(254, max(0, (int)floorf((z - z_min) / z_step))) + 1, an f32 divide: 1 .. 255, 0 an empty cell.  A cell holds the largest q of
+ *   its points (integer maxima: order-free).  Packed: sector-major bytes desc[sector][ring], the rings of a sector padded with zero bytes
+ *   to W = ceil(R/4) little-endian words, S*W words per descriptor.  info2: n_used (points that passed the filters; -1 for a row that came
+ *   through vloam_place_load) and n_occupied (non-zero cells).
+ *   Distance: dist(Q, D, s) = sum over sector j and ring i of |Q[(j + s) mod S][i] - D[j][i]|; best(Q, D) the smallest over s = 0 .. S-1,
+ *   ties to the smallest s.  Rows rank by dist ascending, then row index ascending; rows with index >= count - exclude_last are skipped.
+ *   All integers: records are bit for bit a function of the inputs, from run to run.
+ *   Yaw convention: when the query's content is the row's content turned by +m sectors in the sensor frame (a point at azimuth a in the
+ *   row's sweep lies at a + m*2pi/S in the query's), the match has shift == m, and the query sensor's heading is the row's turned by
+ *   -shift*2pi/S about z: q_query ~= q_row * Rz(-shift*2pi/S), Rz(a) = (0, 0, sin(a/2), cos(a/2)).
+ * vloam_place_enable: once per handle (a second call: VLOAM_ERR_ORDER); allocates capacity rows (S*W*4 + 20 bytes each) and the scratch,
+ *   freed by vloam_destroy.  vloam_place_describe: the descriptor of a cloud, the database untouched (info2 may be null).
+ *   vloam_place_add: describe and append; tag is the caller's (e.g. the sweep's frame index); *row_out (may be null) the row's index, known
+ *   when the call returns; a full database: VLOAM_ERR_CAPACITY, unchanged.  vloam_place_get: rows first .. first + count - 1 copied out
+ *   (tags, info2 may be null).  vloam_place_load: appends rows made elsewhere — how a database travels; pad bytes must be zero
+ *   (VLOAM_ERR_INVALID), more rows than fit: VLOAM_ERR_CAPACITY, unchanged.  vloam_place_query*: the k best rows as vloam_place_match
+ *   records, unused places row == -1 and the rest zero; an empty or fully excluded database: VLOAM_OK, every row == -1.
+ *   Host forms wait for that one stream only.  Device forms (_device: the cloud, and for describe / query the outputs, are device
+ *   addresses) enqueue and return; results are complete after vloam_sync and the buffers must stay valid until then.
+ * The database is NOT part of a checkpoint (vloam_checkpoint_save): carry it with vloam_place_get / vloam_place_load.
+ * Refusals, options first and before the handle is looked at (VLOAM_ERR_INVALID, each with its own vloam_last_error()): null options or
+ *   struct_size, reserved != 0, n_ring outside 1 .. 32, n_sector outside 1 .. 120, capacity outside 1 .. 1048576, a max_range or z_step
+ *   that is not finite and positive, a z_min that is not finite, a min_range that is negative or not finite, min_range >= max_range; k
+ *   outside 1 .. 8, exclude_last < 0; a negative count, n > 16777216, a null buffer with a positive count, a null result.  Then the
+ *   handle: null (VLOAM_ERR_INVALID); n_sessions > 1 (VLOAM_ERR_INVALID, "not offered"); any call but vloam_place_enable on a handle that
+ *   was not enabled (VLOAM_ERR_ORDER).
+ * Not offered: batched handles; automatic appends from inside the sweep pipeline; cosine or learned distances; roll or pitch tolerance; a
+ *   pose graph or any correction of the trajectory. */
+typedef struct vloam_place_options {   /* 36 bytes */
+  int struct_size;     /* sizeof as compiled */
+  int n_ring;          /* R, 1 .. 32; default 20 */
+  int n_sector;        /* S, 1 .. 120; default 60 */
+  int capacity;        /* database rows, 1 .. 1048576; default 16384 */
+  float min_range;     /* metres; 0: the handle's minimum_range */
+  float max_range;     /* metres; default 80 */
+  float z_min;         /* metres; default -3 */
+  float z_step;        /* metres; default 0.05 */
+  int reserved;        /* 0 */
+} vloam_place_options;
+typedef struct vloam_place_query_options {
+  int struct_size;     /* sizeof as compiled */
+  int k;               /* 1 .. 8 matches */
+  int exclude_last;    /* >= 0: the youngest rows are skipped */
+  int reserved;        /* 0 */
+} vloam_place_query_options;
+typedef struct vloam_place_match {   /* 32 bytes */
+  int row, tag, shift, dist;
+  int n_occupied_query, n_occupied_row;
+  int pad[2];
+} vloam_place_match;
+void vloam_default_place_options(vloam_place_options* o);               /* 20 rings, 60 sectors, 16384 rows, 0 / 80 m, -3 m, 0.05 m */
+void vloam_default_place_query_options(vloam_place_query_options* o);   /* k 1, exclude_last 0 */
+vloam_status vloam_place_enable(vloam_handle* h, const vloam_place_options* o);
+vloam_status vloam_place_describe(vloam_handle* h, const float* xyzi4, int n, unsigned int* desc_words, int* info2);
+vloam_status vloam_place_describe_device(vloam_handle* h, const void* d_xyzi4, int n, void* d_desc_words, void* d_info2);
+vloam_status vloam_place_add(vloam_handle* h, const float* xyzi4, int n, int tag, int* row_out);
+vloam_status vloam_place_add_device(vloam_handle* h, const void* d_xyzi4, int n, int tag, int* row_out);
+vloam_status vloam_place_count(vloam_handle* h, int* count);
+vloam_status vloam_place_get(vloam_handle* h, int first, int count, unsigned int* desc_words, int* tags, int* info2);
+vloam_status vloam_place_load(vloam_handle* h, const unsigned int* desc_words, const int* tags, int count);
+vloam_status vloam_place_query(vloam_handle* h, const vloam_place_query_options* o, const float* xyzi4, int n, vloam_place_match* matches);
+vloam_status vloam_place_query_device(vloam_handle* h, const vloam_place_query_options* o, const void* d_xyzi4, int n, void* d_matches);
+vloam_status vloam_place_query_descriptor(vloam_handle* h, const vloam_place_query_options* o, const unsigned int* desc_words, vloam_place_match* matches);
+/* Measurement hook (tools/place_probe.py): the match of vloam_place_query_descriptor launched `repeats` (1 .. 1024) times back to back, each
+ * bracketed by HIP events on the stream; ms[r] the device milliseconds of repeat r (match + top-k launches, no copies).  Synchronous. */
+vloam_status vloam_place_time_query(vloam_handle* h, const vloam_place_query_options* o, const unsigned int* desc_words, int repeats, float* ms);
 
 /* Map import: a FRESH handle is given two point clouds in the map frame — the corner map and the surf map, packed (x, y, z, intensity), e.g. what
  * vloam_get_map_kind(h, 0 / 1) of any build of the library returned — and the map<-odometry transform the sequence starts with.  Afterwards it

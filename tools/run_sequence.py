@@ -112,6 +112,25 @@ def parse_relocalize(arg):
     return dict(n_xy=(n_xy, n_xy), n_z=1, n_yaw=n_yaw, half_extent=(ext, ext, 0.0), half_yaw=float(np.deg2rad(yaw)), top_k=int(v[4]) if len(v) == 5 else 4)
 
 
+def place_centre(vl, hd, a, cloud):
+    """--relocalize-global: DIR/place_db.npz loaded into the handle's place database, `cloud` matched against every row at every yaw shift; the
+    centre is the best row's saved pose with its heading turned by the match's shift (c_api.h: q_query = q_row * Rz(-shift * 2 pi / S))."""
+    path = os.path.join(a.load_map, "place_db.npz")
+    if not os.path.exists(path):
+        sys.exit("--relocalize-global needs %s: save the map with --place-db --save-map DIR" % path)
+    db = np.load(path)
+    geom = {k: db[k].item() for k in ("n_ring", "n_sector", "min_range", "max_range", "z_min", "z_step")}
+    hd.place_enable(capacity=max(int(db["desc"].shape[0]), 1), **geom)
+    hd.place_load(db["desc"], db["tags"])
+    m = hd.place_query(cloud, k=1)[0]
+    if m["row"] < 0:
+        sys.exit("--relocalize-global: %s holds no rows" % path)
+    print("place match: row %d, tag %d, shift %d, dist %d" % (m["row"], m["tag"], m["shift"], m["dist"]))
+    pose = db["poses"][int(m["row"])]
+    q = vl.place_yaw_pose(pose[:4], int(m["shift"]), int(geom["n_sector"]))
+    return q / np.linalg.norm(q), pose[4:7].copy()
+
+
 def score_json(s):
     return {"n_hit": s["n_hit"].tolist(), "n_used": s["n_used"].tolist(), "sum_d2_q24": [int(x) for x in s["sum_d2_q24"]]}
 
@@ -214,6 +233,14 @@ def main():
                     help="with --load-map / --resume and --localize-only: the first sweep is relocalised around the start pose instead of localised from it "
                          "(vloam_map_relocalize: candidates every STEP_XY metres within +-EXT_XY in x and y and every STEP_DEG degrees within +-YAW_DEG of yaw, "
                          "the TOP_K best — default 4 — refined); the first --metrics line carries the winning candidate, its scores and the refined pose")
+    ap.add_argument("--place-db", action="store_true",
+                    help="keep a place database (vloam_place_enable, default geometry): every sweep's raw cloud is added, tagged with its frame index; with "
+                         "--save-map DIR it is written as DIR/place_db.npz (desc, tags, the geometry, and per row the mapping pose of that frame, poses [n, 7])")
+    ap.add_argument("--relocalize-global", metavar="\"EXT_XY STEP_XY YAW_DEG STEP_DEG [TOP_K]\"",
+                    help="with --load-map DIR --localize-only: no start pose is needed — the first sweep is matched against DIR/place_db.npz "
+                         "(vloam_place_query), the best row's pose turned by the match's yaw shift becomes the start pose, and the sweep is relocalised "
+                         "around it exactly as --relocalize does; one more line of output names the row, its tag, the shift and the distance")
+    ap.add_argument("--first-sweep", type=int, default=0, metavar="K", help="the input starts at its sweep K (the sweeps in front of it are left out)")
     ap.add_argument("--imu-T-velo", help="16 numbers, row major (default: KITTI 2011_09_26 extrinsics, approx.)")
     ap.add_argument("--imu-T-cam0", help="16 numbers, row major")
     a = ap.parse_args()
@@ -231,6 +258,10 @@ def main():
         seq = synth.SynthSequence(n_rings=64, n_azimuth=a.azimuth, n_sweeps=max(a.synthetic, 2) + 1, sensor=a.sensor)
         load_sweep = seq.sweep
         n = a.synthetic
+    if a.first_sweep:
+        if not 0 <= a.first_sweep < n:
+            sys.exit("--first-sweep K: 0 <= K < %d" % n)
+        load_all, load_sweep, n = load_sweep, (lambda k: load_all(k + a.first_sweep)), n - a.first_sweep
     if n == 0:
         sys.exit("no sweeps")
 
@@ -254,6 +285,10 @@ def main():
     if a.relocalize and not a.localize_only:
         sys.exit("--relocalize goes with --localize-only: an import fixes the start transform before any sweep arrives, so a SEQUENCE cannot start from a "
                  "relocalised pose in one run; relocalise with --localize-only, then start the sequence with --load-map DIR --start-pose and the pose it printed")
+    if a.relocalize_global:
+        if not (a.load_map and a.localize_only) or a.relocalize or a.start_pose:
+            sys.exit("--relocalize-global goes with --load-map DIR --localize-only, and replaces --start-pose and --relocalize")
+        a.relocalize = a.relocalize_global   # from the matched centre on it is --relocalize
     if a.relocalize:
         parse_relocalize(a.relocalize)
     if a.resume and a.load_map:
@@ -280,6 +315,8 @@ def main():
         hd.enable_pose_info(a.lo_min_eig, a.map_min_eig)
     if a.pose_cov:
         hd.pose_cov_enable()
+    if a.place_db:
+        hd.place_enable(capacity=max(n, 1))
     if a.vloam:
         if real_images:   # PointCloudUtil::loadTransformations (point_cloud_util.cpp:5-116)
             hd.vo_set_calib(*kio.load_transformations(a.calib_cam_to_cam, a.calib_velo_to_cam))
@@ -306,7 +343,7 @@ def main():
         tf.LO2Cam0StartFrame(row0[0:4], row0[4:7], 0)
         tf.MO2Cam0StartFrame(row0[7:11], row0[11:14], 0)
     if a.load_map:
-        q0, t0 = read_start_pose(a)
+        q0, t0 = place_centre(vl, hd, a, load_sweep(0)) if a.relocalize_global else read_start_pose(a)
         res = hd.map_import(np.load(os.path.join(a.load_map, "corner.npy")), np.load(os.path.join(a.load_map, "surf.npy")), q0, t0)
         print("imported %d corner / %d surf map points from %s (%d / %d outside the window)" % (res["n_voxels"][0], res["n_voxels"][1], a.load_map,
                                                                                               res["n_outside_window"][0], res["n_outside_window"][1]))
@@ -335,6 +372,8 @@ def main():
             lo, lm = loam.laser_odometry, loam.laser_mapping
             tf.LO2CamPrior(lo.q_last_curr, lo.t_last_curr)
             q_lo, t_lo, q_mo, t_mo = lo.q_w_curr, lo.t_w_curr, lm.q_w_curr, lm.t_w_curr
+        if a.place_db:
+            hd.place_add(cloud, count + a.first_sweep)
         lo_rows.append(tf.LO2Cam0StartFrame(q_lo, t_lo, count))
         mo_rows.append(tf.MO2Cam0StartFrame(q_mo, t_mo, count))
         pub_points, pub_overflow = None, False
@@ -413,6 +452,13 @@ def main():
         with open(os.path.join(a.save_map, "start_pose.txt"), "w") as f:
             f.write(" ".join("%.17g" % v for v in row[7:14]) + "\n")
         print("wrote %d corner / %d surf map points to %s" % (halves[0].shape[0], halves[1].shape[0], a.save_map))
+        if a.place_db:
+            desc, tags, _ = hd.place_get()
+            o = hd.place_options
+            poses = np.stack([hd.trajectory(int(t) - a.first_sweep, 1)[0][7:14] for t in tags]) if tags.shape[0] else np.zeros((0, 7))
+            np.savez(os.path.join(a.save_map, "place_db.npz"), desc=desc, tags=tags, poses=poses, n_ring=o.n_ring, n_sector=o.n_sector,
+                     min_range=float(np.float32(hd.cfg.minimum_range)) if o.min_range == 0 else o.min_range, max_range=o.max_range, z_min=o.z_min, z_step=o.z_step)
+            print("wrote %d place rows to %s/place_db.npz" % (desc.shape[0], a.save_map))
 
 
 if __name__ == "__main__":

@@ -106,6 +106,32 @@ def score_rank(scores):
     return np.lexsort((np.arange(s.shape[0]), s["sum_d2_q24"].sum(axis=1, dtype=np.uint64), -s["n_hit"].sum(axis=1, dtype=np.int64)))
 
 
+class PlaceOptions(C.Structure):
+    """vloam_place_options (c_api.h; vloam_place_enable)."""
+    _fields_ = [("struct_size", C.c_int), ("n_ring", C.c_int), ("n_sector", C.c_int), ("capacity", C.c_int), ("min_range", C.c_float),
+                ("max_range", C.c_float), ("z_min", C.c_float), ("z_step", C.c_float), ("reserved", C.c_int)]
+
+
+class PlaceQueryOptions(C.Structure):
+    """vloam_place_query_options (c_api.h; vloam_place_query*)."""
+    _fields_ = [("struct_size", C.c_int), ("k", C.c_int), ("exclude_last", C.c_int), ("reserved", C.c_int)]
+
+
+# vloam_place_match (c_api.h): 8 ints, 32 bytes
+PLACE_MATCH_DTYPE = np.dtype([("row", "<i4"), ("tag", "<i4"), ("shift", "<i4"), ("dist", "<i4"), ("n_occupied_query", "<i4"), ("n_occupied_row", "<i4"),
+                              ("pad", "<i4", (2,))])
+assert C.sizeof(PlaceOptions) == 36 and C.sizeof(PlaceQueryOptions) == 16 and PLACE_MATCH_DTYPE.itemsize == 32
+PLACE_MAX_K = 8
+
+
+def place_yaw_pose(q_row, shift, n_sector):
+    """The yaw convention of c_api.h: the query sensor's orientation q_row * Rz(-shift * 2 pi / n_sector) (xyzw) for a match with that shift."""
+    a = -float(shift) * 2.0 * np.pi / float(n_sector)
+    x, y, z, w = (float(v) for v in q_row)
+    sz, cw = np.sin(a / 2.0), np.cos(a / 2.0)
+    return np.array([x * cw + y * sz, y * cw - x * sz, z * cw + w * sz, w * cw - z * sz])
+
+
 class MapImportOptions(C.Structure):
     """vloam_map_import_options (c_api.h; vloam_map_import / vloam_map_import_device)."""
     _fields_ = [("struct_size", C.c_int), ("reserved", C.c_int * 3), ("q_wmap_wodom", C.c_double * 4), ("t_wmap_wodom", C.c_double * 3)]
@@ -893,6 +919,130 @@ class Handle:
                    for j in range(k)]
         return dict(n_candidates=int(r["n_candidates"]), n_refined=k, best=int(r["best"]), candidate=r["candidate"][:k].copy(), coarse=r["coarse"][:k].copy(),
                     refined=refined, fine=r["fine"][:k].copy())
+
+    # ---- place recognition (vloam_place_*): sweep descriptors, a database of them on the device, one descriptor against every row and yaw shift
+    def place_enable(self, n_ring=None, n_sector=None, capacity=None, min_range=None, max_range=None, z_min=None, z_step=None):
+        """vloam_place_enable, once per handle: the descriptor's geometry (None: the defaults of vloam_default_place_options — 20 rings, 60
+        sectors, 16384 rows, min_range 0 = the handle's minimum_range, 80 m, -3 m, 0.05 m).  Returns the options as used."""
+        opt = PlaceOptions()
+        self.L.vloam_default_place_options(C.byref(opt))
+        for k, v in dict(n_ring=n_ring, n_sector=n_sector, capacity=capacity).items():
+            if v is not None:
+                setattr(opt, k, int(v))
+        for k, v in dict(min_range=min_range, max_range=max_range, z_min=z_min, z_step=z_step).items():
+            if v is not None:
+                setattr(opt, k, float(v))
+        self._chk(self.L.vloam_place_enable(self.h, C.byref(opt)))
+        self.place_options = opt
+        self.place_words = opt.n_sector * ((opt.n_ring + 3) // 4)
+        return opt
+
+    def _place_words(self):
+        if not getattr(self, "place_words", 0):
+            raise VloamError(ERR_ORDER, "vloam_place_enable has not been called on this handle")
+        return self.place_words
+
+    @staticmethod
+    def _place_cloud(cloud):
+        a = np.ascontiguousarray(cloud, dtype=np.float32).reshape(-1, 4)
+        return a, (_fp(a) if a.shape[0] else None), int(a.shape[0])
+
+    @staticmethod
+    def _place_dev(cloud):
+        n = int(cloud.shape[0])
+        assert cloud.is_cuda and cloud.is_contiguous() and cloud.dtype.is_floating_point and cloud.element_size() == 4 and cloud.shape[-1] == 4
+        return (C.c_void_p(cloud.data_ptr()) if n else None), n
+
+    def _place_query_options(self, k, exclude_last):
+        opt = PlaceQueryOptions()
+        self.L.vloam_default_place_query_options(C.byref(opt))
+        opt.k, opt.exclude_last = int(k), int(exclude_last)
+        return opt
+
+    def place_describe(self, cloud):
+        """vloam_place_describe: (descriptor uint32 [S * W], (n_used, n_occupied)) of a cloud (float32 [n, 4], sensor frame); the database is untouched."""
+        a, ptr, n = self._place_cloud(cloud)
+        desc, info = np.zeros(self._place_words(), np.uint32), np.zeros(2, np.int32)
+        self._chk(self.L.vloam_place_describe(self.h, ptr, n, _fp(desc), _fp(info)))
+        return desc, (int(info[0]), int(info[1]))
+
+    def place_describe_device(self, cloud, desc, info=None):
+        """vloam_place_describe_device: torch tensors on the device — cloud float32 [n, 4], desc int32 [S * W], info int32 [2] or None.  Enqueues
+        and returns: complete after sync()."""
+        ptr, n = self._place_dev(cloud)
+        assert desc.is_cuda and desc.is_contiguous() and desc.numel() * desc.element_size() >= 4 * self._place_words()
+        assert info is None or (info.is_cuda and info.is_contiguous() and info.numel() * info.element_size() >= 8)
+        self._chk(self.L.vloam_place_describe_device(self.h, ptr, n, C.c_void_p(desc.data_ptr()), None if info is None else C.c_void_p(info.data_ptr())))
+
+    def place_add(self, cloud, tag):
+        """vloam_place_add: describe and append with the caller's tag; returns the row's index.  A full database: VloamError(ERR_CAPACITY)."""
+        a, ptr, n = self._place_cloud(cloud)
+        row = C.c_int(-1)
+        self._chk(self.L.vloam_place_add(self.h, ptr, n, int(tag), C.byref(row)))
+        return row.value
+
+    def place_add_device(self, cloud, tag):
+        """vloam_place_add_device: the same with a torch tensor on the device; enqueues and returns the row's index."""
+        ptr, n = self._place_dev(cloud)
+        row = C.c_int(-1)
+        self._chk(self.L.vloam_place_add_device(self.h, ptr, n, int(tag), C.byref(row)))
+        return row.value
+
+    def place_count(self):
+        n = C.c_int(0)
+        self._chk(self.L.vloam_place_count(self.h, C.byref(n)))
+        return n.value
+
+    def place_get(self, first=0, count=None):
+        """vloam_place_get: rows first .. first + count - 1 (None: to the end) as (desc uint32 [count, S * W], tags int32 [count], info int32
+        [count, 2]: n_used — -1 for loaded rows — and n_occupied)."""
+        words = self._place_words()
+        if count is None:
+            count = self.place_count() - int(first)
+        desc, tags, info = np.zeros((max(count, 1), words), np.uint32), np.zeros(max(count, 1), np.int32), np.zeros((max(count, 1), 2), np.int32)
+        self._chk(self.L.vloam_place_get(self.h, int(first), int(count), _fp(desc), _fp(tags), _fp(info)))
+        return desc[:max(count, 0)], tags[:max(count, 0)], info[:max(count, 0)]
+
+    def place_load(self, desc, tags):
+        """vloam_place_load: append rows made elsewhere (desc uint32 [count, S * W], pad bytes zero; tags int32 [count])."""
+        d = np.ascontiguousarray(desc, dtype=np.uint32).reshape(-1, self._place_words())
+        t = np.ascontiguousarray(tags, dtype=np.int32).reshape(-1)
+        assert t.shape[0] == d.shape[0]
+        self._chk(self.L.vloam_place_load(self.h, _fp(d) if d.shape[0] else None, _fp(t) if d.shape[0] else None, int(d.shape[0])))
+
+    def place_query(self, cloud, k=1, exclude_last=0):
+        """vloam_place_query: the k best rows for a cloud as PLACE_MATCH_DTYPE [k] (unused places row == -1): smallest distance over every yaw
+        shift, ties to the smaller shift, then the smaller row; the youngest exclude_last rows are skipped."""
+        opt = self._place_query_options(k, exclude_last)
+        a, ptr, n = self._place_cloud(cloud)
+        out = np.zeros(PLACE_MAX_K, dtype=PLACE_MATCH_DTYPE)
+        self._chk(self.L.vloam_place_query(self.h, C.byref(opt), ptr, n, _fp(out)))
+        return out[:int(k)]
+
+    def place_query_device(self, cloud, out, k=1, exclude_last=0):
+        """vloam_place_query_device: cloud float32 [n, 4] and out (k * 32 bytes) torch tensors on the device; complete after sync()."""
+        opt = self._place_query_options(k, exclude_last)
+        ptr, n = self._place_dev(cloud)
+        assert out.is_cuda and out.is_contiguous() and out.numel() * out.element_size() >= int(k) * PLACE_MATCH_DTYPE.itemsize
+        self._chk(self.L.vloam_place_query_device(self.h, C.byref(opt), ptr, n, C.c_void_p(out.data_ptr())))
+
+    def place_query_descriptor(self, desc, k=1, exclude_last=0):
+        """vloam_place_query_descriptor: the same for a packed descriptor (uint32 [S * W], pad bytes zero)."""
+        opt = self._place_query_options(k, exclude_last)
+        d = np.ascontiguousarray(desc, dtype=np.uint32).reshape(-1)
+        assert d.shape[0] == self._place_words()
+        out = np.zeros(PLACE_MAX_K, dtype=PLACE_MATCH_DTYPE)
+        self._chk(self.L.vloam_place_query_descriptor(self.h, C.byref(opt), _fp(d), _fp(out)))
+        return out[:int(k)]
+
+    def place_time_query(self, desc, repeats, k=1, exclude_last=0):
+        """vloam_place_time_query: HIP-event milliseconds of `repeats` back-to-back matches of a packed descriptor (float32 [repeats])."""
+        opt = self._place_query_options(k, exclude_last)
+        d = np.ascontiguousarray(desc, dtype=np.uint32).reshape(-1)
+        assert d.shape[0] == self._place_words()
+        ms = np.zeros(int(repeats), np.float32)
+        self._chk(self.L.vloam_place_time_query(self.h, C.byref(opt), _fp(d), int(repeats), _fp(ms)))
+        return ms
 
     def _import_options(self, q_wmap_wodom, t_wmap_wodom):
         opt = MapImportOptions()

@@ -472,6 +472,8 @@ vloam_status vloam_destroy(vloam_handle* h) {
   h->pi_ring.destroy();
   if (h->pc.rows) (void)hipFree(h->pc.rows);
   if (h->pc.scratch) (void)hipFree(h->pc.scratch);
+  for (void* p : {(void*)h->place.db, (void*)h->place.tags, (void*)h->place.info, (void*)h->place.best, (void*)h->place.cells, (void*)h->place.qdesc,
+                  (void*)h->place.qinfo, (void*)h->place.qmatch, (void*)h->place.cloud}) if (p) (void)hipFree(p);
   for (int k = 0; k < vloam_handle::kInRing; k++) if (h->ev_in_copied[k]) (void)hipEventDestroy(h->ev_in_copied[k]);
   for (int k = 0; k < 6; k++) if (h->ev[k]) (void)hipEventDestroy(h->ev[k]);
   for (int k = 0; k < vloam_handle::kSets; k++)

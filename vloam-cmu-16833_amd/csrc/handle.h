@@ -1,6 +1,6 @@
 // Host-only: the handle behind the C ABI and what the translation units of the host side share (c_api.cpp: creation and destruction;
 // capi_sweep.cpp: the sweep pipeline; capi_frame.cpp: coupled frames, images, VO; capi_results.cpp: getters and debug hooks; capi_rows.cpp: the
-// per-sweep row products; capi_ckpt.cpp: checkpoints; capi_query.cpp: map queries; capi_localize.cpp: localisation; capi_import.cpp: map import; capi_score.cpp: pose scores and relocalisation).  No .hip file includes this.  Helpers that cross files live in namespace vloam (mangled,
+// per-sweep row products; capi_ckpt.cpp: checkpoints; capi_query.cpp: map queries; capi_localize.cpp: localisation; capi_import.cpp: map import; capi_score.cpp: pose scores and relocalisation; capi_place.cpp: place recognition).  No .hip file includes this.  Helpers that cross files live in namespace vloam (mangled,
 // out of the C symbol list); a helper of one file is static there.
 #pragma once
 #include "../../include/vloam_hip/c_api.h"
@@ -24,6 +24,7 @@
 #include "lm_solve.h"
 #include "lo_kernels.h"
 #include "map_kernels.h"
+#include "place.h"
 #include "pose_cov.h"
 #include "pose_info.h"
 #include "sr_kernels.h"
@@ -199,6 +200,9 @@ struct vloam_handle {
   long long host_calls = 0;
   std::vector<hipEvent_t> prof_events;
   std::vector<int> prof_kids;
+  // place recognition (vloam_place_enable; null / unused on a handle without it): descriptors, the database and the match scratch, allocations of
+  // their own; all of its work goes to `stream`.  Last, so that no other member's place in the handle depends on it
+  PlaceContext place;
 };
 
 #define SINGLE_SESSION_ONLY(h) do { if ((h)->se.B != 1) { set_err("this entry point drives one sequence: the handle has %d sessions (use the vloam_batch_* calls)", (h)->se.B); return VLOAM_ERR_INVALID; } } while (0)
