@@ -6,23 +6,19 @@
 //   k_map_ckpt_pack    grid      table -> stream: a ballot prefix per wavefront on top of the workgroup's offset.  No atomics: the same-address
 //                                atomic per record is what k_map_pub_count / _scatter and k_map_grow cost.  Stream order = slot order.
 //   k_map_ckpt_begin   1 thread  the table's counters and the raw-voxel list start over
-//   k_map_ckpt_unpack  grid      stream -> table: map_reinsert (map_table.h), what k_map_grow does with a record of the old table
+//   k_map_ckpt_unpack  grid      stream -> table: what k_map_grow does with a record of the old table (the movers' one text: map_move_dev.h)
 #include <hip/hip_runtime.h>
 #include "map_kernels.h"
-#include "map_table.h"
+#include "map_move_dev.h"
 
 namespace vloam {
-
-constexpr int kCkptMaxGrid = 2048;   // k_map_grow's geometry: 256 CUs x 8 workgroups of 4 wavefronts
-
-__device__ __forceinline__ bool ckpt_live(const RecVal& v) { return v.key != 0ull && v.count != 0; }
 
 __global__ __launch_bounds__(256) void k_map_ckpt_count(VoxelTable T, int* __restrict__ cnt) {
   __shared__ int s_w[4];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const unsigned span = (T.mask + 1) / gridDim.x, begin = blockIdx.x * span;   // slots and grid are powers of two, span >= 256
   int c = 0;
-  for (unsigned s0 = begin; s0 < begin + span; s0 += 256) c += __popcll(__ballot(ckpt_live(rec_load(&T.rec[s0 + threadIdx.x]))));
+  for (unsigned s0 = begin; s0 < begin + span; s0 += 256) c += __popcll(__ballot(rec_live(rec_load(&T.rec[s0 + threadIdx.x]))));
   if (lane == 0) s_w[wave] = c;
   __syncthreads();
   if (threadIdx.x == 0) cnt[blockIdx.x] = s_w[0] + s_w[1] + s_w[2] + s_w[3];
@@ -34,8 +30,8 @@ __global__ __launch_bounds__(256) void k_map_ckpt_scan(const int* __restrict__ c
   long long base = 0;
   for (int k = 0; k < 2; k++) {
     const int n = k ? n1 : n0;
-    const int* c = cnt + k * kCkptMaxGrid;
-    long long* o = off + k * kCkptMaxGrid;
+    const int* c = cnt + k * kMoveMaxGrid;
+    long long* o = off + k * kMoveMaxGrid;
     const int per = (n + 255) / 256, b0 = threadIdx.x * per;
     long long mine = 0;
     for (int i = b0; i < b0 + per && i < n; i++) mine += c[i];
@@ -57,43 +53,33 @@ __global__ __launch_bounds__(256) void k_map_ckpt_pack(VoxelTable T, const long 
   long long base = off[blockIdx.x];
   for (unsigned s0 = begin; s0 < begin + span; s0 += 256) {
     const RecVal v = rec_load(&T.rec[s0 + threadIdx.x]);
-    const bool live = ckpt_live(v);
+    const bool live = rec_live(v);
     const u64 m = __ballot(live);
     if (lane == 0) s_w[wave] = __popcll(m);
     __syncthreads();
     int before = 0, all = 0;
     for (int w = 0; w < 4; w++) { const int c = s_w[w]; if (w < wave) before += c; all += c; }
     const long long pos = base + before + __popcll(m & ((1ull << lane) - 1ull));
-    if (live && pos < cap) {   // (pos < cap whenever the table is what k_map_ckpt_count saw: nothing of the handle is in flight)
-      uint4* o = reinterpret_cast<uint4*>(&out[pos]);
-      o[0] = make_uint4((unsigned)v.key, (unsigned)(v.key >> 32), __float_as_uint(v.sum.x), __float_as_uint(v.sum.y));
-      o[1] = make_uint4(__float_as_uint(v.sum.z), __float_as_uint(v.sum.w), (unsigned)v.count, key_seq(v.key) ? (unsigned)v.pend_cnt : 0u);
-    }
+    if (live && pos < cap) rec_store_all(&out[pos], v);   // (pos < cap whenever the table is what k_map_ckpt_count saw: nothing of the handle is in flight)
     base += all;
     __syncthreads();
   }
 }
 
 __global__ void k_map_ckpt_begin(VoxelTable Tn, MapFrame* fr, int kind) {
-  if (threadIdx.x == 0) { fr->n_deferred[kind] = 0; fr->n_newraw[kind] = 0; Tn.stats[0] = 0; Tn.stats[1] = 0; Tn.stats[2] = 0; Tn.stats[3] = 0; }
+  if (threadIdx.x == 0) map_move_begin(Tn, fr, kind);
 }
 __global__ __launch_bounds__(256) void k_map_ckpt_unpack(const VoxelRec* __restrict__ in, long long n, VoxelTable Tn, MapFrame* fr, int kind,
                                                          int* __restrict__ deferred, int deferred_cap) {
-  const int lane = threadIdx.x & 63;
   for (long long i0 = (long long)blockIdx.x * 256 + (threadIdx.x & ~63u); i0 < n; i0 += (long long)gridDim.x * 256) {   // wavefront-uniform
-    const long long i = i0 + lane;
-    bool done = false;
-    if (i < n) {
-      const RecVal v = rec_load(&in[i]);
-      if (ckpt_live(v)) done = map_reinsert(Tn, v, fr, kind, deferred, deferred_cap);
-    }
-    const u64 lm = __ballot(done);
-    if (lane == 0 && lm != 0ull) atomicAdd(&Tn.stats[0], __popcll(lm));
+    const long long i = i0 + (threadIdx.x & 63);
+    RecVal v = {};
+    if (i < n) v = rec_load(&in[i]);
+    map_reinsert_wave(Tn, rec_live(v), v, fr, kind, deferred, deferred_cap);
   }
 }
 
 // ---------------------------------------------------------------------------------------------- host side
-static unsigned ckpt_grid(const VoxelTable& T) { const unsigned slots = T.mask + 1; return slots / 256 < (unsigned)kCkptMaxGrid ? slots / 256 : (unsigned)kCkptMaxGrid; }
 
 // Live records of both tables -> n_rec; with d_out != nullptr also the stream itself, in a device buffer of the caller's to hipFree
 // (corner records, then surf records).  Temporary allocations only; the handle is not changed.  ms: kernel times of count + scan / pack (may be null).
@@ -103,13 +89,13 @@ vloam_status map_ckpt_pack(MapContext* m, hipStream_t st, long long n_rec[2], Vo
   hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
   if (d_out) *d_out = nullptr;
   vloam_status rc = VLOAM_OK;
-  if (hipMalloc((void**)&d_cnt, sizeof(int) * 2 * kCkptMaxGrid) != hipSuccess || hipMalloc((void**)&d_off, sizeof(long long) * (2 * kCkptMaxGrid + 2)) != hipSuccess) rc = VLOAM_ERR_HIP;
+  if (hipMalloc((void**)&d_cnt, sizeof(int) * 2 * kMoveMaxGrid) != hipSuccess || hipMalloc((void**)&d_off, sizeof(long long) * (2 * kMoveMaxGrid + 2)) != hipSuccess) rc = VLOAM_ERR_HIP;
   if (rc == VLOAM_OK && ms) for (hipEvent_t& e : ev) if (hipEventCreate(&e) != hipSuccess) rc = VLOAM_ERR_HIP;
-  long long* d_total = d_off ? d_off + 2 * kCkptMaxGrid : nullptr;
+  long long* d_total = d_off ? d_off + 2 * kMoveMaxGrid : nullptr;
   if (rc == VLOAM_OK) {
     if (ms) (void)hipEventRecord(ev[0], st);
-    for (int k = 0; k < 2; k++) VL_RAW_LAUNCH(k_map_ckpt_count, dim3(ckpt_grid(m->tab[k])), dim3(256), 0, st, m->tab[k], d_cnt + k * kCkptMaxGrid);
-    VL_RAW_LAUNCH(k_map_ckpt_scan, dim3(1), dim3(256), 0, st, d_cnt, (int)ckpt_grid(m->tab[0]), (int)ckpt_grid(m->tab[1]), d_off, d_total);
+    for (int k = 0; k < 2; k++) VL_RAW_LAUNCH(k_map_ckpt_count, dim3(map_move_grid(m->tab[k])), dim3(256), 0, st, m->tab[k], d_cnt + k * kMoveMaxGrid);
+    VL_RAW_LAUNCH(k_map_ckpt_scan, dim3(1), dim3(256), 0, st, d_cnt, (int)map_move_grid(m->tab[0]), (int)map_move_grid(m->tab[1]), d_off, d_total);
     if (ms) (void)hipEventRecord(ev[1], st);
     if (hipGetLastError() != hipSuccess || hipStreamSynchronize(st) != hipSuccess ||
         hipMemcpy(n_rec, d_total, 2 * sizeof(long long), hipMemcpyDeviceToHost) != hipSuccess) rc = VLOAM_ERR_HIP;
@@ -118,7 +104,7 @@ vloam_status map_ckpt_pack(MapContext* m, hipStream_t st, long long n_rec[2], Vo
     const long long n = n_rec[0] + n_rec[1];
     if (hipMalloc((void**)d_out, (size_t)(n + 1) * sizeof(VoxelRec)) != hipSuccess) { *d_out = nullptr; rc = VLOAM_ERR_HIP; }
     if (rc == VLOAM_OK) {
-      for (int k = 0; k < 2; k++) VL_RAW_LAUNCH(k_map_ckpt_pack, dim3(ckpt_grid(m->tab[k])), dim3(256), 0, st, m->tab[k], d_off + k * kCkptMaxGrid, *d_out, n);
+      for (int k = 0; k < 2; k++) VL_RAW_LAUNCH(k_map_ckpt_pack, dim3(map_move_grid(m->tab[k])), dim3(256), 0, st, m->tab[k], d_off + k * kMoveMaxGrid, *d_out, n);
       if (ms) (void)hipEventRecord(ev[2], st);
       if (hipGetLastError() != hipSuccess || hipStreamSynchronize(st) != hipSuccess) rc = VLOAM_ERR_HIP;
     }
@@ -149,8 +135,7 @@ vloam_status map_ckpt_unpack(MapContext* m, hipStream_t st, const void* recs, co
     for (int k = 0; k < 2; k++) {
       VL_RAW_LAUNCH(k_map_ckpt_begin, dim3(1), dim3(64), 0, st, m->tab[k], m->frame, k);
       if (n_rec[k] == 0) continue;
-      const long long blocks = (n_rec[k] + 255) / 256;
-      VL_RAW_LAUNCH(k_map_ckpt_unpack, dim3((unsigned)(blocks < kCkptMaxGrid ? blocks : kCkptMaxGrid)), dim3(256), 0, st, d_in + (k ? n_rec[0] : 0), n_rec[k], m->tab[k],
+      VL_RAW_LAUNCH(k_map_ckpt_unpack, dim3(map_move_grid((size_t)n_rec[k])), dim3(256), 0, st, d_in + (k ? n_rec[0] : 0), n_rec[k], m->tab[k],
                     m->frame, k, m->deferred[k], k ? m->surf_cap : kStackCapCorner);
     }
     if (ms) (void)hipEventRecord(ev[1], st);

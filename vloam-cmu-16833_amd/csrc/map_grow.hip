@@ -2,51 +2,28 @@
 // per-sweep report the host's growth decision starts from, and that decision.  A translation unit (and code object) of its own: the kernels
 // every handle launches (map_kernels.hip, map_stack.hip, map_output.hip) are not touched by it.
 //   k_map_grow_begin  1 thread  the lists that hold slot ids and the table's counters start over
-//   k_map_grow        grid      every live record of the old table -> the new one
+//   k_map_grow        grid      every live record of the old table -> the new one (the movers' one text: map_move_dev.h)
 //   k_map_progress    1 WG      behind k_map_finalize of every mapped sweep: live keys, block keys, keys incl. tombstones -> host-mapped words
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include "map_kernels.h"
-#include "map_table.h"
+#include "map_move_dev.h"
 
 namespace vloam {
 
 // One step: k_map_grow_begin, memsets of the new rec / blk, k_map_grow — between two sweeps on the mapping stream, in front of k_map_prepare.
-// k_map_grow walks the OLD table in place (no staging list: the new table is another buffer) and, for every live record, does what
-// k_map_rebuild_insert does: claim a slot (same hash, same kMaxProbe, same CAS), store the value, publish the voxel's occupancy block, and
-// re-append raw voxels to the deferred list — slot ids change, exactly as in a rebuild.  Tombstones (count 0) are not carried over, so a step
-// into a table of the SAME size is the tombstone reclamation of such a handle.  pend[] of the new table is not written: between two sweeps
-// every seq-0 record has pend_cnt == 0 (k_map_finalize stored it), and a raw point's pend_cnt is its arrival stamp, copied with the value.
-// stats / deferred / the frame counters stay where they are (session arena); To.stats == Tn.stats.
+// k_map_grow walks the OLD table in place (no staging list: the new table is another buffer) and moves every live record into the new one
+// (map_move_dev.h) — slot ids change, exactly as in a rebuild.  Tombstones (count 0) are not carried over, so a step into a table of the SAME
+// size is the tombstone reclamation of such a handle.  stats / deferred / the frame counters stay where they are (session arena);
+// To.stats == Tn.stats.
 __global__ void k_map_grow_begin(VoxelTable Tn, MapFrame* fr, int kind) {
-  if (threadIdx.x == 0) { fr->n_deferred[kind] = 0; fr->n_newraw[kind] = 0; Tn.stats[0] = 0; Tn.stats[1] = 0; Tn.stats[2] = 0; Tn.stats[3] = 0; }
+  if (threadIdx.x == 0) map_move_begin(Tn, fr, kind);
 }
 __global__ __launch_bounds__(256) void k_map_grow(VoxelTable To, VoxelTable Tn, MapFrame* fr, int kind, int* __restrict__ deferred, int deferred_cap,
                                                   int* host_flags) {
-  const int lane = threadIdx.x & 63;
   for (unsigned s0 = blockIdx.x * 256 + (threadIdx.x & ~63u); s0 <= To.mask; s0 += gridDim.x * 256) {   // wavefront-uniform (slots are a multiple of 64)
-    const RecVal v = rec_load(&To.rec[s0 + lane]);
-    const bool live = v.key != 0ull && v.count != 0;
-    bool done = false;
-    if (live) {
-      const int seq = key_seq(v.key);
-      unsigned s = (unsigned)mix64(v.key) & Tn.mask;
-      for (int probe = 0; probe < kMaxProbe && !done; probe++, s = (s + 1) & Tn.mask) {
-        if (atomicCAS(&Tn.rec[s].key, 0ull, v.key) != 0ull) continue;   // keys are unique in the old table
-        rec_store_value(&Tn.rec[s], v.sum, v.count, seq ? v.pend_cnt : 0);
-        int Ai, Aj, Ak;
-        unpack_cube(v.key, &Ai, &Aj, &Ak);
-        if (seq == 0 && !map_publish_block(Tn, Ai, Aj, Ak, key_lx(v.key), key_ly(v.key), key_lz(v.key))) atomicOr(&fr->error, kErrMapFull);
-        if (seq == 0 && rec_raw(v.count)) {
-          const int dpos = atomicAdd(&fr->n_deferred[kind], 1);
-          if (dpos < deferred_cap) deferred[dpos] = (int)s;
-        }
-        done = true;
-      }
-      if (!done) atomicOr(&fr->error, kErrMapFull);
-    }
-    const u64 lm = __ballot(done);   // stats {keys in the new table, 0, block keys}: one add per wavefront (the block keys are counted by map_publish_block)
-    if (lane == 0 && lm != 0ull) atomicAdd(&Tn.stats[0], __popcll(lm));
+    const RecVal v = rec_load(&To.rec[s0 + (threadIdx.x & 63)]);
+    map_reinsert_wave(Tn, rec_live(v), v, fr, kind, deferred, deferred_cap);
   }
   if (blockIdx.x == 0 && threadIdx.x == 0 && host_flags) __hip_atomic_store(&host_flags[kind], 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
 }
@@ -134,9 +111,7 @@ static vloam_status map_grow_step(MapContext* m, hipStream_t st, int kind, int n
   VL_RAW_LAUNCH(k_map_grow_begin, dim3(1), dim3(64), 0, st, To, m->frame, kind);
   VoxelTable Tn = To;
   map_grow_adopt(Tn, new_lg, p);
-  // a memory-latency-bound scatter: every wave slot of the chip (256 CUs x 8 workgroups of 4 wavefronts), grid-stride beyond
-  const unsigned old_slots = To.mask + 1, grid = old_slots / 256 < 2048 ? old_slots / 256 : 2048;
-  VL_RAW_LAUNCH(k_map_grow, dim3(grid), dim3(256), 0, st, To, Tn, m->frame, kind, m->deferred[kind], kind ? m->surf_cap : kStackCapCorner, m->host_flags);
+  VL_RAW_LAUNCH(k_map_grow, dim3(map_move_grid(To)), dim3(256), 0, st, To, Tn, m->frame, kind, m->deferred[kind], kind ? m->surf_cap : kStackCapCorner, m->host_flags);
   const bool ok = hipGetLastError() == hipSuccess && hipEventRecord(old.ev, st) == hipSuccess;
   m->tab[kind] = Tn;   // (whatever was enqueued reads the new table from here on)
   G.retired.push_back(old);

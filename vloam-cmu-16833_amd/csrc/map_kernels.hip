@@ -29,6 +29,7 @@
 #include "map_kernels.h"
 #include "map_device.h"
 #include "map_table.h"
+#include "map_move_dev.h"
 #include "subwave.h"
 
 namespace vloam {
@@ -790,42 +791,25 @@ __global__ __launch_bounds__(256) void k_map_finalize_tier(VL_MAP_FINALIZE_PARAM
 // ---------------------------------------------------------------------------------------------- table rebuild (tombstone reclamation)
 // Purged entries keep their key so that probe chains stay intact; on a long drive they would fill the table.  When the host sees
 // the flag k_map_finalize raises, it enqueues — between two sweeps, on the mapping stream — gather (live records -> list), two
-// memsets, reinsert.  Voxel contents are untouched: only slot positions change (nothing keeps slot ids across sweeps except the
-// deferred list, which is rebuilt here).
+// memsets, reinsert (the movers' one text: map_move_dev.h).  Voxel contents are untouched: only slot positions change (nothing keeps slot
+// ids across sweeps except the deferred list, which is rebuilt here).
 __global__ __launch_bounds__(256) void k_map_rebuild_gather(VoxelTable T, VoxelRec* __restrict__ tmp, int cap, int* n_tmp, MapFrame* fr, int kind) {
-  if (blockIdx.x == 0 && threadIdx.x == 0) { fr->n_deferred[kind] = 0; fr->n_newraw[kind] = 0; }   // slot ids change: both lists are rebuilt from the raw flags
+  if (blockIdx.x == 0 && threadIdx.x == 0) map_move_begin(T, fr, kind);   // (nothing in this launch reads what it writes)
   for (unsigned s = blockIdx.x * 256 + threadIdx.x; s <= T.mask; s += gridDim.x * 256) {
     const RecVal v = rec_load(&T.rec[s]);
-    if (v.key == 0ull || v.count == 0) continue;
+    if (!rec_live(v)) continue;
     const int o = atomicAdd(n_tmp, 1);
-    if (o < cap) { VoxelRec r; r.key = v.key; r.sx = v.sum.x; r.sy = v.sum.y; r.sz = v.sum.z; r.si = v.sum.w; r.count = v.count; r.pend_cnt = key_seq(v.key) ? v.pend_cnt : 0; tmp[o] = r; }   // (a raw point's pend_cnt is its arrival stamp)
+    if (o < cap) rec_store_all(&tmp[o], v);
     else atomicOr(&fr->error, kErrMapFull);
   }
 }
 __global__ __launch_bounds__(256) void k_map_rebuild_insert(VoxelTable T, const VoxelRec* __restrict__ tmp, int cap, int* n_tmp, MapFrame* fr, int kind,
-                                                            int* __restrict__ deferred, int deferred_cap, float inv, int* host_flags) {
+                                                            int* __restrict__ deferred, int deferred_cap, int* host_flags) {
   const int n = min(*n_tmp, cap);
-  for (int e = blockIdx.x * 256 + threadIdx.x; e < n; e += gridDim.x * 256) {
-    const VoxelRec r = tmp[e];
-    unsigned s = (unsigned)mix64(r.key) & T.mask;
-    bool done = false;
-    for (int probe = 0; probe < kMaxProbe && !done; probe++, s = (s + 1) & T.mask) {
-      if (atomicCAS(&T.rec[s].key, 0ull, r.key) != 0ull) continue;   // keys are unique in the list
-      rec_store_value(&T.rec[s], make_float4(r.sx, r.sy, r.sz, r.si), r.count, r.pend_cnt);
-      int Ai, Aj, Ak;
-      unpack_cube(r.key, &Ai, &Aj, &Ak);
-      if (key_seq(r.key) == 0 && !map_publish_block(T, Ai, Aj, Ak, key_lx(r.key), key_ly(r.key), key_lz(r.key))) atomicOr(&fr->error, kErrMapFull);
-      if (key_seq(r.key) == 0 && rec_raw(r.count)) {  // raw voxel of a cube outside the valid block: still owed a centroid (see k_map_finalize)
-        const int dpos = atomicAdd(&fr->n_deferred[kind], 1);
-        if (dpos < deferred_cap) deferred[dpos] = (int)s;
-      }
-      done = true;
-    }
-    if (!done) atomicOr(&fr->error, kErrMapFull);
-  }
-  (void)inv;
+  for (int e = blockIdx.x * 256 + threadIdx.x; e < n; e += gridDim.x * 256)
+    map_reinsert(T, rec_load(&tmp[e]), fr, kind, deferred, deferred_cap);   // (the list holds live records only)
   if (blockIdx.x == 0 && threadIdx.x == 0) {
-    T.stats[0] = n; T.stats[1] = 0;
+    T.stats[0] = n;   // keys in the table (the block keys are counted by map_publish_block)
     if (host_flags) __hip_atomic_store(&host_flags[kind], 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
   }
 }
@@ -925,9 +909,8 @@ static vloam_status map_rebuild_enqueue(MapContext* m0, hipStream_t st, int sess
   VL_RAW_LAUNCH(k_map_rebuild_gather, dim3(1024), dim3(256), 0, st, T, m->rebuild_tmp, m->rebuild_cap, m->rebuild_n, m->frame, kind);
   if (hipMemsetAsync(T.rec, 0, slots * sizeof(VoxelRec), st) != hipSuccess) return VLOAM_ERR_HIP;
   if (hipMemsetAsync(T.blk, 0, bslots * sizeof(ulonglong2), st) != hipSuccess) return VLOAM_ERR_HIP;
-  if (hipMemsetAsync(T.stats, 0, 4 * sizeof(int), st) != hipSuccess) return VLOAM_ERR_HIP;
   VL_RAW_LAUNCH(k_map_rebuild_insert, dim3(1024), dim3(256), 0, st, T, m->rebuild_tmp, m->rebuild_cap, m->rebuild_n, m->frame, kind,
-                     m->deferred[kind], cap, m->inv_leaf[kind], m->host_flags);
+                     m->deferred[kind], cap, m->host_flags);
   m0->rebuilds++;
   return hipGetLastError() == hipSuccess ? VLOAM_OK : VLOAM_ERR_HIP;
 }

@@ -30,7 +30,7 @@ __global__ void k_map_register(const float4* __restrict__ cloud, const FrameScal
 // Is the record at a table slot a point of /laser_cloud_map (the window's centre cube at cW, cH, cD), and then its order key and the point:
 // the export's and the publication's one rule
 __device__ __forceinline__ bool pub_row(const RecVal& v, int cW, int cH, int cD, int kind, u64* okey, float4* p) {
-  if (v.key == 0ull || v.count == 0) return false;
+  if (!rec_live(v)) return false;
   if (key_seq(v.key) == 0 && rec_raw(v.count)) return false;   // a raw voxel is published through its point records
   int Ai, Aj, Ak;
   unpack_cube(v.key, &Ai, &Aj, &Ak);

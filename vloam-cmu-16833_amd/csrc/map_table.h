@@ -1,6 +1,6 @@
 // The voxel tables of the map as device code sees them: hash, voxel key, record access, occupancy blocks.  Shared by map_kernels.hip (the
-// sweep's kernels), map_output.hip (export and publication), map_grow.hip (the growable map's rehash), map_ckpt.hip, map_import.hip and, through
-// map_walk.h, map_query.hip and map_score.hip, which are separate code objects.  rec_find, rec_point and rec_order_key serve the map's readers
+// sweep's kernels), map_output.hip (export and publication), map_import.hip, the three movers of records (through map_move_dev.h, which holds
+// their text) and, through map_walk.h, map_query.hip and map_score.hip, which are separate code objects.  rec_find, rec_point and rec_order_key serve the map's readers
 // only (map_output.hip, map_walk.h and its two kernels): the sweep's kernels keep their own lookups.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -55,10 +55,19 @@ __device__ __forceinline__ RecVal rec_load(const VoxelRec* r) {
   v.count = (int)b.z; v.pend_cnt = (int)b.w;
   return v;
 }
+// live: the slot holds a key that was not purged (a purged record keeps its key so that probe chains stay intact)
+__device__ __forceinline__ bool rec_live(const RecVal& v) { return v.key != 0ull && v.count != 0; }
 // everything but the key (which only find-or-insert writes)
 __device__ __forceinline__ void rec_store_value(VoxelRec* r, float4 sum, int count, int pend_cnt) {
   reinterpret_cast<float2*>(r)[1] = make_float2(sum.x, sum.y);
   reinterpret_cast<uint4*>(r)[1] = make_uint4(__float_as_uint(sum.z), __float_as_uint(sum.w), (unsigned)count, (unsigned)pend_cnt);
+}
+// a whole record into a list or stream (not a table slot: no reader races for the key).  pend_cnt leaves a table as what it is between two
+// sweeps: a point record's arrival stamp, zero for a voxel's record
+__device__ __forceinline__ void rec_store_all(VoxelRec* r, const RecVal& v) {
+  uint4* o = reinterpret_cast<uint4*>(r);
+  o[0] = make_uint4((unsigned)v.key, (unsigned)(v.key >> 32), __float_as_uint(v.sum.x), __float_as_uint(v.sum.y));
+  o[1] = make_uint4(__float_as_uint(v.sum.z), __float_as_uint(v.sum.w), (unsigned)v.count, key_seq(v.key) ? (unsigned)v.pend_cnt : 0u);
 }
 
 // bounded lookup of one record; a chain of kMaxProbe slots counts as absent and is reported.  slot (may be null): where the record was found
@@ -101,31 +110,6 @@ __device__ bool map_publish_block(const VoxelTable& T, int Ai, int Aj, int Ak, i
     }
   }
   return false;
-}
-
-// One live record of a checkpoint's stream (k_map_ckpt_unpack) into table Tn, as k_map_rebuild_insert and k_map_grow do it: claim a slot (same
-// hash, same kMaxProbe, same CAS; keys are unique in the source), store the value, publish the voxel's occupancy block and re-append a raw voxel
-// to the deferred list.  pend[] of Tn is not written (map_grow.hip).  false: no slot within the probe bound (kErrMapFull raised).
-// k_map_grow keeps its own text of these lines: calling this function from it changes its register allocation (measured on the device assembly),
-// and the code objects of handles that are never saved or loaded are to stay what they are.
-__device__ __forceinline__ bool map_reinsert(const VoxelTable& Tn, const RecVal& v, MapFrame* fr, int kind, int* __restrict__ deferred, int deferred_cap) {
-  bool done = false;
-  const int seq = key_seq(v.key);
-  unsigned s = (unsigned)mix64(v.key) & Tn.mask;
-  for (int probe = 0; probe < kMaxProbe && !done; probe++, s = (s + 1) & Tn.mask) {
-    if (atomicCAS(&Tn.rec[s].key, 0ull, v.key) != 0ull) continue;
-    rec_store_value(&Tn.rec[s], v.sum, v.count, seq ? v.pend_cnt : 0);
-    int Ai, Aj, Ak;
-    unpack_cube(v.key, &Ai, &Aj, &Ak);
-    if (seq == 0 && !map_publish_block(Tn, Ai, Aj, Ak, key_lx(v.key), key_ly(v.key), key_lz(v.key))) atomicOr(&fr->error, kErrMapFull);
-    if (seq == 0 && rec_raw(v.count)) {
-      const int dpos = atomicAdd(&fr->n_deferred[kind], 1);
-      if (dpos < deferred_cap) deferred[dpos] = (int)s;
-    }
-    done = true;
-  }
-  if (!done) atomicOr(&fr->error, kErrMapFull);
-  return done;
 }
 
 }  // namespace vloam
