@@ -917,6 +917,68 @@ vloam_status vloam_get_stage_ms(vloam_handle* h, double ms4[4], int* scans);
  * {N_in, N2, n_sharp, n_lessSharp, n_flat, n_lessFlat, C, S, F_o_corner, F_o_plane, E_o, n_c, n_s, K_m, E_m, M} of the last scan. */
 vloam_status vloam_get_counts(vloam_handle* h, long long counts16[16]);
 
+/* Map clean-up: voxels that later sweeps see THROUGH are removed from the map — what a parked car, a pedestrian or a bus leaves behind.  A
+ * visibility test in the sensor's range image (one image per sweep), not a ray walk: conservative at grazing incidence, and integers from the
+ * projection on.  Opt-in by calling: a handle that never carves allocates and launches nothing of this, and no kernel of a sweep changes.
+ *   Projection of a point (x, y, z), all f32, every operation rounded on its own, atanf / atan2f glibc's (csrc/fdlibm_f32.h): h2 = x*x + y*y;
+ *   r = sqrtf(h2 + z*z); the point projects when x, y, z are finite, min_range <= r <= max_range and 0 <= rf < rows with
+ *   rf = (atanf(z / sqrtf(h2)) - e0) * ((float)rows / (e1 - e0)), e0 / e1 = elev_min_deg / elev_max_deg * 0.017453292f;
+ *   row = (int)floorf(rf); col = (int)floorf((atan2f(y, x) + PI_F) * ((float)cols / (2.0f * PI_F))), PI_F = 0x40490fdb, col == cols wraps to 0;
+ *   quantised range q = (unsigned)floorf(r / range_res).
+ *   1. Range images: per sweep rows x cols words, empty = 0xffffffff; every point of the sweep that projects leaves min(q) in its pixel.
+ *   2. Candidates: the live voxel records of the selected kinds (kind_mask: 1 corner map | 2 surf map) whose cube lies inside the 21 x 21 x 11
+ *      window, at the point vloam_get_map_kind returns for them.  Voxels that hold un-merged raw points (cubes outside the valid 5 x 5 x 3
+ *      block) are never removed: counted in skipped_raw.  Per sweep s the candidate goes into the sensor frame, p_s = R^T (p - t) with
+ *      q normalised and R from it in f64 on the host, d = (double)p - t, each component (R0c*d0 + R1c*d1) + R2c*d2 in f64, rounded to f32 —
+ *      and is projected as above (no projection: the sweep does not vote).  c the image's pixel there, m the minimum over the 3 x 3 pixels around
+ *      it (columns wrap, rows clamp), qm the candidate's quantised range, margin_q = (unsigned)floorf(margin / range_res):
+ *      the sweep SEES THROUGH the candidate when c is a return and qm + margin_q < m; it CONFIRMS it when c is a return and |qm - c| <= margin_q.
+ *      A candidate is removed when at least min_votes sweeps see through it and none confirms it.
+ *   3. apply == 1 (single-sequence handles): the removed records are dropped, the per-cube counts follow, and the table's same-size
+ *      reclamation (the rebuild of a fixed handle, the same-size rehash of a growable one) is enqueued before the call returns: table and
+ *      occupancy blocks keep no trace of them.  apply == 0 writes nothing the sequence owns.
+ *   The removed points come as packed (x, y, z, intensity) in unspecified order; counters and the removed SET are a function of the inputs alone.
+ * Poses: poses7[s] = (qx, qy, qz, qw, tx, ty, tz), map <- sensor of sweep s; NULL (n_sweeps == 1 only): the handle's last mapped pose.
+ * Both forms first synchronise the handle (as vloam_get_map_kind), run on the mapping stream and wait for their result: opt, n, poses7 and res
+ *   are host memory in both; vloam_map_carve takes host sweeps and a host list, vloam_map_carve_device a HOST array of n_sweeps device
+ *   addresses (packed float4 each) and a device list of cap points.  The scratch is one allocation made by the first call, kept until vloam_destroy.
+ * More removals than cap: VLOAM_ERR_CAPACITY, res filled (n_removed_out the capacity needed), the list's content undefined, nothing applied.
+ * Refusals, options first and before the handle is looked at (VLOAM_ERR_INVALID, each with its own vloam_last_error()): null options or
+ *   struct_size; kind_mask outside 1 .. 3; rows < 1, cols < 4 or rows * cols > 1048576; elevations that are not finite, outside -90 .. 90 or
+ *   less than 0.001 degrees apart; ranges that are not finite, min_range <= 0 or >= max_range; range_res not finite and positive or below
+ *   max_range / 2^30; margin negative, not finite or above 2^30 range_res; min_votes outside 1 .. 16; apply outside 0 .. 1; n_sweeps outside
+ *   1 .. 16; null arrays; a count outside 0 .. 262144; a null sweep with a positive count; null poses with n_sweeps > 1; a non-finite pose
+ *   component; a quaternion whose norm is off 1 by more than 1e-6; cap < 0 or a null list with cap > 0; a null result.  Then the handle: null
+ *   (VLOAM_ERR_INVALID); with_mapping == 0 (VLOAM_ERR_ORDER); apply on a handle with n_sessions > 1 (VLOAM_ERR_INVALID; a dry run works on
+ *   the selected session).
+ * Not offered: ray walking through free space, votes kept across calls, removal of un-merged raw points, re-insertion of what a sweep
+ *   confirms, per-point labels of the sweeps (which returns were dynamic). */
+typedef struct vloam_carve_options {   /* 48 bytes */
+  int struct_size;                     /* sizeof as compiled */
+  int kind_mask;                       /* 1 corner map | 2 surf map; default 3 */
+  int rows, cols;                      /* range image; default 64 x 1024 */
+  float elev_min_deg, elev_max_deg;    /* its vertical field of view; default -25, +3 */
+  float min_range, max_range;          /* metres; default 2, 80 */
+  float range_res;                     /* metres per range step; default 0.05 */
+  float margin;                        /* metres; default 0.5 */
+  int min_votes;                       /* sweeps that must see through; default 1 */
+  int apply;                           /* 0 dry run (default), 1 remove */
+} vloam_carve_options;
+typedef struct vloam_carve_result {    /* 104 bytes; [corner map, surf map] */
+  long long examined[2];               /* candidates */
+  long long in_view[2];                /* ... that project into at least one sweep's image */
+  long long seen_through[2];           /* ... that at least one sweep sees through */
+  long long confirmed[2];              /* ... that at least one sweep confirms */
+  long long removed[2];
+  long long skipped_raw[2];            /* voxels of un-merged raw points: never candidates */
+  long long n_removed_out;             /* points the list holds (VLOAM_ERR_CAPACITY: would have to hold) */
+} vloam_carve_result;
+void vloam_default_carve_options(vloam_carve_options* o);
+vloam_status vloam_map_carve(vloam_handle* h, const vloam_carve_options* o, const float* const* xyz_pad4, const int* n, const double* poses7,
+                             int n_sweeps, float* removed_xyzi4, long long cap, vloam_carve_result* res);
+vloam_status vloam_map_carve_device(vloam_handle* h, const vloam_carve_options* o, const void* const* d_xyz_pad4, const int* n, const double* poses7,
+                                    int n_sweeps, void* d_removed_xyzi4, long long cap, vloam_carve_result* res);
+
 #ifdef __cplusplus
 }
 #endif

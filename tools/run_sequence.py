@@ -225,6 +225,10 @@ def main():
                          "pose_frame = 1) and write LOC0.txt in the results-row format; the map is never updated, no sweep is added to the sequence")
     ap.add_argument("--save-map", metavar="DIR", help="after the last sweep write the map as DIR/corner.npy and DIR/surf.npy (vloam_get_map_kind: float32 [n, 4], map frame) "
                                                       "and the last mapped pose as DIR/start_pose.txt (qx qy qz qw tx ty tz): what --load-map takes, with any build of the library")
+    ap.add_argument("--carve", metavar="\"N_LAST_SWEEPS [MIN_VOTES]\"",
+                    help="after the last sweep, before --save-map: remove the map voxels that the run's last N_LAST_SWEEPS sweeps (at most 16) see through "
+                         "under their mapping poses and none of them confirms (vloam_map_carve, apply; MIN_VOTES sweeps must see through, default 1) — "
+                         "what a parked car or a pedestrian left in the map; the removed points are written as OUT/carved.npy")
     ap.add_argument("--load-map", metavar="DIR", help="import DIR/corner.npy and DIR/surf.npy as the map of the fresh handle before the first sweep (vloam_map_import); "
                                                       "with --localize-only as --resume: every sweep is localised against the imported map, which is never updated")
     ap.add_argument("--start-pose", metavar="\"qx qy qz qw tx ty tz\"", help="with --load-map: the map<-odometry transform the sequence starts with "
@@ -291,6 +295,13 @@ def main():
         a.relocalize = a.relocalize_global   # from the matched centre on it is --relocalize
     if a.relocalize:
         parse_relocalize(a.relocalize)
+    if a.carve:
+        w = a.carve.split()
+        if len(w) not in (1, 2) or not all(v.isdigit() for v in w) or not 1 <= int(w[0]) <= 16 or not 1 <= int(w[-1]) <= 16:
+            sys.exit("--carve \"N_LAST_SWEEPS [MIN_VOTES]\": 1 .. 16 sweeps, 1 .. 16 votes")
+        if a.localize_only or a.vloam:
+            sys.exit("--carve cleans the map of a LiDAR run that maps: not with --localize-only or --vloam")
+        a.carve = (int(w[0]), int(w[1]) if len(w) == 2 else 1)
     if a.resume and a.load_map:
         sys.exit("--resume and --load-map both fill a fresh handle: choose one")
     if a.start_pose and not a.load_map:
@@ -443,6 +454,14 @@ def main():
     print("wrote %d rows to %s/{LO0,MO0%s}.txt" % (n - start, a.out, ",VO0" if vo_rows else ""))
     if a.map_pub_number:
         print("wrote %d published maps to %s/map_<frame>.npy" % (n_pub, a.out))
+    if a.carve:   # clean the map with the run's last sweeps under their mapping poses (vloam_map_carve, apply)
+        n_last, votes = a.carve
+        first = max(start, n - n_last)
+        poses = hd.trajectory(first, n - first)[:, 7:14]
+        removed, res = hd.map_carve([load_sweep(k) for k in range(first, n)], poses, apply=True, min_votes=votes)
+        print("carved the map with sweeps %d .. %d (min_votes %d): %d corner / %d surf voxels removed of %d / %d examined (%d / %d confirmed)" % (
+            first, n - 1, votes, res["removed"][0], res["removed"][1], res["examined"][0], res["examined"][1], res["confirmed"][0], res["confirmed"][1]))
+        np.save(os.path.join(a.out, "carved.npy"), removed)
     if a.save_map:
         os.makedirs(a.save_map, exist_ok=True)
         halves = [hd.get_map_kind(k) for k in (0, 1)]

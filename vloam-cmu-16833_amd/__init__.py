@@ -143,6 +143,20 @@ MAP_IMPORT_RESULT_DTYPE = np.dtype([
     ("max_per_voxel", "<i4", (2,)), ("center_cube", "<i4", (3,)), ("pad", "<i4")])
 
 
+class CarveOptions(C.Structure):
+    """vloam_carve_options (c_api.h; vloam_map_carve / vloam_map_carve_device)."""
+    _fields_ = [("struct_size", C.c_int), ("kind_mask", C.c_int), ("rows", C.c_int), ("cols", C.c_int), ("elev_min_deg", C.c_float),
+                ("elev_max_deg", C.c_float), ("min_range", C.c_float), ("max_range", C.c_float), ("range_res", C.c_float), ("margin", C.c_float),
+                ("min_votes", C.c_int), ("apply", C.c_int)]
+
+
+# vloam_carve_result (c_api.h): 13 long long, 104 bytes; the pairs are [corner map, surf map]
+CARVE_RESULT_DTYPE = np.dtype([
+    ("examined", "<i8", (2,)), ("in_view", "<i8", (2,)), ("seen_through", "<i8", (2,)), ("confirmed", "<i8", (2,)), ("removed", "<i8", (2,)),
+    ("skipped_raw", "<i8", (2,)), ("n_removed_out", "<i8")])
+CARVE_MAX_SWEEPS = 16
+
+
 # vloam_sweep_record (c_api.h): 32 ints then 8 doubles, 192 bytes
 SWEEP_RECORD_DTYPE = np.dtype([
     ("frame", "<i4"), ("error_bits", "<i4"), ("flags", "<i4"), ("n_in", "<i4"), ("n_cloud", "<i4"), ("n_sharp", "<i4"), ("n_less_sharp", "<i4"),
@@ -1081,6 +1095,74 @@ class Handle:
         res = torch.zeros(MAP_IMPORT_RESULT_DTYPE.itemsize, dtype=torch.uint8, device=next((c.device for c in (corner, surf) if c is not None), "cuda"))
         self._chk(self.L.vloam_map_import_device(self.h, C.byref(opt), ptr[0], C.c_longlong(n[0]), ptr[1], C.c_longlong(n[1]), C.c_void_p(res.data_ptr())))
         return self._import_result(res.cpu().numpy().view(MAP_IMPORT_RESULT_DTYPE))
+
+    def _carve_options(self, apply, **kw):
+        opt = CarveOptions()
+        self.L.vloam_default_carve_options(C.byref(opt))
+        for k, v in kw.items():
+            if not hasattr(opt, k) or k == "struct_size":
+                raise AttributeError("vloam_carve_options has no field %r" % k)
+            setattr(opt, k, v)
+        opt.apply = int(apply)
+        return opt
+
+    @staticmethod
+    def _carve_poses(poses, n_sweeps):
+        if poses is None:
+            return None
+        p = np.ascontiguousarray(poses, dtype=np.float64).reshape(-1, 7)
+        assert p.shape[0] == n_sweeps, "one pose (qx qy qz qw tx ty tz, map <- sensor) per sweep"
+        return p
+
+    @staticmethod
+    def _carve_result(res):
+        return {k: (res[0][k].copy() if res[0][k].ndim else res[0][k].item()) for k in CARVE_RESULT_DTYPE.names}
+
+    def map_carve(self, sweeps, poses=None, apply=False, cap=None, **options):
+        """vloam_map_carve: remove (apply) or list (dry run, the default) the map voxels that the given sweeps see through.  sweeps: up to 16
+        arrays float32 [n, 4] (x, y, z, -) in the sensor frame, NaN rows allowed; poses: [n_sweeps, 7] (qx qy qz qw tx ty tz, map <- sensor),
+        None with one sweep: the last mapped pose; options: fields of vloam_carve_options (kind_mask, rows, cols, elev_min_deg, elev_max_deg,
+        min_range, max_range, range_res, margin, min_votes).  cap: capacity of the removed list (None: a dry run sizes it first).  Returns
+        (removed float32 [n, 4] in unspecified order, the fields of vloam_carve_result as a dict).  Synchronises the handle."""
+        clouds = [np.ascontiguousarray(s, dtype=np.float32).reshape(-1, 4) for s in sweeps]
+        ns = len(clouds)
+        ptrs = (C.c_void_p * max(ns, 1))(*[c.ctypes.data if c.shape[0] else None for c in clouds])
+        n = (C.c_int * max(ns, 1))(*[c.shape[0] for c in clouds])
+        p = self._carve_poses(poses, ns)
+        res = np.zeros(1, dtype=CARVE_RESULT_DTYPE)
+
+        def call(apply_now, buf, cap_now):
+            opt = self._carve_options(apply_now, **options)
+            return self.L.vloam_map_carve(self.h, C.byref(opt), ptrs, n, None if p is None else _fp(p), ns, None if buf is None else _fp(buf),
+                                          C.c_longlong(cap_now), _fp(res))
+        if cap is None:   # a dry run with an empty list: VLOAM_OK when nothing leaves, else the capacity needed
+            st = call(False, None, 0)
+            if st != ERR_CAPACITY:
+                self._chk(st)
+                if not apply:
+                    return np.zeros((0, 4), np.float32), self._carve_result(res)
+            cap = int(res[0]["n_removed_out"])
+        buf = np.zeros((max(int(cap), 1), 4), dtype=np.float32)
+        self._chk(call(apply, buf if cap else None, int(cap)))
+        return buf[:int(res[0]["n_removed_out"])].copy(), self._carve_result(res)
+
+    def map_carve_device(self, sweeps, poses, removed, apply=False, **options):
+        """vloam_map_carve_device: the same with torch tensors on the device — sweeps float32 [n, 4] each, removed a float32 [cap, 4] tensor
+        the removed points are written into.  Returns the fields of vloam_carve_result as a dict (n_removed_out rows of removed are valid);
+        more removals than cap raise VloamError(ERR_CAPACITY)."""
+        ns = len(sweeps)
+        for c in sweeps:
+            assert c.is_cuda and c.is_contiguous() and c.element_size() == 4 and c.dtype.is_floating_point and c.shape[-1] == 4
+        assert removed.is_cuda and removed.is_contiguous() and removed.element_size() == 4 and removed.shape[-1] == 4
+        ptrs = (C.c_void_p * max(ns, 1))(*[c.data_ptr() if c.shape[0] else None for c in sweeps])
+        n = (C.c_int * max(ns, 1))(*[int(c.shape[0]) for c in sweeps])
+        p = self._carve_poses(poses, ns)
+        res = np.zeros(1, dtype=CARVE_RESULT_DTYPE)
+        opt = self._carve_options(apply, **options)
+        cap = int(removed.shape[0])
+        self._chk(self.L.vloam_map_carve_device(self.h, C.byref(opt), ptrs, n, None if p is None else _fp(p), ns,
+                                                C.c_void_p(removed.data_ptr()) if cap else None, C.c_longlong(cap), _fp(res)))
+        return self._carve_result(res)
 
     def published_map(self):
         """The latest /laser_cloud_map the mapping stream published (vloam_limits::map_pub_number): (float32 [n, 4], 0-based sweep index),

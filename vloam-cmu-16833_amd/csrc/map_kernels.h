@@ -171,6 +171,20 @@ struct MapLocalize {
   vloam_localize_result* result = nullptr;   // the host form's record
 };
 
+// Map clean-up (vloam_map_carve; map_carve.hip): what one call's kernels share.  The scratch — poses, counters, range images, uploaded sweeps and
+// the removed list — is one allocation of its own made by the first call and regrown when a call needs more; null on a handle that never carves.
+struct CarveGeom {        // the projection into the range image, f32 as c_api.h states it (set on the host: carve_geom)
+  int rows, cols, n_sweeps, min_votes;
+  float min_range, max_range, range_res;
+  float elev_min, row_scale, col_scale;
+  unsigned margin_q;
+};
+struct CarvePose { double R[9], t[3]; };   // map <- sensor: p_map = R p_s + t (row-major R, from the normalised quaternion)
+constexpr int kCarveMaxSweeps = 16, kCarveMaxPoints = 262144, kCarveMaxPixels = 1 << 20;
+constexpr int kCarveCounters = 6;          // examined, in_view, seen_through, confirmed, removed, skipped_raw
+struct CarveCounters { unsigned long long cnt[2][kCarveCounters]; unsigned long long n_removed; };
+struct MapCarve { char* base = nullptr; size_t bytes = 0; };
+
 struct MapContext {
   MapState* state = nullptr;
   MapFrame* frame = nullptr;
@@ -218,6 +232,7 @@ struct MapContext {
     return m;
   }
   MapLocalize* loc = nullptr;   // localisation scratch: null until the first vloam_map_localize* call (host-side; not rebased: single-sequence handles only)
+  MapCarve* carve = nullptr;    // map clean-up scratch: null until the first vloam_map_carve* call (host-side, like loc)
   MapPub pub;              // published clouds (off on a default handle)
   float4* registered = nullptr;  // full-resolution cloud in the map frame, on request
   long long* assoc_cyc = nullptr;  // [2][8] debug: phase cycle sums of k_map_assoc per outer round
@@ -233,6 +248,7 @@ vloam_status map_init(MapContext* m, hipStream_t st);
 vloam_status map_enqueue(MapContext* m, const vloam_config& cfg, hipStream_t st, const SRBuffers& cur, LOState* lo, double* traj_row14,
                          bool skip_frame, int set, ProfHook* ph, hipEvent_t done = nullptr);
 vloam_status map_force_rebuild(MapContext* m, hipStream_t st);  // every session
+vloam_status map_reclaim_enqueue(MapContext* m, hipStream_t st, int kind);   // one table of a single-sequence handle: rebuild (fixed) or same-size rehash (growable)
 void map_destroy(MapContext* m);
 // ---- map_stack.hip: the scan-feature VoxelGrid, enqueued on the scan-registration stream
 vloam_status map_stack_enqueue(MapContext* m, hipStream_t st, const SRBuffers& cur, int set, ProfHook* ph, hipEvent_t done = nullptr);
@@ -284,6 +300,13 @@ void map_stack_enqueue_loc(MapContext* m, hipStream_t st, const float4* corner, 
 // h_result: host memory.  The sticky map-full error is the caller's to read (MapFrame::error).
 vloam_status map_import_run(MapContext* m, hipStream_t st, const double pose7[7], const void* const cloud[2], const int n[2], bool host_clouds,
                             vloam_map_import_result* h_result);
+// ---- map_carve.hip (a code object of its own): vloam_map_carve.  With nothing of the handle in flight, on st: range images of the sweeps
+// (clouds[s]: n[s] packed float4, host memory with host_io, else device addresses), the vote over the records of the kinds in kind_mask of session
+// `session`, the removed points into `removed` (cap points; host memory with host_io) and, with apply (single-sequence handles), the removal and the
+// tables' reclamation.  Waits for st.  h_out: the counters; n_removed > cap: nothing was applied.
+vloam_status map_carve_run(MapContext* m, int session, hipStream_t st, const CarveGeom& G, int kind_mask, const void* const* clouds, const int* n,
+                           const CarvePose* poses, bool host_io, void* removed, long long cap, bool apply, CarveCounters* h_out);
+void map_carve_free(MapContext* m);
 // ---- map_grow.hip: growable handles (m->grow != null).  map_force_grow: test hook, one doubling of both tables now (between two sweeps, on the mapping stream).
 // map_grow_release: frees retired buffers whose grow chain has finished (hipEventQuery); call with nothing of the handle in flight — hipFree
 // synchronises the device.

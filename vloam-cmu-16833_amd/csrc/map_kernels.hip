@@ -891,6 +891,7 @@ vloam_status map_init(MapContext* m, hipStream_t st) {
 
 void map_destroy(MapContext* m) {
   map_localize_free(m);
+  map_carve_free(m);
   if (m->grow) map_grow_destroy(m);
   if (m->host_flags) { (void)hipHostFree(m->host_flags); m->host_flags = nullptr; }
   for (int k = 0; k < 2; k++)
@@ -914,6 +915,8 @@ static vloam_status map_rebuild_enqueue(MapContext* m0, hipStream_t st, int sess
   m0->rebuilds++;
   return hipGetLastError() == hipSuccess ? VLOAM_OK : VLOAM_ERR_HIP;
 }
+
+vloam_status map_reclaim_enqueue(MapContext* m, hipStream_t st, int kind) { return map_rebuild_enqueue(m, st, 0, kind); }
 
 vloam_status map_force_rebuild(MapContext* m, hipStream_t st) {
   for (int b = 0; b < m->se.B; b++)
