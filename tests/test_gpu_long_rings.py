@@ -9,7 +9,7 @@ import sys
 import numpy as np
 import pytest
 
-from test_gpu_scan_registration import check_cloud
+from test_gpu_scan_registration import FAR_RING, assert_grid_too_fine, check_cloud, far_stretch_cloud
 from test_gpu_batch import same_poses
 from test_gpu_launch_configs import LAUNCH, assert_map, assert_poses, oracle_for
 
@@ -93,6 +93,20 @@ def test_ring_of_exactly_the_long_tier_limit_and_one_more(vl, orc):
         h.scan_registration(one_ring(16385, noise=0.05))
         h.laser_odometry()   # (the stage that reads the sweep's error word)
     assert ei.value.status == vl.ERR_CAPACITY and "16384" in str(ei.value)
+
+
+def test_voxel_grid_too_fine_for_a_long_ring_passes_its_candidates_through(vl, orc, synth):
+    """The same guard of the per-ring VoxelGrid(0.2) in the long tier: the far-stretch cloud with 4 097 returns on its far ring, on a handle
+    of the smallest ring capacity above 4 096."""
+    cloud = far_stretch_cloud(synth, n_far_ring=4097)
+    h = vl.Handle(0, scan_line=16, max_ring_points=4097, debug=1, with_mapping=0)
+    h.reset_frame()
+    h.scan_registration(cloud)
+    o = orc.Oracle(scan_line=16, with_mapping=False)
+    assert o.scan_registration(cloud) == 0
+    assert np.bincount(o.cloud(0)[:, 3].astype(np.int64))[FAR_RING] == 4097
+    assert_grid_too_fine(o, FAR_RING)
+    check_features(h, o, "far stretch on a 4 097-point ring")
 
 
 def test_long_rings_with_a_voxel_for_almost_every_point(vl, orc, synth):

@@ -132,6 +132,53 @@ def test_rings_with_a_voxel_for_almost_every_point(vl, orc, synth):
         check_cloud(h.features(which), o.cloud(which), name, max_flips=flips)
 
 
+FAR_RING = 8   # the scan line of far_stretch_cloud that carries the far returns
+
+
+def far_stretch_cloud(synth, n_far_ring=256):
+    """16 scan lines of 256 columns at ~20 m (FAR_RING: n_far_ring columns) in ring-major order.  On FAR_RING the returns of the azimuths
+    -140 .. -208 degrees (48 consecutive ones at 256 columns) lie at ~20 km: x spans 4.7 km there and y 22 km, z 350 m."""
+    rng = np.random.default_rng(11)
+    rings = []
+    for r, el_deg in enumerate(synth.beam_elevations_deg(16)):
+        n = n_far_ring if r == FAR_RING else 256
+        az = -2 * np.pi * np.arange(n) / n
+        rad = 20.0 + 0.05 * rng.standard_normal(n)
+        if r == FAR_RING:
+            far = (np.arange(n) * 256 >= 100 * n) & (np.arange(n) * 256 < 148 * n)
+            rad[far] = 20000.0 + 5.0 * rng.standard_normal(np.count_nonzero(far))
+        el = np.deg2rad(el_deg)
+        c = np.zeros((n, 4), dtype=np.float32)
+        c[:, 0], c[:, 1], c[:, 2] = rad * np.cos(el) * np.cos(az), rad * np.cos(el) * np.sin(az), rad * np.sin(el)
+        rings.append(c)
+    return np.concatenate(rings)
+
+
+def assert_grid_too_fine(o, ring):
+    """The premise of the guard cases, from the oracle's labels and cloud: the lessFlat candidates of `ring` (label <= 0 inside the six sectors)
+    span more than INT_MAX cells of 0.2 m by PCL's dx * dy * dz, and the oracle's lessFlat cloud holds every one of them (output = input)."""
+    full, lab = o.cloud(0), o.sr_ints(2)
+    s, e = int(o.sr_ints(3)[ring]), int(o.sr_ints(4)[ring])   # the sectors cover [s, e - 1]
+    assert np.all(full[s:e, 3].astype(np.int32) == ring)
+    cand = full[s:e][lab[s:e] <= 0]
+    inv = np.float32(1.0) / np.float32(0.2)   # inverse_leaf_size_
+    ext = ((cand[:, :3].max(axis=0) - cand[:, :3].min(axis=0)).astype(np.float32) * inv).astype(np.int64) + 1
+    cells = int(ext[0]) * int(ext[1]) * int(ext[2])
+    assert cells > 2 ** 31 - 1, "ring %d: only %d cells" % (ring, cells)
+    kept = np.count_nonzero(o.cloud(4)[:, 3].astype(np.int32) == ring)
+    assert kept == cand.shape[0] and kept >= 20, "ring %d: %d lessFlat points for %d candidates" % (ring, kept, cand.shape[0])
+
+
+def test_voxel_grid_too_fine_for_a_ring_passes_its_candidates_through(vl, orc, synth):
+    """PCL's "leaf size is too small" guard of the per-ring VoxelGrid(0.2) in the LDS tier: a ring whose lessFlat candidates reach from 20 m
+    to 20 km has more than INT_MAX cells, and the filter's output is its input, in input order."""
+    h, o = run_both(vl, orc, far_stretch_cloud(synth), scan_line=16)
+    assert_grid_too_fine(o, FAR_RING)
+    check_cloud(h.features(0), o.cloud(0), "laserCloud")
+    for which, name in [(1, "sharp"), (2, "lessSharp"), (3, "flat"), (4, "lessFlat")]:
+        check_cloud(h.features(which), o.cloud(which), name)
+
+
 def test_equal_curvatures_are_picked_in_the_canonical_order(vl, orc, synth):
     """Ties.  std::sort leaves points of equal curvature in an unspecified order (scan_registration.cpp:323); the oracle's canonical order
     is (curvature, index), walked from the top for the sharp picks and from the bottom for the flat picks.  The device never sorts: a pick is

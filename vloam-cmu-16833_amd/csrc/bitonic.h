@@ -1,6 +1,6 @@
 // Bitonic sorting network on u64 keys in LDS for a workgroup of `nthreads` lanes (a multiple of 64): strides below 64 are cross-lane
 // exchanges on keys held in registers, only the wide strides go through LDS behind a workgroup barrier.  Shared by the scan-registration
-// ring kernel (voxel runs of a scan line, sr_kernels.hip) and the mapping stage's scan-feature VoxelGrid (map_stack.hip) and published map (map_output.hip).
+// ring kernels (voxel runs of a scan line, sr_ring.hip; voxel keys of a long one, sr_ring_long.hip) and the mapping stage's scan-feature VoxelGrid (map_stack.hip) and published map (map_output.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -1,4 +1,4 @@
-// Host-visible launch interface of the scan-registration kernels (sr_kernels.hip).
+// Host-visible launch interface of the scan-registration kernels (sr_kernels.hip; the ring kernels: sr_ring.hip, sr_ring_long.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 #include "vloam_device.h"

@@ -17,71 +17,19 @@
 //                                working arrays in HBM, sectors walked in order; launched like the big tier, behind it
 //   k_sr_compact     1 WG/ring   ring/sector-ordered feature clouds (+ per-ring bounding boxes of the less-clouds for the mapping
 //                                stage's VoxelGrid)                                                 SR:338-344,388,439
+// This file: first / last, label, scatter, compact, adopt and the launch.  k_sr_ring: sr_ring.hip; k_sr_ring_long: sr_ring_long.hip; the rules
+// those two share: sr_ring_dev.h.
 #include <hip/hip_runtime.h>
 #include <limits.h>
 #include <float.h>
-#include <type_traits>
 #include <math.h>
 #include "sr_kernels.h"
-#include "bitonic.h"
+#include "sr_ring.h"
+#include "sr_wave.h"
 #include "fdlibm_f32.h"
 #include <cstdlib>
 
 namespace vloam {
-
-typedef unsigned long long u64;
-
-__device__ __forceinline__ void lds_fence_wave() {
-  // LDS ops of one wavefront retire in order; this only has to stop the compiler from caching or
-  // reordering LDS accesses across the point where lanes exchange data.
-  __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
-  __builtin_amdgcn_wave_barrier();
-}
-
-// Wavefront-wide unsigned max / min through DPP row operations (no LDS crossbar, a handful of cycles per step): quad swaps,
-// row rotations, then the row_bcast15 / row_bcast31 carries of gfx9; the result lands in lane 63 and is broadcast.
-template <int CTRL, int ROW_MASK>
-__device__ __forceinline__ unsigned dpp_max_step(unsigned v) {
-  const unsigned o = (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, CTRL, ROW_MASK, 0xf, false);  // lanes without a source keep 0
-  return o > v ? o : v;
-}
-__device__ __forceinline__ unsigned wave_max_u32(unsigned v) {
-  v = dpp_max_step<0xB1, 0xf>(v);   // quad_perm [1,0,3,2]
-  v = dpp_max_step<0x4E, 0xf>(v);   // quad_perm [2,3,0,1]
-  v = dpp_max_step<0x124, 0xf>(v);  // row_ror:4
-  v = dpp_max_step<0x128, 0xf>(v);  // row_ror:8   -> every lane holds the max of its row of 16
-  v = dpp_max_step<0x142, 0xa>(v);  // row_bcast15 -> rows 1 and 3 fold in the row below
-  v = dpp_max_step<0x143, 0xc>(v);  // row_bcast31 -> rows 2 and 3 fold in lane 31
-  return (unsigned)__builtin_amdgcn_readlane((int)v, 63);
-}
-__device__ __forceinline__ unsigned wave_min_u32(unsigned v) { return ~wave_max_u32(~v); }
-// The same steps for f32 min / max (finite values) and an integer sum; lanes without a source combine with themselves (min / max) or 0 (sum).
-template <int CTRL, int ROW_MASK, bool MAX>
-__device__ __forceinline__ float dpp_fminmax_step(float v) {
-  const float o = __int_as_float(__builtin_amdgcn_update_dpp(__float_as_int(v), __float_as_int(v), CTRL, ROW_MASK, 0xf, false));
-  return MAX ? fmaxf(o, v) : fminf(o, v);
-}
-template <bool MAX>
-__device__ __forceinline__ float wave_fminmax(float v) {
-  v = dpp_fminmax_step<0xB1, 0xf, MAX>(v);
-  v = dpp_fminmax_step<0x4E, 0xf, MAX>(v);
-  v = dpp_fminmax_step<0x124, 0xf, MAX>(v);
-  v = dpp_fminmax_step<0x128, 0xf, MAX>(v);
-  v = dpp_fminmax_step<0x142, 0xa, MAX>(v);
-  v = dpp_fminmax_step<0x143, 0xc, MAX>(v);
-  return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 63));
-}
-template <int CTRL, int ROW_MASK>
-__device__ __forceinline__ int dpp_add_step(int v) { return v + __builtin_amdgcn_update_dpp(0, v, CTRL, ROW_MASK, 0xf, false); }
-__device__ __forceinline__ int wave_sum_i32(int v) {
-  v = dpp_add_step<0xB1, 0xf>(v);
-  v = dpp_add_step<0x4E, 0xf>(v);
-  v = dpp_add_step<0x124, 0xf>(v);
-  v = dpp_add_step<0x128, 0xf>(v);
-  v = dpp_add_step<0x142, 0xa>(v);
-  v = dpp_add_step<0x143, 0xc>(v);
-  return __builtin_amdgcn_readlane(v, 63);
-}
 
 // SR:157 removeNaNFromPointCloud + SR:100-129 removeClosedPointCloud
 __device__ __forceinline__ bool sr_survives_s1(float x, float y, float z, float thres) {
@@ -380,938 +328,6 @@ __global__ __launch_bounds__(kLabelThreads) void k_sr_scatter(BatchIn bi, FrameS
 }
 
 // ------------------------------------------------------------------------------------------------
-// Block-wide helpers for k_sr_ring (512 threads = 8 wavefronts).
-constexpr int kRingThreads = 512;
-
-// In-place exclusive scan of an LDS int array (n <= 16 * kRingThreads); returns the total.  Per-thread chunk sums, a shuffle scan inside
-// every wavefront, the eight wavefront totals through LDS: three workgroup barriers (a Hillis-Steele scan over 512 partial sums took 18).
-__device__ int block_exclusive_scan(int* a, int n, int* scratch /* kRingThreads ints */) {
-  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-  const int per = (n + kRingThreads - 1) / kRingThreads;
-  const int lo = tid * per, hi = min(lo + per, n);
-  int s = 0;
-  for (int k = lo; k < hi; k++) s += a[k];
-  int inc = s;
-  for (int d = 1; d < 64; d <<= 1) { const int o = __shfl_up(inc, d); if (lane >= d) inc += o; }
-  __syncthreads();   // (scratch may still be read by the caller's previous use)
-  if (lane == 63) scratch[wv] = inc;
-  __syncthreads();
-  int base = 0, total = 0;
-  for (int w = 0; w < kRingThreads / 64; w++) { const int t = scratch[w]; base += w < wv ? t : 0; total += t; }
-  int run = base + inc - s;
-  for (int k = lo; k < hi; k++) { int v = a[k]; a[k] = run; run += v; }
-  __syncthreads();
-  return total;
-}
-
-__device__ __forceinline__ void bitonic_step(u64* a, int t, int j, int k) {
-  const int i = ((t & ~(j - 1)) << 1) | (t & (j - 1));
-  const int l = i | j;
-  const bool up = (i & k) == 0;
-  const u64 x = a[i], y = a[l];
-  if ((x > y) == up) { a[i] = y; a[l] = x; }
-}
-
-// SR:353-376 == SR:397-420.  Serial neighbour suppression around local index ind (one lane).
-__device__ void sr_spread(int ind, const float* px, const float* py, const float* pz, unsigned char* picked) {
-  for (int l = 1; l <= 5; l++) {
-    float dx = px[ind + l] - px[ind + l - 1];
-    float dy = py[ind + l] - py[ind + l - 1];
-    float dz = pz[ind + l] - pz[ind + l - 1];
-    if ((double)(dx * dx + dy * dy + dz * dz) > 0.05) break;
-    picked[ind + l] = 1;
-  }
-  for (int l = -1; l >= -5; l--) {
-    float dx = px[ind + l] - px[ind + l + 1];
-    float dy = py[ind + l] - py[ind + l + 1];
-    float dz = pz[ind + l] - pz[ind + l + 1];
-    if ((double)(dx * dx + dy * dy + dz * dz) > 0.05) break;
-    picked[ind + l] = 1;
-  }
-}
-
-// Two capacity tiers of the LDS-resident ring.  CAP = kRingCapSmall covers every real HDL-64E / HDL-32 / VLP-16 ring (a revolution
-// has <= ~2 100 firings) in 78.75 KB of LDS, so TWO rings share a CU (and other kernels' workgroups still find LDS next to one);
-// the kMaxRingLen tier (146 KB, one workgroup per CU) is launched right behind it and only works on rings the small tier had to
-// leave alone (len > kRingCapSmall).
-constexpr int kRingCapSmall = 2176, kSectCapSmall = 512, kRingWatch = 2144;   // an HDL-64E revolution at 10 Hz has <= 2 083 firings per laser
-constexpr int kLongWatch = kMaxRingLen - 32;   // the big tier's warning to the long tier (the same margin)
-template <int CAP, int SECT>
-constexpr size_t sr_ring_keys_bytes() { return sizeof(u64) * kSectors * SECT > (size_t)12 * CAP ? sizeof(u64) * kSectors * SECT : (size_t)12 * CAP; }
-
-template <int CAP, int SECT, bool BIG_TIER>
-__global__ __launch_bounds__(kRingThreads) void k_sr_ring(const float4* __restrict__ cloud, FrameScalars* S, int* __restrict__ sharp_idx,
-                                                          int* __restrict__ less_sharp_idx, int* __restrict__ flat_idx,
-                                                          float4* __restrict__ ring_ds, float* __restrict__ dbg_curv,
-                                                          int* __restrict__ dbg_sort, int* __restrict__ dbg_picked,
-                                                          int* __restrict__ dbg_label, long long* __restrict__ dbg_cyc /* [rings][8] */,
-                                                          int* ring_watch /* host-mapped [2][kMaxBatch] */, int tier_follows, size_t ss) {
-  VL_SESSION(ss); RB(cloud); RB(S); RB(sharp_idx); RB(less_sharp_idx); RB(flat_idx); RB(ring_ds); RB(dbg_curv); RB(dbg_sort); RB(dbg_picked);
-  RB(dbg_label); RB(dbg_cyc);
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  float* px = (float*)smem;                          // [CAP]
-  float* py = px + CAP;
-  float* pz = py + CAP;
-  float* pi = pz + CAP;                              // intensity
-  u64* keys = (u64*)(pi + CAP);                      // debug sort: [kSectors * SECT]; VoxelGrid: run keys [CAP] + voxel ids [CAP]
-  int* iscratch = (int*)((unsigned char*)keys + sr_ring_keys_bytes<CAP, SECT>());  // [CAP] heads / ranks
-  int* scan_tmp = iscratch + CAP;                    // [kRingThreads]
-  unsigned char* picked = (unsigned char*)(scan_tmp + kRingThreads);  // [CAP]
-  signed char* label = (signed char*)(picked + CAP);                 // [CAP]
-  unsigned char* gap = (unsigned char*)(label + CAP);                // [CAP]
-  unsigned char* reachb = gap + CAP;                                 // [CAP]
-  int* s_sp = (int*)(reachb + CAP);                                   // [kSectors]   (all LDS lives in the dynamic
-  int* s_ep = s_sp + 8;                                              // [kSectors]    region so its base stays 16-B aligned)
-  float* s_red = (float*)(s_ep + 8);                                 // [6]
-  int* s_ncand_p = (int*)(s_red + 8);
-  int* s_leak_lo = s_ncand_p + 8;                                     // [kSectors] lowest / highest local index marked by
-  int* s_leak_hi = s_leak_lo + 8;                                    // [kSectors] sector s's picks (unclipped)
-  int* s_zone = s_leak_hi + 8;                                       // [kSectors] incoming spill the sector was computed with
-  int* s_any = s_zone + 8;
-
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  // One workgroup per ring (gridDim.x == kMaxRings) — or, as the catch-all behind the small tier on sweeps for which the host has
-  // not launched the full big tier, ONE workgroup per session that walks the rings and works on the (normally zero) oversized ones.
-  auto one_ring = [&](const int r) {
-  long long tstamp[8];
-  int nstamp = 0;
-#define SR_STAMP() do { if (dbg_cyc) tstamp[nstamp] = clock64(); nstamp++; } while (0)
-  SR_STAMP();
-  const int len = S->ring_count[r], off = S->ring_off[r];
-  const int start = off + 5, end = off + len - 6;  // SR:278-280
-  if (BIG_TIER && len <= kRingCapSmall) return;    // the small tier has done this ring
-  if (tid < kSectors * 3) (&S->sect_cnt[r][0][0])[tid] = 0;
-  if (tid == 0) S->ring_ds_cnt[r] = 0;
-  // The big tier asks for 146 KB of LDS just to start, which on a busy chip (batches) costs tens of microseconds even when it has
-  // nothing to do: the host only launches its full grid while rings near the small tier's capacity have been seen (ring_watch, a
-  // host-mapped word it polls without synchronising) or during the first sweeps; otherwise a single catch-all workgroup per session
-  // follows the small tier, so that a ring which outgrows the small tier without that warning is still processed (slowly: the rings
-  // one after the other, until the host has seen the watch word).
-  // The same between the big tier and the long tier (k_sr_ring_long, long-tier handles only): the big tier raises the second watch word
-  // (ring_watch[kMaxBatch + session]) for rings near kMaxRingLen, which the host only reads on handles that have a long tier.
-  if (!BIG_TIER && tid == 0 && len > kRingWatch && ring_watch) __hip_atomic_store(&ring_watch[blockIdx.z], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-  if (BIG_TIER && tid == 0 && len > kLongWatch && ring_watch) __hip_atomic_store(&ring_watch[kMaxBatch + blockIdx.z], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-  // tier_follows: the next tier is launched behind this one (small tier: the big tier; big tier: the long tier) and takes what does not fit
-  if (len > CAP) { if (!tier_follows && tid == 0) atomicOr(&S->error, kErrRingTooLong); return; }
-  if (end - start < 6) return;  // SR:314
-
-  for (int l = tid; l < len; l += kRingThreads) {
-    float4 p = cloud[off + l];
-    px[l] = p.x; py[l] = p.y; pz[l] = p.z; pi[l] = p.w;
-    picked[l] = 0; label[l] = 0;  // SR:305-306
-  }
-  if (tid < kSectors) {
-    s_sp[tid] = start + (end - start) * tid / 6;            // SR:319
-    s_ep[tid] = start + (end - start) * (tid + 1) / 6 - 1;  // SR:320
-  }
-  __syncthreads();
-  SR_STAMP();
-
-  // ---- neighbour-suppression reach of every point, computed once in parallel (SR:353-376 walks outwards while consecutive
-  // points are closer than sqrt(0.05) m): gap bit l = 1 when dist2(p[l+1], p[l]) > 0.05; reach[l] = (how many of l-1..l-5) |
-  // (how many of l+1..l+5) << 4 a pick at l would mark.  The gap bits of 64 consecutive points are one ballot word; a point then
-  // reads its five bits forward and five bits backward out of three words (count of trailing / leading zeros) instead of walking up to
-  // ten bytes, each a dependent LDS round trip.
-  u64* gapw = (u64*)gap;   // [CAP / 64 + 1] ballot words (the byte array's place)
-  for (int base = wave * 64; base < len; base += kRingThreads) {   // wavefront-uniform
-    const int l = base + lane;
-    bool g = true;
-    if (l + 1 < len) {
-      const float dx = px[l + 1] - px[l], dy = py[l + 1] - py[l], dz = pz[l + 1] - pz[l];
-      g = (double)(dx * dx + dy * dy + dz * dz) > 0.05;
-    }
-    const u64 m = __ballot(g);
-    if (lane == 0) gapw[base >> 6] = m;
-  }
-  __syncthreads();
-  for (int l = 5 + tid; l < len - 5; l += kRingThreads) {  // picks are >= 5 away from both ring ends
-    const int c = l >> 6, b = l & 63;
-    const u64 w0 = gapw[c], wn = gapw[c + 1], wp = c > 0 ? gapw[c - 1] : 0ull;
-    // forward: bits l .. l+4 (SR:353-364 stops at the first gap)
-    const unsigned fw = (unsigned)(((w0 >> b) | ((wn << 1) << (63 - b))) & 31ull);
-    const int f = min(5, (int)__builtin_ctz(fw | 32u));
-    // backward: bits l-1 .. l-5, bit l-1 on top (SR:365-376)
-    const unsigned bw = b >= 5 ? (unsigned)((w0 >> (b - 5)) & 31ull) : (unsigned)(((wp >> (59 + b)) | (w0 << (5 - b))) & 31ull);
-    const int k = min(5, (int)__builtin_clz((bw << 27) | (1u << 26)));
-    reachb[l] = (unsigned char)(k | (f << 4));
-  }
-
-  auto curvature = [&](int i) {  // SR:288-303
-    const float dX = px[i - 5] + px[i - 4] + px[i - 3] + px[i - 2] + px[i - 1] - 10 * px[i] + px[i + 1] + px[i + 2] + px[i + 3] + px[i + 4] + px[i + 5];
-    const float dY = py[i - 5] + py[i - 4] + py[i - 3] + py[i - 2] + py[i - 1] - 10 * py[i] + py[i + 1] + py[i + 2] + py[i + 3] + py[i + 4] + py[i + 5];
-    const float dZ = pz[i - 5] + pz[i - 4] + pz[i - 3] + pz[i - 2] + pz[i - 1] - 10 * pz[i] + pz[i + 1] + pz[i + 2] + pz[i + 3] + pz[i + 4] + pz[i + 5];
-    return dX * dX + dY * dY + dZ * dZ;
-  };
-
-  // ---- debug only: the reference's std::sort of every sector (SR:323, canonical tie order: index ascending), as a
-  // wavefront-local bitonic network in LDS.  The production path below never sorts.
-  if (dbg_sort && wave < kSectors) {
-    const int sp = s_sp[wave] - off, ep = s_ep[wave] - off;  // local indices
-    const int seclen = ep - sp + 1;
-    int P = 2;
-    while (P < seclen) P <<= 1;
-    u64* K = keys + wave * SECT;
-    for (int t = lane; t < P; t += 64) {
-      u64 key = ~0ull;
-      if (t < seclen) key = ((u64)__float_as_uint(curvature(sp + t)) << 32) | (unsigned)(sp + t);  // c >= 0: bits order like the value
-      K[t] = key;
-    }
-    lds_fence_wave();
-    for (int k = 2; k <= P; k <<= 1)
-      for (int j = k >> 1; j > 0; j >>= 1) {
-        bitonic_stage(K, P, j, k, lane, 64);
-        lds_fence_wave();
-      }
-    for (int t = lane; t < seclen; t += 64) dbg_sort[off + sp + t] = off + (int)(K[t] & 0xffffffffu);
-  }
-  __syncthreads();
-  SR_STAMP();
-
-  // ---- greedy picks (SR:325-422).  The reference sorts each sector by curvature and walks the sorted list from the top (2
-  // sharp + 18 less-sharp picks) and from the bottom (4 flat picks), skipping points suppressed by earlier picks.  Walking a
-  // sorted list and taking the first eligible entry is the same as taking the arg-max (arg-min) over the eligible entries,
-  // and at most 24 entries are ever taken — so nothing is sorted: every lane keeps the curvatures of its sector points in
-  // registers (point t of the sector lives in lane t % 64, slot t / 64) with one eligibility bit each, and a pick is one
-  // wavefront arg-max (two DPP reductions: curvature bits, then index among the ties — descending (c, index) order for the
-  // sharp walk, ascending for the flat walk, exactly the sorted list's order).
-  //
-  // The sectors of a ring are walked in order by the reference and a pick's neighbour suppression can spill over the sector
-  // boundary (SR:353-376), so sector s + 1 formally depends on sector s.  The spill reaches at most 5 points and only
-  // matters if one of them would otherwise be selected, so all six sectors run at once (one wavefront each) without incoming
-  // marks; afterwards the boundaries are checked in order and a sector is redone — with the marks of its predecessor applied
-  // first — only when a spilled-on point had been selected.  Marks are clipped to the own sector while picking (a later
-  // sector must not disturb an earlier one); the full extents are applied at the end so that `picked` ends up exactly like
-  // cloudNeighborPicked.
-  // A redone sector does not start over: its picks are taken in priority order, so every pick made BEFORE the first one the new spill
-  // invalidates stands — the picks of both walks are kept in LDS, the kept ones are replayed (marks only, all at once, one lane each)
-  // and the walk resumes behind them.  On average half of the second pass; a spill that hits a flat pick keeps the whole sharp walk.
-  unsigned* cbits = (unsigned*)keys;      // [CAP] curvature bits of the sector points (a redo reads them back instead of 33 LDS reads per point)
-  constexpr int kPickSlots = kMaxLessSharpPerSect + kMaxFlatPerSect;
-  int* s_plist = iscratch + 64;                         // [kSectors][kPickSlots] local index of the walks' picks, in pick order
-  int* s_pcnt = s_plist + kSectors * kPickSlots;        // [kSectors][2] picks of the sharp / flat walk
-  auto run_sector_q = [&](auto kq_tag, int s, int in_hi, bool redo, int keep_sharp, bool sharp_final, int keep_flat) {
-    constexpr int kQ = decltype(kq_tag)::value;   // register slots per lane: sector length <= 64 kQ
-    // (the same in every lane: in scalar registers, so that what derives from them — the lane masks of suppress() — is scalar too)
-    const int sp_l = __builtin_amdgcn_readfirstlane(s_sp[s] - off), ep_l = __builtin_amdgcn_readfirstlane(s_ep[s] - off);
-    const int seclen = ep_l - sp_l + 1;
-    int* plist = s_plist + s * kPickSlots;
-    if (redo) {  // forget the previous result, then apply the predecessor's spill
-      for (int l = sp_l + lane; l <= ep_l; l += 64) { picked[l] = (l <= in_hi) ? 1 : 0; label[l] = 0; }
-      lds_fence_wave();
-    }
-    // A pick is a chain of dependent instructions on a wavefront that is (almost) alone on its SIMD — ~8 cycles each —, so the walk is
-    // written for few instructions per pick: the lane's candidates are kept PRE-MASKED (an ineligible slot holds the walk's neutral
-    // value: the lane's best is a max3 / min3 tree), the winner's local index travels with its suppression reach in one word (no LDS
-    // round trip for the reach), the lane that owns the winner is found by ballot (a second reduction only when two lanes tie), and the
-    // picks stay in registers (lane k: pick k) until the walk is over — labels, index lists and the pick list are written once, in parallel.
-    unsigned cb[kQ];                      // curvature bits of point sp_l + q * 64 + lane
-    unsigned pay[kQ];                     // its local index << 8 | reach byte
-    unsigned sharp_bits = 0, flat_bits = 0, elig = 0, inside = 0;
-#pragma unroll
-    for (int q = 0; q < kQ; q++) {
-      cb[q] = 0; pay[q] = 0;
-      if (q * 64 < seclen) {
-        const int t = q * 64 + lane;
-        if (t < seclen) {
-          const int i = sp_l + t;
-          inside |= 1u << q;
-          if (redo) {
-            cb[q] = cbits[i];
-          } else {
-            const float c0 = curvature(i);
-            if (dbg_curv) dbg_curv[off + i] = c0;
-            cb[q] = __float_as_uint(c0);   // c >= 0: the bit pattern orders like the value
-            cbits[i] = cb[q];
-          }
-          pay[q] = ((unsigned)i << 8) | (unsigned)reachb[i];
-          // SR:330 / SR:383 compare the f32 curvature with the double 0.1, which lies between two neighbouring floats (0.099999994 and
-          // 0.1f = 0.100000001): (double)c > 0.1 <=> c >= 0.1f and (double)c < 0.1 <=> c < 0.1f — no f64 convert and compare per point
-          const float c = __uint_as_float(cb[q]);
-          if (c >= 0.1f) sharp_bits |= 1u << q;
-          if (c < 0.1f) flat_bits |= 1u << q;
-          if (i > in_hi) elig |= 1u << q;
-        }
-      }
-    }
-    int* o_sharp = sharp_idx + (r * kSectors + s) * kMaxSharpPerSect;
-    int* o_less = less_sharp_idx + (r * kSectors + s) * kMaxLessSharpPerSect;
-    int* o_flat = flat_idx + (r * kSectors + s) * kMaxFlatPerSect;
-    int n_less = 0, n_flat = 0;
-    unsigned my_sharp = 0, my_flat = 0;   // lane k: pick k of the sharp / flat walk (local index << 8 | reach)
-    int leak_lo = INT_MAX, leak_hi = -1;
-    unsigned v[kQ];                       // the running walk's pre-masked candidates
-    // SR:353-376 around the winner, as far as the walk itself needs it: the (at most 11) covered points of the sector leave the
-    // candidates.  The marks themselves (cloudNeighborPicked) are written after the walk, by one lane per pick.
-    auto suppress = [&](unsigned pw, unsigned neutral) {
-      const int lf = (int)(pw >> 8);
-      const int lo_m = lf - (int)(pw & 15u), hi_m = lf + (int)((pw >> 4) & 15u);
-      const int tlo = max(lo_m - sp_l, 0), thi = min(hi_m - sp_l, seclen - 1);
-      const unsigned d = (unsigned)(lane - tlo), span = (unsigned)(thi - tlo);
-#pragma unroll
-      for (int q = 0; q < kQ; q++)
-        if (d + (unsigned)(q * 64) <= span) v[q] = neutral;
-    };
-    // the marks (clipped to the sector) and extents of picks [from, to) of a walk: lane k marks around pick k
-    auto apply_marks = [&](unsigned my, int from, int to) {
-      int lo_m = INT_MAX, hi_m = -1;
-      if (lane >= from && lane < to) {
-        const int lf = (int)(my >> 8);
-        lo_m = lf - (int)(my & 15u); hi_m = lf + (int)((my >> 4) & 15u);
-        for (int l = max(lo_m, sp_l); l <= min(hi_m, ep_l); l++) picked[l] = 1;
-      }
-      leak_lo = min(leak_lo, (int)wave_min_u32((unsigned)lo_m));
-      leak_hi = max(leak_hi, (int)wave_max_u32((unsigned)(hi_m + 1)) - 1);
-    };
-    // which of the lane's points no pick has marked (the walks themselves only keep v[] current)
-    auto refresh_elig = [&]() {
-      lds_fence_wave();
-#pragma unroll
-      for (int q = 0; q < kQ; q++)
-        if (((inside >> q) & 1u) && picked[sp_l + q * 64 + lane]) elig &= ~(1u << q);
-    };
-    // kept picks [first, first + n) of the pick list come back into the registers (lane k: pick k); the first n_marking of them mark
-    auto replay = [&](int first, int n, int n_marking, int sharp_walk) {
-      unsigned my = 0;
-      if (lane < n) { const int lf = plist[first + lane]; my = ((unsigned)lf << 8) | (unsigned)reachb[lf]; }
-      if (sharp_walk) my_sharp = my; else my_flat = my;
-      apply_marks(my, 0, n_marking);
-    };
-    // SR:327-378, descending curvature
-    if (keep_sharp > 0) { replay(0, keep_sharp, keep_sharp, 1); n_less = keep_sharp; }
-    if (!sharp_final) {
-      if (redo) refresh_elig();
-#pragma unroll
-      for (int q = 0; q < kQ; q++) v[q] = ((elig & sharp_bits) >> q) & 1u ? cb[q] : 0u;   // candidates have c > 0.1, i.e. non-zero bits
-      for (int picks = keep_sharp + 1; picks <= kMaxLessSharpPerSect; picks++) {
-        unsigned lb = v[0];
-#pragma unroll
-        for (int q = 1; q < kQ; q++) lb = max(lb, v[q]);
-        const unsigned mh = wave_max_u32(lb);
-        if (mh == 0) break;
-        unsigned pl = 0;
-#pragma unroll
-        for (int q = 0; q < kQ; q++) if (v[q] == mh) pl = pay[q];   // ascending: the higher index wins ties
-        const u64 tie = __ballot(lb == mh);
-        const unsigned pw = (tie & (tie - 1ull)) == 0ull ? (unsigned)__builtin_amdgcn_readlane((int)pl, __ffsll((long long)tie) - 1) : wave_max_u32(pl);
-        if (lane == n_less) my_sharp = pw;
-        n_less++;
-        suppress(pw, 0u);
-      }
-      apply_marks(my_sharp, keep_sharp, n_less);
-    }
-    // SR:380-422, ascending curvature
-    if (keep_flat > 0) { replay(kMaxLessSharpPerSect, keep_flat, min(keep_flat, kMaxFlatPerSect - 1), 0); n_flat = keep_flat; }
-    refresh_elig();
-#pragma unroll
-    for (int q = 0; q < kQ; q++) v[q] = ((elig & flat_bits) >> q) & 1u ? cb[q] : 0xffffffffu;   // (c < 0.1: never all ones)
-    for (int picks = keep_flat + 1;; picks++) {
-      unsigned lb = v[0];
-#pragma unroll
-      for (int q = 1; q < kQ; q++) lb = min(lb, v[q]);
-      const unsigned mh = wave_min_u32(lb);
-      if (mh == 0xffffffffu) break;
-      unsigned pl = 0xffffffffu;
-#pragma unroll
-      for (int q = kQ - 1; q >= 0; q--) if (v[q] == mh) pl = pay[q];   // descending: the lower index wins ties
-      const u64 tie = __ballot(lb == mh);
-      const unsigned pw = (tie & (tie - 1ull)) == 0ull ? (unsigned)__builtin_amdgcn_readlane((int)pl, __ffsll((long long)tie) - 1) : wave_min_u32(pl);
-      if (lane == n_flat) my_flat = pw;
-      n_flat++;
-      if (picks >= kMaxFlatPerSect) break;  // the 4th flat point is emitted but not suppressed (SR:390-394)
-      suppress(pw, 0xffffffffu);
-    }
-    apply_marks(my_flat, keep_flat, min(n_flat, kMaxFlatPerSect - 1));
-    // labels, index lists, pick list: one lane per pick
-    const int n_sharp = min(n_less, kMaxSharpPerSect);
-    if (lane < n_less) {
-      const int lf = (int)(my_sharp >> 8);
-      label[lf] = lane < kMaxSharpPerSect ? 2 : 1;
-      o_less[lane] = off + lf; plist[lane] = lf;
-      if (lane < n_sharp) o_sharp[lane] = off + lf;
-    }
-    if (lane < n_flat) { const int lf = (int)(my_flat >> 8); label[lf] = -1; o_flat[lane] = off + lf; plist[kMaxLessSharpPerSect + lane] = lf; }
-    lds_fence_wave();
-    if (lane == 0) {
-      S->sect_cnt[r][s][0] = n_sharp; S->sect_cnt[r][s][1] = n_less; S->sect_cnt[r][s][2] = n_flat;
-      s_leak_lo[s] = leak_lo; s_leak_hi[s] = leak_hi;
-      s_zone[s] = in_hi;
-      s_pcnt[2 * s] = n_less; s_pcnt[2 * s + 1] = n_flat;
-    }
-  };
-  auto run_sector = [&](int s, int in_hi, bool redo, int keep_sharp, bool sharp_final, int keep_flat) {
-    if (s_ep[s] - s_sp[s] + 1 <= 6 * 64) run_sector_q(std::integral_constant<int, 6>{}, s, in_hi, redo, keep_sharp, sharp_final, keep_flat);   // HDL-64E: ~330 points per sector
-    else run_sector_q(std::integral_constant<int, SECT / 64>{}, s, in_hi, redo, keep_sharp, sharp_final, keep_flat);
-  };
-  if (wave < kSectors) run_sector(wave, -1, false, 0, false, 0);
-  __syncthreads();
-  SR_STAMP();
-  // fixed point over the boundaries: a sector is redone when the spill it was computed with differs from its predecessors'
-  // current spill in a way that can matter.  Sector 0 never changes, so after round k sectors 0..k are final.
-  for (int round = 0; round < kSectors - 1; round++) {
-    if (tid == 0) *s_any = 0;
-    __syncthreads();
-    bool redo = false, sharp_final = false;
-    int in_hi = -1, keep_sharp = 0, keep_flat = 0;
-    if (wave >= 1 && wave < kSectors) {
-      const int sp_l = s_sp[wave] - off, ep_l = s_ep[wave] - off;
-      for (int q = 0; q < wave; q++) in_hi = max(in_hi, s_leak_hi[q]);  // a spill reaches 5 points: several sectors when they are tiny
-      in_hi = min(in_hi, ep_l);
-      if (in_hi < sp_l) in_hi = -1;
-      const int used = s_zone[wave];
-      if (in_hi > used) {        // the spill grew: matters only if a newly covered point (at most 5) had been selected
-        const int nl = s_pcnt[2 * wave], nf = s_pcnt[2 * wave + 1];
-        int lf = -1;
-        if (lane < kMaxLessSharpPerSect) { if (lane < nl) lf = s_plist[wave * kPickSlots + lane]; }
-        else if (lane < kPickSlots) { if (lane - kMaxLessSharpPerSect < nf) lf = s_plist[wave * kPickSlots + lane]; }
-        const unsigned long long hit = __ballot(lf > used && lf <= in_hi);   // (picks lie inside the sector, i.e. at or above sp_l)
-        redo = hit != 0ull;
-        if (redo) {   // everything picked before the first invalidated pick stands
-          const int k = __ffsll((long long)hit) - 1;
-          if (k < kMaxLessSharpPerSect) { keep_sharp = k; }
-          else { keep_sharp = nl; sharp_final = true; keep_flat = k - kMaxLessSharpPerSect; }
-        }
-        if (!redo && lane == 0) s_zone[wave] = in_hi;
-      } else if (in_hi < used) {  // the spill shrank: points that were blocked are free again — from the start
-        redo = true;
-      }
-      if (redo && lane == 0) *s_any = 1;
-    }
-    __syncthreads();  // every wavefront has read its predecessor's spill before anything is redone
-    if (*s_any == 0) break;
-    if (redo) run_sector(wave, in_hi, true, keep_sharp, sharp_final, keep_flat);
-    __syncthreads();
-  }
-  if (wave == 0) {
-    // full mark extents (beyond the own sector), as the reference leaves them behind
-    for (int s = 0; s < kSectors; s++) {
-      const int sp_l = s_sp[s] - off, ep_l = s_ep[s] - off;
-      const int lo_m = s_leak_lo[s], hi_m = s_leak_hi[s];
-      if (hi_m < 0) continue;
-      if (lane < 8) {
-        const int lb = lo_m + lane, lf = ep_l + 1 + lane;
-        if (lb < sp_l) picked[lb] = 1;
-        if (lf <= hi_m) picked[lf] = 1;
-      }
-    }
-  }
-  __syncthreads();
-  SR_STAMP();
-  if (dbg_picked) for (int l = tid; l < len; l += kRingThreads) { dbg_picked[off + l] = picked[l]; dbg_label[off + l] = label[l]; }
-
-  // ---- lessFlat (SR:424-430) + per-ring pcl::VoxelGrid leaf 0.2 (SR:433-437)
-  const int c_lo = 5, c_hi = len - 7;  // local range covered by the six sectors: [start, end-1]
-
-  // bounding box of the candidates (getMinMax3D)
-  float mn[3] = {3.4e38f, 3.4e38f, 3.4e38f}, mx[3] = {-3.4e38f, -3.4e38f, -3.4e38f};
-  int mycnt = 0;
-  for (int l = c_lo + tid; l <= c_hi; l += kRingThreads)
-    if (label[l] <= 0) {
-      mn[0] = fminf(mn[0], px[l]); mx[0] = fmaxf(mx[0], px[l]);
-      mn[1] = fminf(mn[1], py[l]); mx[1] = fmaxf(mx[1], py[l]);
-      mn[2] = fminf(mn[2], pz[l]); mx[2] = fmaxf(mx[2], pz[l]);
-      mycnt++;
-    }
-  for (int a = 0; a < 3; a++) { mn[a] = wave_fminmax<false>(mn[a]); mx[a] = wave_fminmax<true>(mx[a]); }   // (DPP row steps: no LDS crossbar)
-  mycnt = wave_sum_i32(mycnt);
-  float* wred = (float*)scan_tmp;  // [8 waves][6] + counts
-  if (lane == 0) {
-    for (int a = 0; a < 3; a++) { wred[wave * 8 + a] = mn[a]; wred[wave * 8 + 3 + a] = mx[a]; }
-    ((int*)wred)[wave * 8 + 6] = mycnt;
-  }
-  __syncthreads();
-  // (every lane folds the eight wavefronts' results itself — broadcast reads — instead of waiting for one lane behind a second barrier)
-  int ncand = 0;
-  for (int a = 0; a < 3; a++) { mn[a] = wred[a]; mx[a] = wred[3 + a]; }
-  for (int w = 0; w < kRingThreads / 64; w++) {
-    for (int a = 0; a < 3; a++) { mn[a] = fminf(mn[a], wred[w * 8 + a]); mx[a] = fmaxf(mx[a], wred[w * 8 + 3 + a]); }
-    ncand += ((int*)wred)[w * 8 + 6];
-  }
-  if (ncand == 0) return;
-  const float inv = 1.0f / 0.2f;  // inverse_leaf_size_
-  const long long dx = (long long)((mx[0] - mn[0]) * inv) + 1, dy = (long long)((mx[1] - mn[1]) * inv) + 1, dz = (long long)((mx[2] - mn[2]) * inv) + 1;
-  float4* out = ring_ds + (size_t)r * kMaxRingLen;
-  if (dx * dy * dz > (long long)INT_MAX) {
-    // PCL: "Leaf size is too small for the input dataset" -> output = input.  Keep input order.
-    for (int l = tid; l < len; l += kRingThreads) iscratch[l] = (l >= c_lo && l <= c_hi && label[l] <= 0) ? 1 : 0;
-    __syncthreads();
-    block_exclusive_scan(iscratch, len, scan_tmp);
-    for (int l = c_lo + tid; l <= c_hi; l += kRingThreads)
-      if (label[l] <= 0) out[iscratch[l]] = make_float4(px[l], py[l], pz[l], pi[l]);
-    if (tid == 0) S->ring_ds_cnt[r] = ncand;
-    return;
-  }
-  int min_b[3], div_b[3];
-  for (int a = 0; a < 3; a++) {
-    min_b[a] = (int)floorf(mn[a] * inv);
-    div_b[a] = (int)floorf(mx[a] * inv) - min_b[a] + 1;
-  }
-  // Consecutive ring points mostly fall into the same 0.2 m voxel, so the sort runs over RUNS (maximal stretches of
-  // consecutive candidates sharing a voxel), not points: key = (voxel index, first point of the run).  Sorted runs of one
-  // voxel are in input order and so are the points inside a run, hence summing run after run reproduces the
-  // input-order f32 sums of pcl::VoxelGrid exactly, with a network several times smaller.
-  // run key = voxel index : first point : last point (32 : 20 : 12 bits; a run is known by its first point, so the order is (voxel,
-  // first point)).  The run's head writes the voxel and its own position, the point behind its last point ORs in where the run ended:
-  // the centroid pass below then walks [first, last] without testing every point's voxel (a dependent LDS trip per point otherwise).
-  //
-  // Every wavefront takes a CONTIGUOUS stretch of the ring, 64 consecutive points per trip: a point's predecessor sits in the lane
-  // below, the run heads of a trip are one ballot word and a head's run number is a population count — no voxel array, no flag array,
-  // no workgroup scan (that was five passes over LDS behind five barriers; this is two passes behind two).
-  u64* K2 = keys;                      // [<= CAP] run keys
-  unsigned* K2w = (unsigned*)K2;       // [2 t] low word, [2 t + 1] high word
-  constexpr int kTrips = (CAP + kRingThreads - 1) / kRingThreads;
-  const int seg = ((len + kRingThreads - 1) / kRingThreads) * 64;   // points per wavefront (<= 64 kTrips)
-  const int seg0 = wave * seg;
-  auto voxel_of = [&](int l) -> int {  // -1: not a lessFlat candidate
-    if (l < c_lo || l > c_hi || label[l] > 0) return -1;
-    const int ijk0 = (int)(floorf(px[l] * inv) - (float)min_b[0]);
-    const int ijk1 = (int)(floorf(py[l] * inv) - (float)min_b[1]);
-    const int ijk2 = (int)(floorf(pz[l] * inv) - (float)min_b[2]);
-    return ijk0 + ijk1 * div_b[0] + ijk2 * div_b[0] * div_b[1];
-  };
-  int vidx[kTrips];
-  u64 headm[kTrips], pcandm[kTrips];   // trip's run heads / lanes whose predecessor is a candidate
-  int nheads = 0;
-  {
-    int carry = seg0 > 0 && seg0 - 1 < len ? voxel_of(seg0 - 1) : -2;   // the point in front of the stretch (-2: none)
-    carry = __builtin_amdgcn_readfirstlane(carry);
-#pragma unroll
-    for (int it = 0; it < kTrips; it++) {
-      vidx[it] = -1; headm[it] = 0ull; pcandm[it] = 0ull;
-      if (it * 64 < seg) {
-        const int l = seg0 + it * 64 + lane;
-        const int v = l < len ? voxel_of(l) : -1;
-        int pv = __shfl_up(v, 1);
-        if (lane == 0) pv = carry;
-        carry = __builtin_amdgcn_readlane(v, 63);
-        vidx[it] = v;
-        headm[it] = __ballot(v >= 0 && pv != v);
-        pcandm[it] = __ballot(pv >= 0);
-        nheads += __popcll(headm[it]);
-        if (l < CAP) K2[l] = 0ull;   // (run numbers never exceed point numbers: every key that will be ORed together starts from zero)
-      }
-    }
-  }
-  int* s_heads = scan_tmp + 64;        // [8] (behind the bounding-box slots: a slow wavefront may still be reading those)
-  if (lane == 0) s_heads[wave] = nheads;
-  __syncthreads();
-  int nrun = 0, running = 0;
-  for (int w = 0; w < kRingThreads / 64; w++) { const int t = s_heads[w]; running += w < wave ? t : 0; nrun += t; }
-  int P2 = 2;
-  while (P2 < nrun) P2 <<= 1;
-  for (int t = nrun + tid; t < P2 && t < CAP; t += kRingThreads) K2[t] = ~0ull;   // the sorting network's padding
-#pragma unroll
-  for (int it = 0; it < kTrips; it++) {
-    if (it * 64 < seg) {
-      const int l = seg0 + it * 64 + lane;
-      const int v = vidx[it];
-      const u64 hm = headm[it];
-      const bool head = (hm >> lane) & 1ull;
-      const int run = running + __popcll(hm & ((1ull << lane) - 1ull));   // heads in front of l
-      if (head) { K2w[2 * run + 1] = (unsigned)v; atomicOr(&K2w[2 * run], (unsigned)l << 12); }
-      if (((pcandm[it] >> lane) & 1ull) && (head || v < 0)) atomicOr(&K2w[2 * (run - 1)], (unsigned)(l - 1));   // l - 1 closed its run
-      running += __popcll(hm);
-    }
-  }
-  __syncthreads();
-  SR_STAMP();
-  // a stage with stride j <= 64 only moves data inside 128-element blocks that belong to one wavefront (64 consecutive
-  // compare-exchanges), so only the wide strides need a workgroup barrier
-  if (P2 > CAP) {
-    // More runs than the largest power of two the key array holds (only the small tier's 2 176-point rings can get here, with a
-    // voxel of its own for almost every point): rank by counting instead of padding the network to 4 096 keys.  Keys are unique.
-    constexpr int NQ = (CAP + kRingThreads - 1) / kRingThreads;
-    u64 mine[NQ];
-    int rk[NQ];
-#pragma unroll
-    for (int q = 0; q < NQ; q++) {
-      const int t = tid + q * kRingThreads;
-      mine[q] = t < nrun ? K2[t] : ~0ull;
-      int below = 0;
-      if (t < nrun) for (int e = 0; e < nrun; e++) below += K2[e] < mine[q];
-      rk[q] = below;
-    }
-    __syncthreads();
-#pragma unroll
-    for (int q = 0; q < NQ; q++) if (tid + q * kRingThreads < nrun) K2[rk[q]] = mine[q];
-  } else if (P2 < 128) {
-    for (int k = 2; k <= P2; k <<= 1)
-      for (int j = k >> 1; j > 0; j >>= 1) {
-        bitonic_stage(K2, P2, j, k, tid, kRingThreads);
-        const int next_j = j > 1 ? j >> 1 : k;  // first stride of the next merge level
-        if (j > 64 || next_j > 64) __syncthreads(); else lds_fence_wave();
-      }
-  } else if (P2 < 256 * (kRingThreads / 64)) {
-    // up to 1 024 keys: 128-key blocks (two keys per lane) keep all eight wavefronts busy; strides <= 64 run in registers, the strides >= 128
-    // go through LDS behind a workgroup barrier
-    bitonic_reg_stages(K2, P2, 2, 128, tid, kRingThreads);
-    __syncthreads();
-    for (int k = 256; k <= P2; k <<= 1) {
-      for (int j = k >> 1; j >= 128; j >>= 1) {
-        bitonic_stage(K2, P2, j, k, tid, kRingThreads);
-        __syncthreads();
-      }
-      bitonic_reg_stages(K2, P2, k, k, tid, kRingThreads);
-      __syncthreads();
-    }
-  } else {
-    // 2 048 keys and more: 256-key blocks (four keys per lane, one block per wavefront at 2 048); strides <= 128 run in registers, only the
-    // strides >= 256 — 6 of the 66 stages at 2 048 run keys — go through LDS (41.5 k -> 37 k cycles; at 1 024 keys the wider blocks would
-    // leave four wavefronts idle: 19 k -> 26 k)
-    bitonic_reg_stages4(K2, P2, 2, 256, tid, kRingThreads);
-    __syncthreads();
-    for (int k = 512; k <= P2; k <<= 1) {
-      for (int j = k >> 1; j >= 256; j >>= 1) {
-        bitonic_stage(K2, P2, j, k, tid, kRingThreads);
-        __syncthreads();
-      }
-      bitonic_reg_stages4(K2, P2, k, k, tid, kRingThreads);
-      __syncthreads();
-    }
-  }
-  __syncthreads();
-  SR_STAMP();
-  // voxel heads -> output rank, the same way (contiguous stretches of the sorted keys, ballot words, population counts), then the centroids
-  int nvox = 0;
-  {
-    const int qseg = ((nrun + kRingThreads - 1) / kRingThreads) * 64, q0 = wave * qseg;
-    u64 kreg[kTrips], hm[kTrips];
-    unsigned carry = q0 > 0 && q0 - 1 < nrun ? (unsigned)(K2[q0 - 1] >> 32) : 0xffffffffu;   // (no voxel has that index: idx <= INT_MAX)
-    int mine = 0;
-#pragma unroll
-    for (int it = 0; it < kTrips; it++) {
-      kreg[it] = 0ull; hm[it] = 0ull;
-      if (it * 64 < qseg) {
-        const int t = q0 + it * 64 + lane;
-        const u64 k0 = t < nrun ? K2[t] : ~0ull;
-        const unsigned vid = (unsigned)(k0 >> 32);
-        unsigned pv = (unsigned)__shfl_up((int)vid, 1);
-        if (lane == 0) pv = carry;
-        carry = (unsigned)__builtin_amdgcn_readlane((int)vid, 63);
-        kreg[it] = k0;
-        hm[it] = __ballot(t < nrun && vid != pv);
-        mine += __popcll(hm[it]);
-      }
-    }
-    int* s_vox = scan_tmp + 72;   // [8]
-    if (lane == 0) s_vox[wave] = mine;
-    __syncthreads();
-    int running = 0;
-    for (int w = 0; w < kRingThreads / 64; w++) { const int c = s_vox[w]; running += w < wave ? c : 0; nvox += c; }
-#pragma unroll
-    for (int it = 0; it < kTrips; it++) {
-      if (it * 64 < qseg) {
-        const int t = q0 + it * 64 + lane;
-        if ((hm[it] >> lane) & 1ull) {
-          const unsigned vid = (unsigned)(kreg[it] >> 32);
-          float sx = 0.f, sy = 0.f, sz = 0.f, si = 0.f;  // CentroidPoint<PointXYZI>: f32 sums in input order
-          int npt = 0;
-          u64 k = kreg[it];
-          for (int u = t;;) {
-            const int l0 = (int)((k >> 12) & 0xfffu), l1 = (int)(k & 0xfffu);
-            for (int l = l0; l <= l1; l++) { sx += px[l]; sy += py[l]; sz += pz[l]; si += pi[l]; }
-            npt += l1 - l0 + 1;
-            if (++u >= nrun) break;
-            k = K2[u];
-            if ((unsigned)(k >> 32) != vid) break;
-          }
-          const float cnt = (float)npt;
-          out[running + __popcll(hm[it] & ((1ull << lane) - 1ull))] = make_float4(sx / cnt, sy / cnt, sz / cnt, si / cnt);
-        }
-        running += __popcll(hm[it]);
-      }
-    }
-  }
-  if (tid == 0) S->ring_ds_cnt[r] = nvox;
-  SR_STAMP();
-  if (dbg_cyc && tid == 0) {
-    for (int q = 0; q < 7; q++) dbg_cyc[r * 8 + q] = q + 1 < nstamp ? tstamp[q + 1] - tstamp[q] : 0;
-    dbg_cyc[r * 8 + 7] = (long long)nrun | ((long long)nvox << 16) | ((long long)len << 32) | ((long long)ncand << 48);
-  }
-#undef SR_STAMP
-  };
-  // one workgroup per ring — or the catch-all: which rings are oversized (one load per lane, the same answer in every wavefront; normally
-  // none, and the launch ends here).  ONE call site: a second copy of the ring body costs the small tier 50 VGPRs, i.e. its second
-  // workgroup per CU.
-  static_assert(kMaxRings == 64, "one ring per lane");
-  if constexpr (!BIG_TIER) {
-    one_ring((int)blockIdx.x);   // (straight-line: a loop around the body costs this tier 50 VGPRs, i.e. its second workgroup per CU)
-  } else {
-    unsigned long long todo = 1ull << (blockIdx.x & 63);
-    if (gridDim.x != kMaxRings) todo = __ballot(S->ring_count[lane] > kRingCapSmall);
-    while (todo != 0ull) {
-      const int r = __ffsll((long long)todo) - 1;
-      todo &= todo - 1ull;
-      one_ring(r);
-      if (todo != 0ull) __syncthreads();   // the ring's LDS is no longer read
-    }
-  }
-}
-
-// ------------------------------------------------------------------------------------------------
-// The long ring tier (opt-in, vloam_config::max_ring_points > kMaxRingLen): rings of kMaxRingLen + 1 .. max_ring_points points, on handles that
-// asked for them.  Such a ring does not fit the LDS of a CU (~36 B per point in the tiers above, 590 KB at 16 384 points), so this tier keeps
-// its per-point arrays in HBM (SRBuffers::long_*, one region per ring and session; the points themselves are read from the ring-major cloud)
-// and only the reduction slots in LDS.  It is written for global memory rather than as a third instantiation of the LDS body: that body's
-// sector walks keep a sector in registers (211 VGPRs at the big tier's 682-point sectors; a 16 384-point ring has 2 729-point sectors) and its
-// run keys carry 12-bit point indices.  Here, as in the reference:
-//  - the six sectors are walked one after the other by wavefront 0, so a pick's neighbour suppression reaches into the next sector exactly as
-//    cloudNeighborPicked does (SR:353-376) and no boundary fixed point is needed.  A pick is the arg-max (sharp walk) / arg-min (flat walk)
-//    of (curvature, index) over the sector's eligible points, i.e. the first eligible entry of the sector sorted by (curvature, index),
-//    walked from the top or the bottom (the canonical order of the LDS tiers and of the oracle);
-//  - lessFlat's VoxelGrid(0.2) sorts one key per point (voxel : index, non-candidates last), so it takes any number of voxels, and sums every
-//    voxel's points in input order (CentroidPoint, f32).
-// Memory ordering: everything exchanged through these arrays stays inside the workgroup, i.e. on one CU behind one L1: between wavefronts
-// behind __syncthreads() (workgroup-scope release / acquire), between the lanes of wavefront 0 behind lds_fence_wave() — a workgroup-scope
-// fence over every address space (it waits for the wavefront's stores) and a wave barrier.  No other workgroup reads them during the launch;
-// the next launch that does (k_sr_compact: long_ds) is ordered behind this one on the stream.
-constexpr int kLongSlots = ((kMaxRingLenLong - 11 + kSectors - 1) / kSectors + 63) / 64;   // register slots per lane of a sector walk (2 729 points at 16 384)
-
-__global__ __launch_bounds__(kRingThreads) void k_sr_ring_long(const float4* __restrict__ cloud, FrameScalars* S, int* __restrict__ sharp_idx,
-                                                               int* __restrict__ less_sharp_idx, int* __restrict__ flat_idx, int cap, int kcap,
-                                                               u64* keys_all, int* iscr_all, unsigned char* bytes_all, float4* ds_all,
-                                                               float* __restrict__ dbg_curv, int* __restrict__ dbg_sort, int* __restrict__ dbg_picked,
-                                                               int* __restrict__ dbg_label, size_t ss) {
-  VL_SESSION(ss); RB(cloud); RB(S); RB(sharp_idx); RB(less_sharp_idx); RB(flat_idx); RB(keys_all); RB(iscr_all); RB(bytes_all); RB(ds_all);
-  RB(dbg_curv); RB(dbg_sort); RB(dbg_picked); RB(dbg_label);
-  __shared__ int scan_tmp[kRingThreads];
-  __shared__ float wred[kRingThreads / 64 * 8];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  auto one_ring = [&](const int r) {
-    const int len = S->ring_count[r], off = S->ring_off[r];
-    const int start = off + 5, end = off + len - 6;  // SR:278-280
-    if (len <= kMaxRingLen) return;                  // an LDS tier has done this ring
-    if (tid < kSectors * 3) (&S->sect_cnt[r][0][0])[tid] = 0;
-    if (tid == 0) S->ring_ds_cnt[r] = 0;
-    if (len > cap) { if (tid == 0) atomicOr(&S->error, kErrRingTooLong); return; }
-    if (end - start < 6) return;  // SR:314
-    const float4* p = cloud + off;
-    u64* keys = keys_all + (size_t)r * kcap;
-    int* iscr = iscr_all + (size_t)r * kcap;
-    float* curv = (float*)iscr;
-    unsigned char* picked = bytes_all + (size_t)r * 4 * cap;
-    signed char* label = (signed char*)(picked + cap);
-    unsigned char* gap = picked + 2 * cap;
-    unsigned char* reach = picked + 3 * cap;
-    float4* out = ds_all + (size_t)r * cap;
-
-    // gap[l] = 1 when dist2(p[l + 1], p[l]) > 0.05 (SR:353-376 stops there)
-    for (int l = tid; l < len; l += kRingThreads) {
-      picked[l] = 0; label[l] = 0;  // SR:305-306
-      bool g = true;
-      if (l + 1 < len) {
-        const float4 a = p[l], b = p[l + 1];
-        const float dx = b.x - a.x, dy = b.y - a.y, dz = b.z - a.z;
-        g = (double)(dx * dx + dy * dy + dz * dz) > 0.05;
-      }
-      gap[l] = g ? 1 : 0;
-    }
-    __syncthreads();
-    // curvature (SR:288-303) of every sector point and its suppression reach: how many of l-1 .. l-5 (low nibble) and of l+1 .. l+5 (high
-    // nibble) a pick at l marks
-    for (int l = 5 + tid; l <= len - 7; l += kRingThreads) {
-      float4 q[11];
-#pragma unroll
-      for (int k = 0; k < 11; k++) q[k] = p[l - 5 + k];
-      const float dX = q[0].x + q[1].x + q[2].x + q[3].x + q[4].x - 10 * q[5].x + q[6].x + q[7].x + q[8].x + q[9].x + q[10].x;
-      const float dY = q[0].y + q[1].y + q[2].y + q[3].y + q[4].y - 10 * q[5].y + q[6].y + q[7].y + q[8].y + q[9].y + q[10].y;
-      const float dZ = q[0].z + q[1].z + q[2].z + q[3].z + q[4].z - 10 * q[5].z + q[6].z + q[7].z + q[8].z + q[9].z + q[10].z;
-      const float c = dX * dX + dY * dY + dZ * dZ;
-      curv[l] = c;
-      if (dbg_curv) dbg_curv[off + l] = c;
-      int f = 0, k = 0;
-      while (f < 5 && !gap[l + f]) f++;
-      while (k < 5 && !gap[l - 1 - k]) k++;
-      reach[l] = (unsigned char)(k | (f << 4));
-    }
-    __syncthreads();
-    auto sect_lo = [&](int s) { return start + (end - start) * s / 6 - off; };            // SR:319, local
-    auto sect_hi = [&](int s) { return start + (end - start) * (s + 1) / 6 - 1 - off; };  // SR:320, local
-
-    // ---- debug only: the reference's std::sort of every sector (SR:323, ties by index), one sector after the other
-    if (dbg_sort) {
-      for (int s = 0; s < kSectors; s++) {
-        const int sp_l = sect_lo(s), seclen = sect_hi(s) - sp_l + 1;
-        int P = 256;
-        while (P < seclen) P <<= 1;
-        for (int t = tid; t < P; t += kRingThreads)
-          keys[t] = t < seclen ? ((u64)__float_as_uint(curv[sp_l + t]) << 32) | (unsigned)(sp_l + t) : ~0ull;   // c >= 0: bits order like the value
-        __syncthreads();
-        block_bitonic_sort_u64(keys, P, tid, kRingThreads);
-        for (int t = tid; t < seclen; t += kRingThreads) dbg_sort[off + sp_l + t] = off + (int)(keys[t] & 0xffffffffu);
-        __syncthreads();
-      }
-    }
-
-    // ---- greedy picks (SR:325-422), wavefront 0, sector after sector
-    if (wave == 0) {
-      for (int s = 0; s < kSectors; s++) {
-        const int sp_l = sect_lo(s), ep_l = sect_hi(s);
-        int* o_sharp = sharp_idx + (r * kSectors + s) * kMaxSharpPerSect;
-        int* o_less = less_sharp_idx + (r * kSectors + s) * kMaxLessSharpPerSect;
-        int* o_flat = flat_idx + (r * kSectors + s) * kMaxFlatPerSect;
-        unsigned v[kLongSlots];   // point sp_l + q * 64 + lane: its curvature bits while it is a candidate of the running walk, else the walk's neutral value
-        // the candidates of a walk: points no earlier pick has marked — of this sector or, over the seam, of the previous one
-        auto load = [&](bool sharp_walk) {
-          lds_fence_wave();   // this wavefront's marks are stored before they are read back
-#pragma unroll
-          for (int q = 0; q < kLongSlots; q++) {
-            const int i = sp_l + q * 64 + lane;
-            v[q] = sharp_walk ? 0u : 0xffffffffu;
-            if (i <= ep_l && !picked[i]) {
-              // SR:330 / SR:383: (double)c > 0.1 <=> c >= 0.1f, (double)c < 0.1 <=> c < 0.1f (0.1 lies between two neighbouring floats)
-              const float c = curv[i];
-              if (sharp_walk ? c >= 0.1f : c < 0.1f) v[q] = __float_as_uint(c);   // c >= 0: the bits order like the value
-            }
-          }
-        };
-        // SR:345-376 around the winner: cloudNeighborPicked in memory (one lane per marked point), and the marked points leave the walk
-        auto mark = [&](int w, unsigned neutral) {
-          const unsigned rb = reach[w];
-          const int lo_m = w - (int)(rb & 15u), hi_m = w + (int)(rb >> 4);
-          if (lane <= hi_m - lo_m) picked[lo_m + lane] = 1;
-#pragma unroll
-          for (int q = 0; q < kLongSlots; q++) {
-            const int i = sp_l + q * 64 + lane;
-            if (i >= lo_m && i <= hi_m) v[q] = neutral;
-          }
-        };
-        // SR:327-378, descending (curvature, index)
-        load(true);
-        int n_less = 0;
-        while (n_less < kMaxLessSharpPerSect) {
-          unsigned lb = v[0];
-          int qb = 0;
-#pragma unroll
-          for (int q = 1; q < kLongSlots; q++) if (v[q] >= lb) { lb = v[q]; qb = q; }   // ties: the higher index
-          const unsigned hi = wave_max_u32(lb);
-          if (hi == 0) break;   // (candidates have c >= 0.1f: non-zero bits)
-          const int w = (int)wave_max_u32(lb == hi ? (unsigned)(sp_l + qb * 64 + lane) : 0u);
-          if (lane == 0) {
-            label[w] = n_less < kMaxSharpPerSect ? 2 : 1;
-            o_less[n_less] = off + w;
-            if (n_less < kMaxSharpPerSect) o_sharp[n_less] = off + w;
-          }
-          n_less++;
-          mark(w, 0u);
-        }
-        // SR:380-422, ascending (curvature, index)
-        load(false);
-        int n_flat = 0;
-        while (n_flat < kMaxFlatPerSect) {
-          unsigned lb = v[0];
-          int qb = 0;
-#pragma unroll
-          for (int q = 1; q < kLongSlots; q++) if (v[q] < lb) { lb = v[q]; qb = q; }   // ties: the lower index
-          const unsigned hi = wave_min_u32(lb);
-          if (hi == 0xffffffffu) break;   // (c < 0.1f: never all ones)
-          const int w = (int)wave_min_u32(lb == hi ? (unsigned)(sp_l + qb * 64 + lane) : 0xffffffffu);
-          if (lane == 0) { label[w] = -1; o_flat[n_flat] = off + w; }
-          n_flat++;
-          if (n_flat >= kMaxFlatPerSect) break;  // the 4th flat point is emitted but not suppressed (SR:390-394)
-          mark(w, 0xffffffffu);
-        }
-        if (lane == 0) { S->sect_cnt[r][s][0] = min(n_less, kMaxSharpPerSect); S->sect_cnt[r][s][1] = n_less; S->sect_cnt[r][s][2] = n_flat; }
-      }
-    }
-    __syncthreads();
-    if (dbg_picked) for (int l = tid; l < len; l += kRingThreads) { dbg_picked[off + l] = picked[l]; dbg_label[off + l] = label[l]; }
-
-    // ---- lessFlat (SR:424-430) + per-ring pcl::VoxelGrid leaf 0.2 (SR:433-437), as in k_sr_ring
-    const int c_lo = 5, c_hi = len - 7;  // local range covered by the six sectors: [start, end-1]
-    float mn[3] = {3.4e38f, 3.4e38f, 3.4e38f}, mx[3] = {-3.4e38f, -3.4e38f, -3.4e38f};
-    int mycnt = 0;
-    for (int l = c_lo + tid; l <= c_hi; l += kRingThreads)
-      if (label[l] <= 0) {
-        const float4 q = p[l];
-        mn[0] = fminf(mn[0], q.x); mx[0] = fmaxf(mx[0], q.x);
-        mn[1] = fminf(mn[1], q.y); mx[1] = fmaxf(mx[1], q.y);
-        mn[2] = fminf(mn[2], q.z); mx[2] = fmaxf(mx[2], q.z);
-        mycnt++;
-      }
-    for (int a = 0; a < 3; a++) { mn[a] = wave_fminmax<false>(mn[a]); mx[a] = wave_fminmax<true>(mx[a]); }
-    mycnt = wave_sum_i32(mycnt);
-    if (lane == 0) {
-      for (int a = 0; a < 3; a++) { wred[wave * 8 + a] = mn[a]; wred[wave * 8 + 3 + a] = mx[a]; }
-      ((int*)wred)[wave * 8 + 6] = mycnt;
-    }
-    __syncthreads();
-    int ncand = 0;
-    for (int a = 0; a < 3; a++) { mn[a] = wred[a]; mx[a] = wred[3 + a]; }
-    for (int w = 0; w < kRingThreads / 64; w++) {
-      for (int a = 0; a < 3; a++) { mn[a] = fminf(mn[a], wred[w * 8 + a]); mx[a] = fmaxf(mx[a], wred[w * 8 + 3 + a]); }
-      ncand += ((int*)wred)[w * 8 + 6];
-    }
-    if (ncand == 0) return;
-    const float inv = 1.0f / 0.2f;  // inverse_leaf_size_
-    const long long dx = (long long)((mx[0] - mn[0]) * inv) + 1, dy = (long long)((mx[1] - mn[1]) * inv) + 1, dz = (long long)((mx[2] - mn[2]) * inv) + 1;
-    if (dx * dy * dz > (long long)INT_MAX) {
-      // PCL: "Leaf size is too small for the input dataset" -> output = input.  Keep input order.
-      for (int l = tid; l < len; l += kRingThreads) iscr[l] = (l >= c_lo && l <= c_hi && label[l] <= 0) ? 1 : 0;
-      __syncthreads();
-      block_exclusive_scan(iscr, len, scan_tmp);
-      for (int l = c_lo + tid; l <= c_hi; l += kRingThreads)
-        if (label[l] <= 0) out[iscr[l]] = p[l];
-      if (tid == 0) S->ring_ds_cnt[r] = ncand;
-      return;
-    }
-    int min_b[3], div_b[3];
-    for (int a = 0; a < 3; a++) {
-      min_b[a] = (int)floorf(mn[a] * inv);
-      div_b[a] = (int)floorf(mx[a] * inv) - min_b[a] + 1;
-    }
-    // key = voxel index : point, ~0 for a point that is no candidate (sorted behind the ncand candidates)
-    int P2 = 256;
-    while (P2 < len) P2 <<= 1;   // <= kcap
-    for (int l = tid; l < P2; l += kRingThreads) {
-      u64 key = ~0ull;
-      if (l >= c_lo && l <= c_hi && label[l] <= 0) {
-        const float4 q = p[l];
-        const int ijk0 = (int)(floorf(q.x * inv) - (float)min_b[0]);
-        const int ijk1 = (int)(floorf(q.y * inv) - (float)min_b[1]);
-        const int ijk2 = (int)(floorf(q.z * inv) - (float)min_b[2]);
-        key = ((u64)(unsigned)(ijk0 + ijk1 * div_b[0] + ijk2 * div_b[0] * div_b[1]) << 32) | (unsigned)l;
-      }
-      keys[l] = key;
-    }
-    __syncthreads();
-    block_bitonic_sort_u64(keys, P2, tid, kRingThreads);
-    // voxel heads -> output rank, then one lane per voxel sums its points in input order
-    for (int t = tid; t < ncand; t += kRingThreads) iscr[t] = (t == 0 || (keys[t] >> 32) != (keys[t - 1] >> 32)) ? 1 : 0;
-    __syncthreads();
-    const int nvox = block_exclusive_scan(iscr, ncand, scan_tmp);
-    for (int t = tid; t < ncand; t += kRingThreads) {
-      const unsigned vid = (unsigned)(keys[t] >> 32);
-      if (t > 0 && (unsigned)(keys[t - 1] >> 32) == vid) continue;
-      float sx = 0.f, sy = 0.f, sz = 0.f, si = 0.f;  // CentroidPoint<PointXYZI>: f32 sums in input order
-      int npt = 0;
-      for (int u = t; u < ncand; u++) {
-        const u64 k = keys[u];
-        if ((unsigned)(k >> 32) != vid) break;
-        const float4 q = p[(int)(k & 0xffffffffu)];
-        sx += q.x; sy += q.y; sz += q.z; si += q.w;
-        npt++;
-      }
-      const float cnt = (float)npt;
-      out[iscr[t]] = make_float4(sx / cnt, sy / cnt, sz / cnt, si / cnt);
-    }
-    if (tid == 0) S->ring_ds_cnt[r] = nvox;
-  };
-  // one workgroup per ring — or the catch-all: ONE workgroup per session walks the long rings (normally none: the launch ends here)
-  static_assert(kMaxRings == 64, "one ring per lane");
-  if (gridDim.x == kMaxRings) {
-    one_ring((int)blockIdx.x);
-  } else {
-    unsigned long long todo = __ballot(S->ring_count[lane] > kMaxRingLen);
-    while (todo != 0ull) {
-      const int r = __ffsll((long long)todo) - 1;
-      todo &= todo - 1ull;
-      one_ring(r);
-      __syncthreads();   // the reduction slots are no longer read
-    }
-  }
-}
-
-// ------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void k_sr_compact(const float4* __restrict__ cloud, FrameScalars* S, const int* __restrict__ sharp_idx,
                                                     const int* __restrict__ less_sharp_idx, const int* __restrict__ flat_idx,
                                                     const float4* __restrict__ ring_ds, float4* __restrict__ sharp,
@@ -1448,19 +464,12 @@ void sr_adopt_launch(hipStream_t st, const SRBuffers& b, int n_full, int n_sharp
 }
 
 // ------------------------------------------------------------------------------------------------
-template <int CAP, int SECT>
-static size_t sr_ring_smem_bytes() {
-  return sizeof(float) * 4 * CAP + sr_ring_keys_bytes<CAP, SECT>() + sizeof(int) * (CAP + kRingThreads) + 4 * CAP + 64 * sizeof(int);
-}
-static_assert(kRingCapSmall % 4 == 0 && 2 * (sizeof(float) * 4 * kRingCapSmall + (size_t)12 * kRingCapSmall + sizeof(int) * (kRingCapSmall + kRingThreads) +
-              4 * kRingCapSmall + 64 * sizeof(int)) <= 160 * 1024, "two small-tier rings must fit the 160 KB of LDS of one CU");
-
 hipError_t sr_init() {
   hipError_t e = hipFuncSetAttribute((const void*)k_sr_ring<kRingCapSmall, kSectCapSmall, false>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                     (int)sr_ring_smem_bytes<kRingCapSmall, kSectCapSmall>());
+                                     (int)SrRingLds<kRingCapSmall, kSectCapSmall>::bytes);
   if (e != hipSuccess) return e;
   return hipFuncSetAttribute((const void*)k_sr_ring<kMaxRingLen, kSectCap, true>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                             (int)sr_ring_smem_bytes<kMaxRingLen, kSectCap>());   // (k_sr_ring_long: static LDS only)
+                             (int)SrRingLds<kMaxRingLen, kSectCap>::bytes);   // (k_sr_ring_long: static LDS only)
 }
 
 hipError_t sr_launch(hipStream_t st, const SRBuffers& b, const BatchIn& bi, Sess se, int N_SCANS, float min_range, int debug_level, ProfHook* ph, hipEvent_t done,
@@ -1502,13 +511,13 @@ hipError_t sr_launch(hipStream_t st, const SRBuffers& b, const BatchIn& bi, Sess
   const bool big_launch = big_tier || long_tier || catchall != 0;
   const bool long_launch = has_long && (long_tier || catchall != 0);
   VLOAM_LAUNCH(ph, kKSrRing, st, (k_sr_ring<kRingCapSmall, kSectCapSmall, false>), dim3(kMaxRings, 1, Z), dim3(kRingThreads),
-               (sr_ring_smem_bytes<kRingCapSmall, kSectCapSmall>()), st, b.cloud, b.S, b.sharp_idx, b.less_sharp_idx,
+               (SrRingLds<kRingCapSmall, kSectCapSmall>::bytes), st, b.cloud, b.S, b.sharp_idx, b.less_sharp_idx,
                b.flat_idx, b.ring_ds, debug ? b.dbg_curv : nullptr, debug ? b.dbg_sort : nullptr, debug ? b.dbg_picked : nullptr,
                debug ? b.dbg_label : nullptr, stamps ? b.dbg_cyc : nullptr, ring_watch, big_launch ? 1 : 0, se.ss);
   // the full big tier while rings near the small tier's capacity are around, else its one-workgroup catch-all
   if (big_launch)
     VLOAM_LAUNCH(ph, kKSrRingBig, st, (k_sr_ring<kMaxRingLen, kSectCap, true>), dim3(big_tier ? kMaxRings : 1, 1, Z), dim3(kRingThreads),
-                 (sr_ring_smem_bytes<kMaxRingLen, kSectCap>()), st, b.cloud, b.S, b.sharp_idx, b.less_sharp_idx,
+                 (SrRingLds<kMaxRingLen, kSectCap>::bytes), st, b.cloud, b.S, b.sharp_idx, b.less_sharp_idx,
                  b.flat_idx, b.ring_ds, debug ? b.dbg_curv : nullptr, debug ? b.dbg_sort : nullptr, debug ? b.dbg_picked : nullptr,
                  debug ? b.dbg_label : nullptr, stamps ? b.dbg_cyc : nullptr, ring_watch, long_launch ? 1 : 0, se.ss);
   if (long_launch)
