@@ -887,7 +887,7 @@ vloam_status vloam_place_time_query(vloam_handle* h, const vloam_place_query_opt
  *   the clouds hold is known only after keying: when they exceed 60 % of a table's slots (or a probe chain reaches its bound) the call returns
  *   VLOAM_ERR_CAPACITY naming the table, the handle carries the sticky map-full error a sweep would have raised (vloam_sync reports it) and is
  *   finished, as after such a sweep.
- * Not offered: batched handles; importing into a handle that has taken sweeps (merging into a live map); un-merged raw points (an export that
+ * Not offered: batched handles; importing into a handle that has taken sweeps (vloam_map_merge below folds clouds into a live map); un-merged raw points (an export that
  *   holds several points of one voxel comes back as their centroid); normals, covariances or any per-point attribute beyond intensity. */
 typedef struct vloam_map_import_options {
   int struct_size;            /* sizeof as compiled */
@@ -909,6 +909,68 @@ vloam_status vloam_map_import(vloam_handle* h, const vloam_map_import_options* o
                               const float* surf_xyzi4, long long n_surf, vloam_map_import_result* out);
 vloam_status vloam_map_import_device(vloam_handle* h, const vloam_map_import_options* o, const void* d_corner, long long n_corner,
                                      const void* d_surf, long long n_surf, void* d_result);
+
+/* Map merge: two point clouds of ANOTHER map — its corner map and its surf map, packed (x, y, z, intensity), e.g. the files of a --save-map
+ * directory or vloam_get_map_kind(h2, 0 / 1) of another handle — are folded into the voxel map of a handle that is live (or fresh), given the
+ * transform between the two maps (vloam_place_query and vloam_map_relocalize find it: where today's drive sits in yesterday's map).  One map out
+ * of two sessions.  Opt-in by calling: a handle that never merges allocates and launches nothing of this, and no kernel of a sweep changes.
+ *   1. Transform.  Every point whose four floats are finite goes into this map's frame in f64 from its f32 components: q_map_src is normalised
+ *      and R formed from it on the host, as vloam_map_carve forms its poses; each output component is ((R_r0*x + R_r1*y) + R_r2*z) + t_r, every
+ *      operation rounded on its own, then rounded to f32.  Intensity is unchanged.  With q = (0, 0, 0, 1) and t = 0 the point is taken as it
+ *      is: an exported map goes in bit for bit.
+ *   2. Keying.  The transformed point gets the cube and the voxel the mapping's own insert would give it at its kind's leaf, against the
+ *      handle's CURRENT window offsets (step 3 of vloam_map_import).  A point whose cube lies outside the window (or outside the voxel key's
+ *      range) is dropped and counted in n_outside_window.  The window does not move, the pose does not change, and no trajectory row, sweep
+ *      count or odometry state is touched.  (A handle that never placed its window — no sweep mapped, nothing imported or restored — gets the
+ *      default window and the identity pose, as from vloam_map_import at the identity, and from then on counts as one that imported.)
+ *   3. Fold, per voxel and kind: what the reference holds after appending the points to the cube's cloud and re-filtering that cube
+ *      (laser_mapping.cpp:654-659, 689-702).  A voxel without a live record: the f32 sum of its new points in INPUT order, every component
+ *      divided by (float)n, one map point (vloam_map_import's rule; a purged record of the same key is reused).  A voxel that holds a merged
+ *      map point: that centroid, plus the new points in input order, divided by (float)(1 + n), one map point; the cube's point count is
+ *      unchanged.  A voxel that holds un-merged raw points (its cube was outside the valid 5 x 5 x 3 block when they arrived): untouched, its new
+ *      points are dropped and counted in n_skipped_raw, as vloam_map_carve skips such voxels.  New voxels get their occupancy block, their
+ *      cube's point count and the table counters that a handle has which inserted them itself.
+ *      The result is a function of the tables' state, the two arrays and the options alone, bit for bit from run to run (no floating-point atomics).
+ *   4. Dry run (apply == 0): lookups only.  n_in, n_new_points, n_hit_points, n_skipped_raw, n_outside_window and n_nonfinite are those of
+ *      the applied call; nothing the sequence owns is written.  n_new_points bounds the records the applied call creates.
+ *   5. Order.  Both forms first do what vloam_sync does (a host sweep that vloam_process_scan deferred is flushed and mapped first; a sticky
+ *      error is reported as there), run on the mapping stream with temporary allocations only, wait for that stream and free them before they
+ *      return.  The device form takes device addresses (clouds and a vloam_map_merge_result) and drops non-finite points, counted in
+ *      n_nonfinite, where the host form refuses them.
+ * Refusals, options first and before the handle is looked at (VLOAM_ERR_INVALID, each with its own vloam_last_error()): null options,
+ *   struct_size, apply outside 0 .. 1, reserved != 0, a non-finite component of q or t, a quaternion whose norm is off 1 by more than 1e-6, a
+ *   negative count, more than 16777216 points of a kind, a null cloud with a positive count, a null result, host form only: a non-finite float in
+ *   a cloud.  Then the handle: null (VLOAM_ERR_INVALID); with_mapping == 0 (VLOAM_ERR_ORDER); n_sessions > 1 (VLOAM_ERR_INVALID); a stage-wise
+ *   sweep in progress (VLOAM_ERR_ORDER).  After any refusal the handle is unchanged and usable.
+ * Capacity: a growable handle (vloam_map_options::grow) first steps its tables to the size its growth bound asks for with live records + n_in
+ *   of each kind as the bound on records (apply only), as vloam_map_import does on empty tables.  A fixed handle cannot be refused up front —
+ *   how many NEW voxels the clouds bring is known only after the lookups (n_new_points of a dry run bounds them): when the live records
+ *   exceed 60 % of a table's slots (or a probe chain reaches its bound) the call returns VLOAM_ERR_CAPACITY naming the table, the handle
+ *   carries the sticky map-full error a sweep would have raised (vloam_sync reports it) and is finished, as after such a sweep.
+ * Not offered: batched handles; collapsing raw voxels; merging place databases or trajectories; estimating the transform (vloam_map_relocalize
+ *   does). */
+typedef struct vloam_map_merge_options {   /* 72 bytes: 4 ints, then 7 doubles */
+  int struct_size;            /* sizeof as compiled */
+  int apply;                  /* 1 merge (default), 0 dry run */
+  int reserved[2];            /* 0 */
+  double q_map_src[4];        /* (x, y, z, w), unit within 1e-6; default identity: this map <- the clouds' frame */
+  double t_map_src[3];        /* default 0 */
+} vloam_map_merge_options;
+typedef struct vloam_map_merge_result {    /* 120 bytes: 14 long long, then 2 ints; [corner, surf] */
+  long long n_in[2];               /* points given */
+  long long n_new_points[2];       /* points whose voxel had no live record */
+  long long n_hit_points[2];       /* points whose voxel held a merged map point (overlap = n_hit_points / n_in) */
+  long long n_skipped_raw[2];      /* points whose voxel holds un-merged raw points: dropped */
+  long long n_outside_window[2];   /* dropped: cube outside the 21 x 21 x 11 window (or outside the key range) */
+  long long n_nonfinite[2];        /* dropped by the device form; the host form refuses instead */
+  long long n_new_voxels[2];       /* apply only, 0 in a dry run: map points (voxel records) created */
+  int max_per_voxel[2];            /* apply only: most points of the call folded into one map point */
+} vloam_map_merge_result;
+void vloam_default_map_merge_options(vloam_map_merge_options* o);   /* apply, identity, zero */
+vloam_status vloam_map_merge(vloam_handle* h, const vloam_map_merge_options* o, const float* corner_xyzi4, long long n_corner,
+                             const float* surf_xyzi4, long long n_surf, vloam_map_merge_result* out);
+vloam_status vloam_map_merge_device(vloam_handle* h, const vloam_map_merge_options* o, const void* d_corner, long long n_corner,
+                                    const void* d_surf, long long n_surf, void* d_result);
 
 /* Timing of the last vloam_sync()ed scans: HIP-event milliseconds accumulated per stage
  * {scanRegistration, laserOdometry, laserMapping, vo} and number of scans covered. */

@@ -229,6 +229,12 @@ def main():
                     help="after the last sweep, before --save-map: remove the map voxels that the run's last N_LAST_SWEEPS sweeps (at most 16) see through "
                          "under their mapping poses and none of them confirms (vloam_map_carve, apply; MIN_VOTES sweeps must see through, default 1) — "
                          "what a parked car or a pedestrian left in the map; the removed points are written as OUT/carved.npy")
+    ap.add_argument("--merge-map", metavar="DIR", help="after the last sweep (or right after --load-map / --resume when the input has no further sweep), before --carve and "
+                                                       "--save-map: fold DIR/corner.npy and DIR/surf.npy, a --save-map directory of ANOTHER run, into the live map "
+                                                       "(vloam_map_merge); the result record is printed and appended to --metrics as one more JSON line {\"map_merge\": ...}")
+    ap.add_argument("--merge-pose", metavar="\"qx qy qz qw tx ty tz\"", help="with --merge-map: this run's map <- the merged map's frame (default: the identity); "
+                                                                             "--localize-only --relocalize of a sweep of this run against DIR finds it")
+    ap.add_argument("--merge-dry-run", action="store_true", help="with --merge-map: look up only (apply = 0): the overlap is reported, the map stays as it is")
     ap.add_argument("--load-map", metavar="DIR", help="import DIR/corner.npy and DIR/surf.npy as the map of the fresh handle before the first sweep (vloam_map_import); "
                                                       "with --localize-only as --resume: every sweep is localised against the imported map, which is never updated")
     ap.add_argument("--start-pose", metavar="\"qx qy qz qw tx ty tz\"", help="with --load-map: the map<-odometry transform the sequence starts with "
@@ -302,6 +308,15 @@ def main():
         if a.localize_only or a.vloam:
             sys.exit("--carve cleans the map of a LiDAR run that maps: not with --localize-only or --vloam")
         a.carve = (int(w[0]), int(w[1]) if len(w) == 2 else 1)
+    if (a.merge_pose or a.merge_dry_run) and not a.merge_map:
+        sys.exit("--merge-pose / --merge-dry-run belong to --merge-map")
+    if a.merge_map and (a.localize_only or a.vloam):
+        sys.exit("--merge-map folds a map into the map of a LiDAR run that maps: not with --localize-only or --vloam")
+    if a.merge_pose:
+        w = a.merge_pose.split()
+        if len(w) != 7:
+            sys.exit("--merge-pose \"qx qy qz qw tx ty tz\": seven numbers")
+        a.merge_pose = [float(v) for v in w]
     if a.resume and a.load_map:
         sys.exit("--resume and --load-map both fill a fresh handle: choose one")
     if a.start_pose and not a.load_map:
@@ -443,6 +458,17 @@ def main():
         if count + 1 == save_at:
             with open(a.save_checkpoint, "wb") as f:
                 f.write(hd.checkpoint())
+    if a.merge_map:   # one map out of two runs (vloam_map_merge): behind the sweeps, in front of --carve / --save-map
+        mp = a.merge_pose or [0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0]
+        res = hd.map_merge(np.load(os.path.join(a.merge_map, "corner.npy")), np.load(os.path.join(a.merge_map, "surf.npy")), q=mp[:4], t=mp[4:],
+                           apply=not a.merge_dry_run)
+        rec = {k: [int(x) for x in v] for k, v in res.items()}
+        rec.update(dir=a.merge_map, pose=mp, apply=not a.merge_dry_run)
+        print("%s %s: %d / %d corner / surf points onto map points, %d / %d into %d / %d new voxels, %d / %d in raw voxels, %d / %d outside the window" % (
+            "would merge" if a.merge_dry_run else "merged", a.merge_map, rec["n_hit_points"][0], rec["n_hit_points"][1], rec["n_new_points"][0], rec["n_new_points"][1],
+            rec["n_new_voxels"][0], rec["n_new_voxels"][1], rec["n_skipped_raw"][0], rec["n_skipped_raw"][1], rec["n_outside_window"][0], rec["n_outside_window"][1]))
+        if mf:
+            mf.write(json.dumps({"map_merge": rec}) + "\n")
     if mf:
         mf.close()
     if a.sweep_log:

@@ -143,6 +143,17 @@ MAP_IMPORT_RESULT_DTYPE = np.dtype([
     ("max_per_voxel", "<i4", (2,)), ("center_cube", "<i4", (3,)), ("pad", "<i4")])
 
 
+class MapMergeOptions(C.Structure):
+    """vloam_map_merge_options (c_api.h; vloam_map_merge / vloam_map_merge_device)."""
+    _fields_ = [("struct_size", C.c_int), ("apply", C.c_int), ("reserved", C.c_int * 2), ("q_map_src", C.c_double * 4), ("t_map_src", C.c_double * 3)]
+
+
+# vloam_map_merge_result (c_api.h): 14 long long then 2 ints, 120 bytes; the pairs are [corner, surf]
+MAP_MERGE_RESULT_DTYPE = np.dtype([
+    ("n_in", "<i8", (2,)), ("n_new_points", "<i8", (2,)), ("n_hit_points", "<i8", (2,)), ("n_skipped_raw", "<i8", (2,)),
+    ("n_outside_window", "<i8", (2,)), ("n_nonfinite", "<i8", (2,)), ("n_new_voxels", "<i8", (2,)), ("max_per_voxel", "<i4", (2,))])
+
+
 class CarveOptions(C.Structure):
     """vloam_carve_options (c_api.h; vloam_map_carve / vloam_map_carve_device)."""
     _fields_ = [("struct_size", C.c_int), ("kind_mask", C.c_int), ("rows", C.c_int), ("cols", C.c_int), ("elev_min_deg", C.c_float),
@@ -1095,6 +1106,44 @@ class Handle:
         res = torch.zeros(MAP_IMPORT_RESULT_DTYPE.itemsize, dtype=torch.uint8, device=next((c.device for c in (corner, surf) if c is not None), "cuda"))
         self._chk(self.L.vloam_map_import_device(self.h, C.byref(opt), ptr[0], C.c_longlong(n[0]), ptr[1], C.c_longlong(n[1]), C.c_void_p(res.data_ptr())))
         return self._import_result(res.cpu().numpy().view(MAP_IMPORT_RESULT_DTYPE))
+
+    def _merge_options(self, q, t, apply):
+        opt = MapMergeOptions()
+        self.L.vloam_default_map_merge_options(C.byref(opt))
+        if q is not None:
+            opt.q_map_src[:] = [float(v) for v in q]
+        if t is not None:
+            opt.t_map_src[:] = [float(v) for v in t]
+        opt.apply = int(apply)
+        return opt
+
+    @staticmethod
+    def _merge_result(out):
+        return {k: out[0][k].copy() for k in MAP_MERGE_RESULT_DTYPE.names}
+
+    def map_merge(self, corner, surf, q=None, t=None, apply=True):
+        """vloam_map_merge: corner / surf (float32 [n, 4]: x, y, z, intensity in ANOTHER map's frame, e.g. a --save-map directory's files; None:
+        empty) are folded into this handle's live map under (q xyzw, t): this map <- the clouds' frame (None: identity / zero).  Points of one
+        voxel join the voxel's map point in input order; apply=False looks up only.  Returns the fields of vloam_map_merge_result as a dict."""
+        opt = self._merge_options(q, t, apply)
+        c, s = self._cloud_arg(corner), self._cloud_arg(surf)
+        out = np.zeros(1, dtype=MAP_MERGE_RESULT_DTYPE)
+        self._chk(self.L.vloam_map_merge(self.h, C.byref(opt), c[1], C.c_longlong(c[2]), s[1], C.c_longlong(s[2]), _fp(out)))
+        return self._merge_result(out)
+
+    def map_merge_device(self, corner, surf, q=None, t=None, apply=True):
+        """vloam_map_merge_device: the same with torch tensors on the device (float32 [n, 4], or None); points with a non-finite float are
+        dropped and counted in n_nonfinite, where map_merge() refuses them.  Returns the result as a dict."""
+        import torch
+        opt = self._merge_options(q, t, apply)
+        ptr, n = [None, None], [0, 0]
+        for k, c in enumerate((corner, surf)):
+            if c is not None and c.shape[0] > 0:
+                assert c.is_cuda and c.is_contiguous() and c.dtype == torch.float32 and c.shape[-1] == 4
+                ptr[k], n[k] = C.c_void_p(c.data_ptr()), int(c.shape[0])
+        res = torch.zeros(MAP_MERGE_RESULT_DTYPE.itemsize, dtype=torch.uint8, device=next((c.device for c in (corner, surf) if c is not None), "cuda"))
+        self._chk(self.L.vloam_map_merge_device(self.h, C.byref(opt), ptr[0], C.c_longlong(n[0]), ptr[1], C.c_longlong(n[1]), C.c_void_p(res.data_ptr())))
+        return self._merge_result(res.cpu().numpy().view(MAP_MERGE_RESULT_DTYPE))
 
     def _carve_options(self, apply, **kw):
         opt = CarveOptions()

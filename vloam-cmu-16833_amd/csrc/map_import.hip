@@ -21,16 +21,9 @@
 #include <math.h>
 #include <string.h>
 #include "map_kernels.h"
-#include "map_device.h"
-#include "map_table.h"
-#include "bitonic.h"
+#include "map_cloud_dev.h"   // what this chain shares with map_merge.hip: keying, scan, the three ordering paths, the input-order fold
 
 namespace vloam {
-
-constexpr int kImportLaneSort = 32;     // voxels of up to this many points are ordered and folded by one lane
-constexpr int kImportLdsSort = 4096;    // ... up to this many by one workgroup in LDS
-constexpr int kImportMaxGrid = 2048;    // k_map_grow's geometry: 256 CUs x 8 workgroups of 4 wavefronts, grid-stride beyond
-constexpr float kImportReach = 1.0e6f;  // coordinates beyond this (metres) are outside any window: the cube arithmetic below stays inside int
 
 struct ImportPose { double q[4], t[3]; };   // by value: the host's transform needs no upload
 struct ImportCtr { int n_vox[2]; int n_big[2]; };
@@ -39,26 +32,8 @@ __global__ __launch_bounds__(64) void k_map_import_prepare(MapState* ms, MapFram
                                                            ImportCtr* ctr, vloam_map_import_result* res) {
   if (threadIdx.x != 0) return;
   MapState s = *ms;
-  for (int k = 0; k < 4; k++) s.q_wmap_wodom[k] = pose.q[k];
-  for (int k = 0; k < 3; k++) s.t_wmap_wodom[k] = pose.t[k];
-  // LaserMapping::input LM:182-195 with the odometry pose of a fresh handle (identity): q_w_curr = q_wmap_wodom * q_wodom_curr, t_w_curr = q_wmap_wodom * t_wodom_curr + t_wmap_wodom
-  double q[4], t[3];
-  dquat_mul(s.q_wmap_wodom, s.q_wodom_curr, q);
-  dquat_rot(s.q_wmap_wodom, s.t_wodom_curr, t);
-  for (int k = 0; k < 3; k++) t[k] = t[k] + s.t_wmap_wodom[k];
-  for (int k = 0; k < 4; k++) s.parameters[k] = q[k];
-  for (int k = 0; k < 3; k++) s.parameters[4 + k] = t[k];
-  // LM:207-216, LM:218-402: every cube is empty, so the six while loops move the centre offsets only
-  int cen[3] = {s.cenW, s.cenH, s.cenD};
-  int cI = cube_abs(t[0]) + cen[0], cJ = cube_abs(t[1]) + cen[1], cK = cube_abs(t[2]) + cen[2];
-  while (cI < 3) { cI++; cen[0]++; }
-  while (cI >= kCubeW - 3) { cI--; cen[0]--; }
-  while (cJ < 3) { cJ++; cen[1]++; }
-  while (cJ >= kCubeH - 3) { cJ--; cen[1]--; }
-  while (cK < 3) { cK++; cen[2]++; }
-  while (cK >= kCubeD - 3) { cK--; cen[2]--; }
-  s.centerCube[0] = cI; s.centerCube[1] = cJ; s.centerCube[2] = cK;
-  s.cenW = cen[0]; s.cenH = cen[1]; s.cenD = cen[2];
+  cloud_place_start(s, pose.q, pose.t);
+  const int cen[3] = {s.cenW, s.cenH, s.cenD};
   *ms = s;
   for (int k = 0; k < 2; k++) { fr->n_deferred[k] = 0; fr->n_newraw[k] = 0; }
   for (int k = 0; k < 4; k++) { stats0[k] = 0; stats1[k] = 0; }
@@ -72,7 +47,7 @@ __global__ __launch_bounds__(64) void k_map_import_prepare(MapState* ms, MapFram
   *res = r;
 }
 
-// An own text of k_map_insert's keying lines (map_kernels.hip): f64 cube test on the f32 point, f32 voxel index, pack_key
+// keying: cloud_key (map_cloud_dev.h); find-or-insert with the table's CAS and probe bound
 __global__ __launch_bounds__(256) void k_map_import_key(const float4* __restrict__ pts, int n, int kind, VoxelTable T, float inv, const MapState* __restrict__ ms,
                                                         MapFrame* fr, int* __restrict__ slot_of, int* __restrict__ vox_slot, ImportCtr* ctr,
                                                         vloam_map_import_result* res) {
@@ -83,77 +58,37 @@ __global__ __launch_bounds__(256) void k_map_import_key(const float4* __restrict
     if (i >= n) continue;
     const float4 p = pts[i];
     int found = -1;
-    if (!(isfinite(p.x) && isfinite(p.y) && isfinite(p.z) && isfinite(p.w))) n_bad++;
-    else if (!(fabsf(p.x) < kImportReach && fabsf(p.y) < kImportReach && fabsf(p.z) < kImportReach)) n_out++;
+    u64 key;
+    if (!cloud_finite(p)) n_bad++;
+    else if (!cloud_key(p, inv, cW, cH, cD, &key)) n_out++;
     else {
-      const int Ai = cube_abs((double)p.x), Aj = cube_abs((double)p.y), Ak = cube_abs((double)p.z);
-      const int wi = Ai + cW, wj = Aj + cH, wk = Ak + cD;   // == cubeI, cubeJ, cubeK of LM:643-652
-      const int lx = (int)floorf(p.x * inv) - cube_voxel_base(Ai, inv), ly = (int)floorf(p.y * inv) - cube_voxel_base(Aj, inv),
-                lz = (int)floorf(p.z * inv) - cube_voxel_base(Ak, inv);
-      if (wi < 0 || wi >= kCubeW || wj < 0 || wj >= kCubeH || wk < 0 || wk >= kCubeD) n_out++;   // LM:654-655
-      else if ((unsigned)lx > (unsigned)kVoxMax || (unsigned)ly > (unsigned)kVoxMax || (unsigned)lz > (unsigned)kVoxMax || !cube_in_key_range(Ai, Aj, Ak)) n_out++;
-      else {
-        const u64 key = pack_key(Ai, Aj, Ak, lx, ly, lz);
-        unsigned s = (unsigned)mix64(key) & T.mask;
-        for (int probe = 0; probe < kMaxProbe; probe++, s = (s + 1) & T.mask) {
-          const u64 old = atomicCAS(&T.rec[s].key, 0ull, key);
-          if (old != 0ull && old != key) continue;
-          if (old == 0ull) {   // first claimant: the voxel joins the list (at most one voxel per point: the list holds n entries)
-            const int v = atomicAdd(&ctr->n_vox[kind], 1);
-            vox_slot[v] = (int)s;
-            T.rec[s].count = v;
-          }
-          atomicAdd(&T.rec[s].pend_cnt, 1);
-          found = (int)s;
-          break;
+      unsigned s = (unsigned)mix64(key) & T.mask;
+      for (int probe = 0; probe < kMaxProbe; probe++, s = (s + 1) & T.mask) {
+        const u64 old = atomicCAS(&T.rec[s].key, 0ull, key);
+        if (old != 0ull && old != key) continue;
+        if (old == 0ull) {   // first claimant: the voxel joins the list (at most one voxel per point: the list holds n entries)
+          const int v = atomicAdd(&ctr->n_vox[kind], 1);
+          vox_slot[v] = (int)s;
+          T.rec[s].count = v;
         }
-        if (found < 0) atomicOr(&fr->error, kErrMapFull);   // no slot within the probe bound: the table is overloaded
+        atomicAdd(&T.rec[s].pend_cnt, 1);
+        found = (int)s;
+        break;
       }
+      if (found < 0) atomicOr(&fr->error, kErrMapFull);   // no slot within the probe bound: the table is overloaded
     }
     slot_of[i] = found;
   }
-  // the two drop counters: one add per wavefront
-  for (int d = 32; d > 0; d >>= 1) { n_out += __shfl_xor(n_out, d); n_bad += __shfl_xor(n_bad, d); }
-  if ((threadIdx.x & 63) == 0) {
-    if (n_out) atomicAdd((unsigned long long*)&res->n_outside_window[kind], (unsigned long long)n_out);
-    if (n_bad) atomicAdd((unsigned long long*)&res->n_nonfinite[kind], (unsigned long long)n_bad);
-  }
+  cloud_count_drops(n_out, n_bad, &res->n_outside_window[kind], &res->n_nonfinite[kind]);
 }
 
 // off[v]: first place of voxel v's segment, off[n_vox]: points placed; the table's key count and the result's voxel figures
-constexpr int kImportScanPer = 8;   // consecutive list entries per thread and round
 __global__ __launch_bounds__(256) void k_map_import_scan(VoxelTable T, int kind, const int* __restrict__ vox_slot, const ImportCtr* __restrict__ ctr,
                                                          int* __restrict__ off, vloam_map_import_result* res) {
   __shared__ int part[256];
   const int tid = threadIdx.x, nv = ctr->n_vox[kind];
-  int base = 0, most = 0;
-  for (int c0 = 0; c0 < nv; c0 += 256 * kImportScanPer) {
-    const int e0 = c0 + tid * kImportScanPer;
-    int cnt[kImportScanPer], sum = 0;
-#pragma unroll
-    for (int e = 0; e < kImportScanPer; e++) {
-      cnt[e] = e0 + e < nv ? T.rec[vox_slot[e0 + e]].pend_cnt : 0;
-      sum += cnt[e];
-      most = max(most, cnt[e]);
-    }
-    part[tid] = sum;
-    __syncthreads();
-    for (int d = 1; d < 256; d <<= 1) {   // inclusive scan of the 256 partial sums
-      const int add = tid >= d ? part[tid - d] : 0;
-      __syncthreads();
-      part[tid] += add;
-      __syncthreads();
-    }
-    int run = base + part[tid] - sum;
-#pragma unroll
-    for (int e = 0; e < kImportScanPer; e++) {
-      if (e0 + e < nv) off[e0 + e] = run;
-      run += cnt[e];
-    }
-    base += part[255];
-    __syncthreads();
-  }
-  for (int d = 32; d > 0; d >>= 1) most = max(most, __shfl_xor(most, d));
+  int most = 0;
+  const int base = cloud_scan(nv, [&](int e) { return T.rec[vox_slot[e]].pend_cnt; }, off, part, &most);
   if ((tid & 63) == 0 && most > 0) atomicMax(&res->max_per_voxel[kind], most);
   if (tid == 0) {
     off[nv] = base;
@@ -172,21 +107,11 @@ __global__ __launch_bounds__(256) void k_map_import_scatter(int n, VoxelTable T,
   }
 }
 
-// One lane: the voxel's points in the order of idx[0 .. cnt) -> the record of slot s (map_finalize_body's arithmetic: 0 + p0 + p1 ..., then / (float)n),
-// its occupancy block and its cube's count
+// One lane: the voxel's points in the order of idx[0 .. cnt) -> the record of slot s (cloud_fold from zero), its occupancy block and its cube's count
 __device__ __forceinline__ void import_fold(const VoxelTable& T, int s, const float4* __restrict__ pts, const int* idx, int cnt, int kind, const MapState* ms,
                                             MapFrame* fr, int* __restrict__ cube_cnt) {
-  float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
-  for (int a = 0; a < cnt; a++) { const float4 p = pts[idx[a]]; acc.x += p.x; acc.y += p.y; acc.z += p.z; acc.w += p.w; }
-  const float nn = (float)cnt;
-  acc.x = acc.x / nn; acc.y = acc.y / nn; acc.z = acc.z / nn; acc.w = acc.w / nn;
-  rec_store_value(&T.rec[s], acc, 1, 0);
-  const u64 key = T.rec[s].key;
-  int Ai, Aj, Ak;
-  unpack_cube(key, &Ai, &Aj, &Ak);
-  if (!map_publish_block(T, Ai, Aj, Ak, key_lx(key), key_ly(key), key_lz(key))) atomicOr(&fr->error, kErrMapFull);
-  const int wi = Ai + ms->cenW, wj = Aj + ms->cenH, wk = Ak + ms->cenD;   // inside the window: k_map_import_key keyed nothing else
-  atomicAdd(&cube_cnt[kind * kCubeNum + wi + kCubeW * wj + kCubeW * kCubeH * wk], 1);
+  rec_store_value(&T.rec[s], cloud_fold(make_float4(0.f, 0.f, 0.f, 0.f), pts, idx, cnt, cnt), 1, 0);
+  cloud_new_voxel(T, T.rec[s].key, kind, ms, fr, cube_cnt);
 }
 
 __global__ __launch_bounds__(256) void k_map_import_reduce(VoxelTable T, int kind, const float4* __restrict__ pts, const int* __restrict__ vox_slot,
@@ -201,12 +126,7 @@ __global__ __launch_bounds__(256) void k_map_import_reduce(VoxelTable T, int kin
       continue;
     }
     int* idx = seg + lo;   // the segment is this lane's alone: ordered in place
-    for (int a = 1; a < cnt; a++) {
-      const int x = idx[a];
-      int c = a - 1;
-      while (c >= 0 && idx[c] > x) { idx[c + 1] = idx[c]; c--; }
-      idx[c + 1] = x;
-    }
+    cloud_order_lane(idx, cnt);
     import_fold(T, vox_slot[v], pts, idx, cnt, kind, ms, fr, cube_cnt);
   }
 }
@@ -218,25 +138,7 @@ __global__ __launch_bounds__(256) void k_map_import_big(VoxelTable T, int kind, 
   const int tid = threadIdx.x, nb = min(ctr->n_big[kind], big_cap);
   for (int b = (int)blockIdx.x; b < nb; b += (int)gridDim.x) {
     const int v = big[b], lo = off[v], cnt = off[v + 1] - lo;
-    const int* ordered = seg + lo;
-    if (cnt <= kImportLdsSort) {
-      int P2 = 256;
-      while (P2 < cnt) P2 <<= 1;
-      for (int e = tid; e < P2; e += 256) a[e] = e < cnt ? (u64)(unsigned)seg[lo + e] : ~0ull;
-      __syncthreads();
-      block_bitonic_sort_u64(a, P2, tid, 256);
-      for (int e = tid; e < cnt; e += 256) seg[lo + e] = (int)a[e];
-    } else {
-      // indices are distinct: the number of smaller ones is the index's place
-      for (int e = tid; e < cnt; e += 256) {
-        const int x = seg[lo + e];
-        int r = 0;
-        for (int j = 0; j < cnt; j++) r += seg[lo + j] < x ? 1 : 0;
-        seg2[lo + r] = x;
-      }
-      ordered = seg2 + lo;
-    }
-    __syncthreads();   // the ordered segment is visible to the folding lane
+    const int* ordered = cloud_order_block(seg, seg2, lo, cnt, a);
     if (tid == 0) import_fold(T, vox_slot[v], pts, ordered, cnt, kind, ms, fr, cube_cnt);
     __syncthreads();   // a[] is free for the next voxel
   }

@@ -184,6 +184,9 @@ constexpr int kCarveMaxSweeps = 16, kCarveMaxPoints = 262144, kCarveMaxPixels = 
 constexpr int kCarveCounters = 6;          // examined, in_view, seen_through, confirmed, removed, skipped_raw
 struct CarveCounters { unsigned long long cnt[2][kCarveCounters]; unsigned long long n_removed; };
 struct MapCarve { char* base = nullptr; size_t bytes = 0; };
+// Map merge (vloam_map_merge; map_merge.hip): this map <- the clouds' frame, p' = R p + t (row-major R from the normalised quaternion, set on
+// the host as CarvePose's).  identity: q = (0, 0, 0, 1) and t = 0, the points are taken as they are
+struct MergeXf { double R[9], t[3]; int identity; };
 
 struct MapContext {
   MapState* state = nullptr;
@@ -300,6 +303,15 @@ void map_stack_enqueue_loc(MapContext* m, hipStream_t st, const float4* corner, 
 // h_result: host memory.  The sticky map-full error is the caller's to read (MapFrame::error).
 vloam_status map_import_run(MapContext* m, hipStream_t st, const double pose7[7], const void* const cloud[2], const int n[2], bool host_clouds,
                             vloam_map_import_result* h_result);
+// ---- map_merge.hip (a code object of its own): vloam_map_merge.  On the tables of a single-sequence handle, live or fresh, nothing in flight: cloud[kind]
+// (n[kind] packed float4 in the other map's frame; host memory with host_clouds, else device memory) goes through X into this map's frame, is keyed
+// against the current window and folded per voxel in input order onto what the voxel holds (apply), or only looked up (dry run).  Temporary
+// allocations only; synchronises st and frees them.  place_start: the window was never placed (map_window_never_placed) — an applied call then
+// starts the handle at the identity as an import would.  h_result: host memory.  The sticky map-full error is the caller's to read (MapFrame::error).
+vloam_status map_merge_run(MapContext* m, hipStream_t st, const MergeXf& X, const void* const cloud[2], const int n[2], bool host_clouds, bool apply,
+                           bool place_start, vloam_map_merge_result* h_result);
+// no sweep mapped, nothing imported or restored: the centre cube was never set (a placed one lies in [3, kCube - 3) on every axis)
+inline bool map_window_never_placed(const MapState& s) { return s.sweep_no == 0 && s.centerCube[0] == 0 && s.centerCube[1] == 0 && s.centerCube[2] == 0; }
 // ---- map_carve.hip (a code object of its own): vloam_map_carve.  With nothing of the handle in flight, on st: range images of the sweeps
 // (clouds[s]: n[s] packed float4, host memory with host_io, else device addresses), the vote over the records of the kinds in kind_mask of session
 // `session`, the removed points into `removed` (cap points; host memory with host_io) and, with apply (single-sequence handles), the removal and the
