@@ -1041,6 +1041,49 @@ vloam_status vloam_map_carve(vloam_handle* h, const vloam_carve_options* o, cons
 vloam_status vloam_map_carve_device(vloam_handle* h, const vloam_carve_options* o, const void* const* d_xyz_pad4, const int* n, const double* poses7,
                                     int n_sweeps, void* d_removed_xyzi4, long long cap, vloam_carve_result* res);
 
+/* Map archive: keep the points of cubes that roll out of the window.  The map is a window of 21 x 21 x 11 cubes of 50 m around the sensor; when
+ * it rolls, the points of the cubes that leave it are dropped for good (as the reference clears the slab that wraps).  On a handle that enabled
+ * the archive, every such point is first copied into a list on the device, so that the map of a whole drive can be saved.  Opt-in and read-only
+ * against the map: a handle that never enables it allocates and launches nothing of this, no kernel of a sweep changes, and an enabled handle
+ * computes byte for byte what it computed without (one more launch per mapped sweep on the mapping stream, which returns at once when the
+ * window did not roll).
+ *   A row is a live record of a cube outside the window the sweep has just placed, at the point vloam_get_map_kind would have returned for it
+ *   before that sweep; a voxel of un-merged raw points contributes those points.  Rows land in the device buffer in unspecified order within a
+ *   sweep; (sweep, kind, cube_k, cube_j, cube_i, tail, order) is unique per row, vloam_map_archive_get sorts by it, and within one cube and kind
+ *   that is the order vloam_get_map_kind had.  A voxel that was evicted, re-entered the window empty and was filled and evicted again has two
+ *   rows (vloam_map_import merges the points of one voxel into their centroid in input order).
+ * vloam_map_archive_enable: synchronises the handle and allocates capacity_rows rows and the counters (an allocation of its own, kept until
+ *   vloam_destroy); rows are collected from the next mapped sweep on.  Refusals (VLOAM_ERR_INVALID, each with its own vloam_last_error()): null
+ *   options or a wrong struct_size; capacity_rows < 1 or > 2^26; a null handle; n_sessions > 1; with_mapping == 0; a second enable.
+ * vloam_map_archive_info: synchronises; out4 = rows held, rows dropped since the last clear, capacity_rows, rolls seen since the enable.
+ * vloam_map_archive_get: synchronises, copies the rows held into rows (host memory, cap rows) sorted by the key above; *n is always the number
+ *   held; cap smaller than that: VLOAM_ERR_CAPACITY, nothing copied and nothing cleared.  clear == 1: rows held and rows dropped start over at 0.
+ * vloam_map_archive_device_ptr: the unsorted device buffer and the address of its counters (n_rows[0] rows held, n_rows[1] rows dropped); the
+ *   content is complete after vloam_sync().
+ * Before the enable the last three return VLOAM_ERR_INVALID.  A full archive never fails the sequence: rows beyond the capacity are not written
+ *   and counted as dropped.
+ * The archive is no part of a checkpoint: vloam_checkpoint_size / _save / _load behave exactly as without it, and a restored handle is not
+ *   enabled and holds no rows.  On a growable handle the launch follows growth steps and same-size reclamations (it takes the tables as they are
+ *   when the sweep is enqueued).  vloam_map_import, vloam_map_merge and vloam_map_localize never roll the window, so they never archive.
+ * Not offered: putting archived cubes back when the window returns (vloam_map_merge with the identity takes the rows), batched handles,
+ *   spilling to the host during a run. */
+typedef struct vloam_map_archive_options {
+  int struct_size;                     /* sizeof as compiled */
+  long long capacity_rows;             /* 1 .. 2^26; default 2^20 (32 MiB) */
+} vloam_map_archive_options;
+typedef struct vloam_map_archive_row {   /* 32 bytes */
+  float x, y, z, intensity;            /* the point vloam_get_map_kind would have returned */
+  unsigned int order;                  /* voxel (lz, ly, lx), 9 bits each, of a merged voxel; the arrival stamp of an un-merged point */
+  short cube_i, cube_j, cube_k;        /* absolute cube (0, 0, 0: the cube the sequence started in), independent of where the window is */
+  unsigned short flags;                /* bit 0: kind (0 corner, 1 surf); bit 1: tail (an un-merged arrival, behind the cube's voxel-ordered part) */
+  int sweep;                           /* 0-based index of the sweep whose roll evicted the point */
+} vloam_map_archive_row;
+void vloam_default_map_archive_options(vloam_map_archive_options* o);   /* 2^20 rows */
+vloam_status vloam_map_archive_enable(vloam_handle* h, const vloam_map_archive_options* o);
+vloam_status vloam_map_archive_info(vloam_handle* h, long long out4[4]);
+vloam_status vloam_map_archive_get(vloam_handle* h, vloam_map_archive_row* rows, long long cap, long long* n, int clear);
+vloam_status vloam_map_archive_device_ptr(vloam_handle* h, void** d_rows, int** d_n_rows);
+
 #ifdef __cplusplus
 }
 #endif

@@ -246,6 +246,12 @@ def main():
     ap.add_argument("--place-db", action="store_true",
                     help="keep a place database (vloam_place_enable, default geometry): every sweep's raw cloud is added, tagged with its frame index; with "
                          "--save-map DIR it is written as DIR/place_db.npz (desc, tags, the geometry, and per row the mapping pose of that frame, poses [n, 7])")
+    ap.add_argument("--archive-rolled", type=int, nargs="?", const=0, default=None, metavar="CAPACITY_ROWS",
+                    help="keep the map points of cubes that roll out of the 21 x 21 x 11 window (vloam_map_archive_enable; CAPACITY_ROWS rows of 32 bytes, "
+                         "default 2^20) and print rows held / dropped at the end; with --save-map DIR corner.npy and surf.npy hold the archive's rows of "
+                         "that kind first (in vloam_map_archive_get's order), then the window's export: the map of the whole drive in the same format.  A "
+                         "voxel that was evicted, re-entered the window empty and was filled again appears twice; --load-map (vloam_map_import) merges "
+                         "the points of one voxel into their centroid in input order")
     ap.add_argument("--relocalize-global", metavar="\"EXT_XY STEP_XY YAW_DEG STEP_DEG [TOP_K]\"",
                     help="with --load-map DIR --localize-only: no start pose is needed — the first sweep is matched against DIR/place_db.npz "
                          "(vloam_place_query), the best row's pose turned by the match's yaw shift becomes the start pose, and the sweep is relocalised "
@@ -317,6 +323,8 @@ def main():
         if len(w) != 7:
             sys.exit("--merge-pose \"qx qy qz qw tx ty tz\": seven numbers")
         a.merge_pose = [float(v) for v in w]
+    if a.archive_rolled is not None and a.localize_only:
+        sys.exit("--archive-rolled keeps what a run that MAPS rolls out of the window: not with --localize-only")
     if a.resume and a.load_map:
         sys.exit("--resume and --load-map both fill a fresh handle: choose one")
     if a.start_pose and not a.load_map:
@@ -343,6 +351,8 @@ def main():
         hd.pose_cov_enable()
     if a.place_db:
         hd.place_enable(capacity=max(n, 1))
+    if a.archive_rolled is not None:
+        hd.map_archive_enable(capacity_rows=a.archive_rolled or None)
     if a.vloam:
         if real_images:   # PointCloudUtil::loadTransformations (point_cloud_util.cpp:5-116)
             hd.vo_set_calib(*kio.load_transformations(a.calib_cam_to_cam, a.calib_velo_to_cam))
@@ -488,9 +498,18 @@ def main():
         print("carved the map with sweeps %d .. %d (min_votes %d): %d corner / %d surf voxels removed of %d / %d examined (%d / %d confirmed)" % (
             first, n - 1, votes, res["removed"][0], res["removed"][1], res["examined"][0], res["examined"][1], res["confirmed"][0], res["confirmed"][1]))
         np.save(os.path.join(a.out, "carved.npy"), removed)
+    if a.archive_rolled is not None:
+        archived, info = hd.map_archive(), hd.map_archive_info()
+        print("map archive: %d rows held of %d (%d corner / %d surf, %d rolls), %d dropped" % (
+            info["rows"], info["capacity_rows"], int(np.count_nonzero((archived["flags"] & vl.MAP_ARCHIVE_KIND) == 0)),
+            int(np.count_nonzero(archived["flags"] & vl.MAP_ARCHIVE_KIND)), info["rolls"], info["dropped"]))
     if a.save_map:
         os.makedirs(a.save_map, exist_ok=True)
         halves = [hd.get_map_kind(k) for k in (0, 1)]
+        if a.archive_rolled is not None:   # the rolled-out points of each kind in front of the window's
+            for k in (0, 1):
+                r = archived[(archived["flags"] & vl.MAP_ARCHIVE_KIND) == k]
+                halves[k] = np.concatenate([np.stack([r["x"], r["y"], r["z"], r["intensity"]], 1), halves[k]])
         np.save(os.path.join(a.save_map, "corner.npy"), halves[0])
         np.save(os.path.join(a.save_map, "surf.npy"), halves[1])
         row = hd.trajectory(n - 1, 1)[0]

@@ -10,6 +10,8 @@ after a short warm-up.  For A/B-ing a kernel change; bench.py remains the measur
       the single sequence with neither product, with pose information, and with pose information + covariance rows (vloam_pose_cov_enable), alternately
   python tools/throughput_probe.py --no-batch --steps 2000 --map-log2 20 --map-grow-ab 3
       the single sequence on a fixed handle and on a growable one (vloam_map_options::grow) of the same size, alternately
+  python tools/throughput_probe.py --no-batch --steps 200 --map-archive-ab 3
+      the single sequence without and with the map archive (vloam_map_archive_enable), alternately
   python tools/throughput_probe.py --grow-step 18,21
       one forced growth step of both tables from 2^18 and from 2^21 slots with the warm-up's map in them (for a kernel trace: --procs 1)"""
 import argparse
@@ -45,6 +47,7 @@ ap.add_argument("--pose-info-ab", type=int, default=0, help="that many off / on 
 ap.add_argument("--pose-cov-ab", type=int, default=0, help="that many off / pose information / pose information + covariance rows (vloam_pose_cov_enable) triples of "
                                                         "single-sequence runs (then of --sessions batches unless --no-batch); replaces the normal run")
 ap.add_argument("--map-grow-ab", type=int, default=0, help="that many fixed / growable pairs of single-sequence runs at --map-log2, fixed first; replaces the normal run")
+ap.add_argument("--map-archive-ab", type=int, default=0, help="that many off / on pairs of single-sequence runs, the map archive (vloam_map_archive_enable) off first; replaces the normal run")
 ap.add_argument("--grow-step", default="", help="comma-separated log2 sizes: a growable handle of that size, --warm sweeps, one forced growth step, timed on the host; replaces the normal run")
 ap.add_argument("--map-log2", type=int, default=22, help="map_capacity_log2 of the handles (voxel table slots)")
 ap.add_argument("--procs", type=int, default=32, help="worker processes for the synthesis (1 under rocprofv3: it follows forked children)")
@@ -79,11 +82,14 @@ def run(B, pub=PUB):
     pub = dict(pub)
     pose_info = pub.pop("pose_info", 0)
     pose_cov = pub.pop("pose_cov", 0)
+    map_archive = pub.pop("map_archive", 0)
     h = vl.Handle(0, n_sessions=B, with_mapping=1, max_frames=a.warm + a.steps + 8, map_capacity_log2=a.map_log2, **pub)
     if pose_info:
         h.enable_pose_info()
     if pose_cov:
         h.pose_cov_enable()
+    if map_archive:
+        h.map_archive_enable()
     step = (lambda k: h.process_scan_device(ptr(k), npts)) if B == 1 else (lambda k: h.batch_process_scan_device([ptr(k)] * B, [npts] * B))
     for k in range(a.warm):
         step(k)
@@ -98,6 +104,7 @@ def run(B, pub=PUB):
     note = "   sweep_log 1" if pub.get("sweep_log") else ""
     note += "   pose_info 1" if pose_info else ""
     note += "   pose_cov 1" if pose_cov else ""
+    note += "   map_archive 1 %s" % (h.map_archive_info(),) if map_archive else ""
     if pub.get("map_pub_number") or pub.get("publish_registered_cloud"):
         note += "   published: map every %d, registered cloud %d" % (pub["map_pub_number"], pub["publish_registered_cloud"])
     print("B = %2d: %8.0f scans/s   (%.1f us per step)%s" % (B, B * a.steps / dt, 1e6 * dt / a.steps, note), flush=True)
@@ -188,6 +195,11 @@ if a.pose_cov_ab:
             run(B, dict(pose_info=0))
             run(B, dict(pose_info=1))
             run(B, dict(pose_info=1, pose_cov=1))
+    sys.exit(0)
+if a.map_archive_ab:
+    for _ in range(a.map_archive_ab):
+        run(1, dict(map_archive=0))
+        run(1, dict(map_archive=1))
     sys.exit(0)
 if a.sweep_log_ab:
     for B in [1] + ([] if a.no_batch else [a.sessions]):

@@ -168,6 +168,18 @@ CARVE_RESULT_DTYPE = np.dtype([
 CARVE_MAX_SWEEPS = 16
 
 
+class MapArchiveOptions(C.Structure):
+    """vloam_map_archive_options (c_api.h; vloam_map_archive_enable)."""
+    _fields_ = [("struct_size", C.c_int), ("capacity_rows", C.c_longlong)]
+
+
+# vloam_map_archive_row (c_api.h), 32 bytes: a point evicted by a roll of the window
+MAP_ARCHIVE_ROW_DTYPE = np.dtype([
+    ("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("intensity", "<f4"), ("order", "<u4"), ("cube_i", "<i2"), ("cube_j", "<i2"), ("cube_k", "<i2"),
+    ("flags", "<u2"), ("sweep", "<i4")])
+MAP_ARCHIVE_KIND, MAP_ARCHIVE_TAIL = 1, 2   # bits of flags
+
+
 # vloam_sweep_record (c_api.h): 32 ints then 8 doubles, 192 bytes
 SWEEP_RECORD_DTYPE = np.dtype([
     ("frame", "<i4"), ("error_bits", "<i4"), ("flags", "<i4"), ("n_in", "<i4"), ("n_cloud", "<i4"), ("n_sharp", "<i4"), ("n_less_sharp", "<i4"),
@@ -1212,6 +1224,38 @@ class Handle:
         self._chk(self.L.vloam_map_carve_device(self.h, C.byref(opt), ptrs, n, None if p is None else _fp(p), ns,
                                                 C.c_void_p(removed.data_ptr()) if cap else None, C.c_longlong(cap), _fp(res)))
         return self._carve_result(res)
+
+    def map_archive_enable(self, capacity_rows=None):
+        """vloam_map_archive_enable: from the next mapped sweep on, the points of cubes that roll out of the map's window are kept in a list of
+        capacity_rows rows (None: the default, 2^20) on the device instead of being lost.  Single-sequence handles with mapping, once."""
+        opt = MapArchiveOptions()
+        self.L.vloam_default_map_archive_options(C.byref(opt))
+        if capacity_rows is not None:
+            opt.capacity_rows = int(capacity_rows)
+        self._chk(self.L.vloam_map_archive_enable(self.h, C.byref(opt)))
+
+    def map_archive_info(self):
+        """vloam_map_archive_info: rows held, rows dropped since the last clear (the archive was full), the capacity, rolls seen.  Synchronises."""
+        v = np.zeros(4, dtype=np.int64)
+        self._chk(self.L.vloam_map_archive_info(self.h, _fp(v)))
+        return dict(rows=int(v[0]), dropped=int(v[1]), capacity_rows=int(v[2]), rolls=int(v[3]))
+
+    def map_archive(self, clear=False):
+        """vloam_map_archive_get: the rows held as a structured array (MAP_ARCHIVE_ROW_DTYPE), sorted by (sweep, kind, cube_k, cube_j, cube_i,
+        tail, order) — within one cube and kind the order get_map_kind() had.  clear: rows held and rows dropped start over.  Synchronises."""
+        n = C.c_longlong(0)
+        st = self.L.vloam_map_archive_get(self.h, None, C.c_longlong(0), C.byref(n), 0)
+        if st != ERR_CAPACITY:
+            self._chk(st)
+        out = np.zeros(max(n.value, 1), dtype=MAP_ARCHIVE_ROW_DTYPE)
+        self._chk(self.L.vloam_map_archive_get(self.h, _fp(out), C.c_longlong(n.value), C.byref(n), 1 if clear else 0))
+        return out[:n.value]
+
+    def map_archive_device_ptr(self):
+        """(device address of the unsorted rows, device address of the counters: int32 rows held, rows dropped); complete after sync()."""
+        p, c = C.c_void_p(), C.c_void_p()
+        self._chk(self.L.vloam_map_archive_device_ptr(self.h, C.byref(p), C.byref(c)))
+        return p.value, c.value
 
     def published_map(self):
         """The latest /laser_cloud_map the mapping stream published (vloam_limits::map_pub_number): (float32 [n, 4], 0-based sweep index),

@@ -174,6 +174,7 @@ static vloam_status enqueue_map(vloam_handle* h, int frame) {
   // set behind k_map_register.  The published map reads the voxel tables only, so it leaves the event where it is.
   const bool publishes = map_publishes(&h->map, skip), reads_set = h->map.pub.cloud_on != 0;
   if (h->sweep_log) sweep_log_map_begin_launch(h->s_map, h->se, h->log_scratch, h->map.frame, h->map.stack_info[cur], skip, &h->prof);
+  if (h->map.archive) h->map.archive->frame = frame;
   vloam_status s = map_enqueue(&h->map, h->cfg, h->s_map, h->sr[cur], h->lo, sub_pose ? h->sub_row : h->traj + (size_t)frame * 14, skip, cur, &h->prof,
                                reads_set ? nullptr : h->ev_map[cur]);
   if (s != VLOAM_OK && h->map.grow && h->map.grow->failed_log2) {   // a growth step's allocation: the old table stays in use, the sweep's mapping is enqueued by a later call

@@ -1,6 +1,6 @@
 // Host-only: the handle behind the C ABI and what the translation units of the host side share (c_api.cpp: creation and destruction;
 // capi_sweep.cpp: the sweep pipeline; capi_frame.cpp: coupled frames, images, VO; capi_results.cpp: getters and debug hooks; capi_rows.cpp: the
-// per-sweep row products; capi_ckpt.cpp: checkpoints; capi_query.cpp: map queries; capi_localize.cpp: localisation; capi_import.cpp: map import; capi_merge.cpp: map merge; capi_score.cpp: pose scores and relocalisation; capi_place.cpp: place recognition; capi_carve.cpp: map clean-up).  No .hip file includes this.  Helpers that cross files live in namespace vloam (mangled,
+// per-sweep row products; capi_ckpt.cpp: checkpoints; capi_query.cpp: map queries; capi_localize.cpp: localisation; capi_import.cpp: map import; capi_merge.cpp: map merge; capi_score.cpp: pose scores and relocalisation; capi_place.cpp: place recognition; capi_carve.cpp: map clean-up; capi_archive.cpp: map archive).  No .hip file includes this.  Helpers that cross files live in namespace vloam (mangled,
 // out of the C symbol list); a helper of one file is static there.
 #pragma once
 #include "../../include/vloam_hip/c_api.h"

@@ -188,6 +188,16 @@ struct MapCarve { char* base = nullptr; size_t bytes = 0; };
 // the host as CarvePose's).  identity: q = (0, 0, 0, 1) and t = 0, the points are taken as they are
 struct MergeXf { double R[9], t[3]; int identity; };
 
+// Map archive (vloam_map_archive_enable; map_archive.hip): the rows of evicted points and their counters, one allocation of its own; null on a
+// handle that never enabled it.  frame: the sweep map_enqueue is about to be called for (set by its caller; the rows carry it)
+struct MapArchive {
+  char* base = nullptr;
+  int* cnt = nullptr;                      // [4] rows held | rows dropped since the last clear | rolls seen | -
+  vloam_map_archive_row* rows = nullptr;   // [cap]
+  long long cap = 0;
+  int frame = 0;
+};
+
 struct MapContext {
   MapState* state = nullptr;
   MapFrame* frame = nullptr;
@@ -236,6 +246,7 @@ struct MapContext {
   }
   MapLocalize* loc = nullptr;   // localisation scratch: null until the first vloam_map_localize* call (host-side; not rebased: single-sequence handles only)
   MapCarve* carve = nullptr;    // map clean-up scratch: null until the first vloam_map_carve* call (host-side, like loc)
+  MapArchive* archive = nullptr;   // map archive: null until vloam_map_archive_enable (host-side, like loc)
   MapPub pub;              // published clouds (off on a default handle)
   float4* registered = nullptr;  // full-resolution cloud in the map frame, on request
   long long* assoc_cyc = nullptr;  // [2][8] debug: phase cycle sums of k_map_assoc per outer round
@@ -319,6 +330,11 @@ inline bool map_window_never_placed(const MapState& s) { return s.sweep_no == 0 
 vloam_status map_carve_run(MapContext* m, int session, hipStream_t st, const CarveGeom& G, int kind_mask, const void* const* clouds, const int* n,
                            const CarvePose* poses, bool host_io, void* removed, long long cap, bool apply, CarveCounters* h_out);
 void map_carve_free(MapContext* m);
+// ---- map_archive.hip (a code object of its own): vloam_map_archive_*.  alloc: rows + counters, zeroed on st and waited for.  enqueue: k_map_archive
+// on st, for map_enqueue — between k_map_prepare and k_map_finalize of a mapped sweep of a single-sequence handle with m->archive set.
+vloam_status map_archive_alloc(MapContext* m, hipStream_t st, long long capacity_rows);
+void map_archive_free(MapContext* m);
+void map_archive_enqueue(const MapContext* m, hipStream_t st);
 // ---- map_grow.hip: growable handles (m->grow != null).  map_force_grow: test hook, one doubling of both tables now (between two sweeps, on the mapping stream).
 // map_grow_release: frees retired buffers whose grow chain has finished (hipEventQuery); call with nothing of the handle in flight — hipFree
 // synchronises the device.

@@ -892,6 +892,7 @@ vloam_status map_init(MapContext* m, hipStream_t st) {
 void map_destroy(MapContext* m) {
   map_localize_free(m);
   map_carve_free(m);
+  map_archive_free(m);
   if (m->grow) map_grow_destroy(m);
   if (m->host_flags) { (void)hipHostFree(m->host_flags); m->host_flags = nullptr; }
   for (int k = 0; k < 2; k++)
@@ -959,6 +960,7 @@ vloam_status map_enqueue(MapContext* m, const vloam_config& cfg, hipStream_t st,
 #undef VL_PREPARE
   if (skip_frame) return hipGetLastError() == hipSuccess ? VLOAM_OK : VLOAM_ERR_HIP;
   m->pub.mapped++;
+  if (m->archive) map_archive_enqueue(m, st);   // the points of cubes this sweep's roll evicts, before k_map_finalize purges them (map_archive.hip)
   for (int outer = 0; outer < 2; outer++) {  // LM:458
     // lanes per query of the 5-NN search: a batch fills the chip with 16-lane groups (four queries per wavefront); a single sequence
     // (9 000 queries on 5 120 wave slots) is quickest with two per wavefront.  VLOAM_MAP_ASSOC_LANES = 16 / 32 / 64 overrides (A/B runs;
