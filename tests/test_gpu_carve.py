@@ -66,7 +66,7 @@ def test_dry_run_equals_the_model(reference):
         got = {k: int(r["res"][k][kind]) for k in COUNTERS}
         print("kind %d: device %s, model %s" % (kind, got, r["model"][kind][1]))
         assert got == r["model"][kind][1]
-        assert int(r["res"]["skipped_raw"][kind]) == 0   # every return lies inside the valid block: no un-merged raw points
+        assert int(r["res"]["skipped_raw"][kind]) == 0   # every return lies inside the valid block: no un-merged raw points (with them: tests/test_gpu_carve_raw.py)
         assert same_rows(r["maps"][kind], r["after"][kind]), "a dry run leaves the map as it was"
     assert r["res"]["n_removed_out"] == want.shape[0] == r["removed"].shape[0] > 0
     assert same_rows(cs.sorted_rows(r["removed"]), cs.sorted_rows(want))

@@ -59,6 +59,25 @@ def qrot(q, v):
     return v + w * c + np.cross(u, c)
 
 
+def dry_run_is_the_mapping(vl, h, r, qm, tm, k):
+    """r: the dry run of the sweep in progress; (qm, tm): what laser_mapping() of that sweep returned right behind it.  Returns whether it solved.
+    (Also the assertion of tests/test_gpu_carve_raw.py, on a map that holds raw voxels.)"""
+    assert bits(r["q_map"]) == bits(qm) and bits(r["t_map"]) == bits(tm), "sweep %d: dry run %s %s, mapping %s %s" % (k, r["q_map"], r["t_map"], qm, tm)
+    st = h.map_state()
+    assert list(r["n_stack"]) == [st["n_corner_stack"], st["n_surf_stack"]] and list(r["n_map"]) == [st["n_map_corner"], st["n_map_surf"]]
+    assert list(r["center_cube"]) == list(st["centerCube"])
+    assert bool(r["flags"] & vl.LOC_SOLVED) == bool(st["do_optimize"]) and bool(r["flags"] & vl.LOC_NOT_OPTIMIZED) != bool(st["do_optimize"])
+    assert r["error_bits"] == 0 and not r["flags"] & (vl.LOC_WOULD_ROLL | vl.LOC_DEGRADED)
+    if st["do_optimize"]:
+        for outer in (0, 1):
+            d = h.map_debug(outer)
+            assert list(r["n_factors"][outer]) == [d["corner_idx"].size, d["surf_idx"].size], (k, outer)
+            assert r["iterations"][outer] == d["rec"]["trace"].shape[0] and r["termination"][outer] == d["rec"]["termination"]
+            assert bits(r["initial_cost"][outer]) == bits(np.float64(d["rec"]["initial_cost"])) and bits(r["final_cost"][outer]) == bits(np.float64(d["rec"]["final_cost"]))
+        assert bits(r["q_guess"]) != bits(r["q_map"]) or bits(r["t_guess"]) != bits(r["t_map"])
+    return bool(st["do_optimize"])
+
+
 def test_dry_run_of_the_sweep_in_progress_is_the_mapping_that_follows(vl, sweeps):
     h = vl.Handle(0, with_mapping=1)
     solved = 0
@@ -68,20 +87,7 @@ def test_dry_run_of_the_sweep_in_progress_is_the_mapping_that_follows(vl, sweeps
         qm, tm = h.laser_mapping()
         if r is None:
             continue
-        assert bits(r["q_map"]) == bits(qm) and bits(r["t_map"]) == bits(tm), "sweep %d: dry run %s %s, mapping %s %s" % (k, r["q_map"], r["t_map"], qm, tm)
-        st = h.map_state()
-        assert list(r["n_stack"]) == [st["n_corner_stack"], st["n_surf_stack"]] and list(r["n_map"]) == [st["n_map_corner"], st["n_map_surf"]]
-        assert list(r["center_cube"]) == list(st["centerCube"])
-        assert bool(r["flags"] & vl.LOC_SOLVED) == bool(st["do_optimize"]) and bool(r["flags"] & vl.LOC_NOT_OPTIMIZED) != bool(st["do_optimize"])
-        assert r["error_bits"] == 0 and not r["flags"] & (vl.LOC_WOULD_ROLL | vl.LOC_DEGRADED)
-        if st["do_optimize"]:
-            solved += 1
-            for outer in (0, 1):
-                d = h.map_debug(outer)
-                assert list(r["n_factors"][outer]) == [d["corner_idx"].size, d["surf_idx"].size], (k, outer)
-                assert r["iterations"][outer] == d["rec"]["trace"].shape[0] and r["termination"][outer] == d["rec"]["termination"]
-                assert bits(r["initial_cost"][outer]) == bits(np.float64(d["rec"]["initial_cost"])) and bits(r["final_cost"][outer]) == bits(np.float64(d["rec"]["final_cost"]))
-            assert bits(r["q_guess"]) != bits(r["q_map"]) or bits(r["t_guess"]) != bits(r["t_map"])
+        solved += dry_run_is_the_mapping(vl, h, r, qm, tm, k)
     assert solved >= 3, solved
     h.close()
 

@@ -7,7 +7,7 @@ of the window, taken before that sweep's LaserMapping::input).  That bookkeeping
     surf     65 848 rows: sweep 41: 2,  42: 1 257, 55: 514,   56: 14 685, 57: 34 983, 58: 14 407
 in 346 (sweep, kind, cube) groups; the first eviction is on sweep 41.  (The walk's first leg moves the window without a cube that holds points
 leaving it; the returns through mapped places evict.)  None of these rows is an un-merged arrival (the sweeps reach no cube outside the valid
-block), so the tail bit is zero in every row checked here.  The tests assert that both kinds are present and that the set spans at least two sweeps.
+block), so the tail bit is zero in every row checked here; tests/test_gpu_archive_tails.py runs the walk at 140 m, where it is not.  The tests assert that both kinds are present and that the set spans at least two sweeps.
 
 Every drive hands the device the ORACLE's odometry pose plus the walk's offset, so what is compared is the mapping stage and the archive."""
 import ctypes as C
