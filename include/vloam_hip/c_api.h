@@ -571,6 +571,30 @@ vloam_status vloam_batch_process_frame_image(vloam_handle* h, const float* const
  *   stage 3 (VO): 0 buckets, 1 per-match rows, 2 LM record */
 vloam_status vloam_debug_get(vloam_handle* h, int stage, int item, void* buf, long long cap_bytes, long long* n_bytes);
 
+/* Test hook: the shared device primitives on caller-supplied arguments (dev_probe.hip; tests/test_gpu_dev_probe.py compares the results with
+ * the host build of the same headers bit for bit).  `in` and `out` are HOST pointers to n elements in the layout of the probe; out_bytes
+ * must be exactly n * (the probe's output element size).  The call needs no handle: it allocates, copies, launches one trivially parallel
+ * kernel on a stream of its own, synchronises and frees.  An unknown `which`, n < 0, a null pointer with n > 0 or a wrong out_bytes returns
+ * VLOAM_ERR_INVALID before anything is allocated or launched; n == 0 returns VLOAM_OK the same way.
+ *   which                      in (per element)                 out (per element)        calls
+ *   VLOAM_PROBE_ATANF          f32 x                            f32                      fd_atanf(x)
+ *   VLOAM_PROBE_ATAN2F         f32 y, x                         f32                      fd_atan2f(y, x)
+ *   VLOAM_PROBE_ELEV           f32 x, y, z                      f32                      fd_atanf(z / sqrtf(x * x + y * y))
+ *   VLOAM_PROBE_TF_ROUNDTRIP   f64 q[4] (xyzw, any norm)        f64 m[9], q[4]           tf_set_rotation, tf_get_rotation of the result
+ *   VLOAM_PROBE_TF_GETROT      f64 m[9] (any matrix)            f64 q[4]                 tf_get_rotation
+ *   VLOAM_PROBE_TF_CHAIN       f64 a.m[9], a.o[3], b.m, b.o     f64 m[9], o[3]           tf_mul(a, tf_inverse(b))
+ *   VLOAM_PROBE_ASSOC          f32 p[4]; f64 q[4], t[3] (72 B)  f32 [4]                  associate_to_map(p, q, t)
+ *   VLOAM_PROBE_QUAT           f64 a[4], b[4], v[3]             f64 r[4], o[3]           dquat_mul(a, b), dquat_rot(a, v)
+ *   VLOAM_PROBE_SORT(P2, T)    u64 [P2]: one problem            u64 [P2], ascending      block_bitonic_sort_u64(a, P2, tid, T), one workgroup of
+ *                                                                                        T lanes per problem; only the (P2, T) pairs the
+ *                                                                                        library's own kernels use (the table in dev_probe.hip) */
+enum {
+  VLOAM_PROBE_ATANF = 1, VLOAM_PROBE_ATAN2F = 2, VLOAM_PROBE_ELEV = 3, VLOAM_PROBE_TF_ROUNDTRIP = 4, VLOAM_PROBE_TF_GETROT = 5,
+  VLOAM_PROBE_TF_CHAIN = 6, VLOAM_PROBE_ASSOC = 7, VLOAM_PROBE_QUAT = 8
+};
+#define VLOAM_PROBE_SORT(P2, T) (0x40000000 | ((T) << 16) | ((P2) >> 4))   /* P2 <= 16384, a multiple of 256; T 256 or 512 */
+vloam_status vloam_debug_probe(int device, int which, const void* in, long long n, void* out, long long out_bytes);
+
 /* Per-kernel HIP-event timer for bench.py's roofline line: brackets every launch of the kernel whose __global__
  * symbol is `name` (e.g. "k_lo_assoc") with an event pair on the handle's own stream.  "" disables.
  * vloam_profile_read returns the summed milliseconds and launch count since the last read. */

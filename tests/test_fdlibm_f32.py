@@ -4,7 +4,9 @@ The reference computes a return's scan line and relative time from glibc's float
 header restates glibc's (fdlibm's) algorithm so that the device produces the same bits.  Compiled here for the host with g++
 -ffp-contract=off (the flag the device translation unit is built with) and run over 2^24 arguments per generator: random bit patterns of
 every binade, the arguments LiDAR returns produce, break points, signed zeros, infinities, NaN.  No GPU involved; the GPU side of the same
-claim is tests/test_gpu_scan_registration.py (intensity and startOri / endOri bit for bit against the oracle, which calls the C library).
+claim is tests/test_gpu_dev_probe.py (the device build of the header against this host build, bit for bit on 2^20 arguments per function,
+through vloam_debug_probe) and, at the arguments a drive produces, tests/test_gpu_scan_registration.py (intensity and startOri / endOri bit
+for bit against the oracle, which calls the C library).
 The check is meaningful on a glibc that still builds atanf / atan2f from the fdlibm float sources (<= 2.40; this image: 2.35)."""
 import os
 import platform

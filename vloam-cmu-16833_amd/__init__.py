@@ -303,6 +303,35 @@ def _fp(a):
     return a.ctypes.data_as(C.c_void_p)
 
 
+# vloam_debug_probe (c_api.h): probe id -> (bytes per input element, bytes per output element)
+PROBE_ATANF, PROBE_ATAN2F, PROBE_ELEV, PROBE_TF_ROUNDTRIP, PROBE_TF_GETROT, PROBE_TF_CHAIN, PROBE_ASSOC, PROBE_QUAT = 1, 2, 3, 4, 5, 6, 7, 8
+PROBE_ELEMENT_BYTES = {PROBE_ATANF: (4, 4), PROBE_ATAN2F: (8, 4), PROBE_ELEV: (12, 4), PROBE_TF_ROUNDTRIP: (32, 104), PROBE_TF_GETROT: (72, 32),
+                       PROBE_TF_CHAIN: (192, 96), PROBE_ASSOC: (72, 16), PROBE_QUAT: (88, 56)}
+# the (P2, workgroup size) pairs of the sort probe: those the library's own kernels call block_bitonic_sort_u64 with (dev_probe.hip)
+PROBE_SORT_PAIRS = tuple((p2, 256) for p2 in (256, 512, 1024, 2048, 4096)) + tuple((p2, 512) for p2 in (256, 512, 1024, 2048, 4096, 8192, 16384))
+
+
+def probe_sort(p2, t):
+    """VLOAM_PROBE_SORT(P2, T) of c_api.h."""
+    return 0x40000000 | (int(t) << 16) | (int(p2) >> 4)
+
+
+def debug_probe(which, data, device=0):
+    """Test hook (vloam_debug_probe): the device primitive `which` on the elements of `data` (any array whose bytes are whole input elements in
+    the probe's layout; for a sort probe, whole problems of P2 u64 keys).  Returns the raw output bytes as a uint8 array."""
+    a = np.ascontiguousarray(data)
+    in_b, out_b = PROBE_ELEMENT_BYTES.get(which, (8, 8))
+    if a.nbytes % in_b:
+        raise ValueError("%d bytes are no whole number of %d-byte elements" % (a.nbytes, in_b))
+    n = a.nbytes // in_b
+    out = np.zeros(max(n * out_b, 8), dtype=np.uint8)
+    L = lib()
+    st = L.vloam_debug_probe(C.c_int(device), C.c_int(which), _fp(a), C.c_longlong(n), _fp(out), C.c_longlong(n * out_b))
+    if st != VLOAM_OK:
+        raise VloamError(st, L.vloam_last_error().decode())
+    return out[:n * out_b]
+
+
 class Handle:
     """One sequence on one GPU (``vloam_handle``)."""
 

@@ -13,7 +13,9 @@
 // order, no fused multiply-adds on the x86-64 baseline.  Restated below operation for operation (constants by their bit patterns); the
 // translation unit is built with -ffp-contract=off, so the device rounds every product and sum exactly like that build.
 // tests/test_fdlibm_f32.py compiles this header for the host and compares it with the C library's atanf / atan2f bit for bit on 2^26
-// arguments per function (all binades, the break points, signed zeros, infinities, NaN).
+// arguments per function (all binades, the break points, signed zeros, infinities, NaN); tests/test_gpu_dev_probe.py holds the DEVICE build
+// to that host build bit for bit on 2^20 arguments per function (dev_probe.hip: denormals, the early-return thresholds, the divide and sqrtf
+// of the elevation expression) — which is where "no contraction, correctly rounded f32 divide, no denormal flush" is asserted.
 //
 //   Original notice of the restated sources:  Copyright (C) 1993 by Sun Microsystems, Inc. All rights reserved.  Developed at SunPro, a
 //   Sun Microsystems, Inc. business.  Permission to use, copy, modify, and distribute this software is freely granted, provided that this
